@@ -8,9 +8,13 @@ MuJoCo-equivalent physics, obs, reward, termination, truncation) + SB3 auto-rese
 U[-1,1)^4 pre-generated in HBM (action_space.sample(), debug_training.py:111 / configs[1]).
 The timed loop replays hipGraphs of the step launches (launch-bound at this size).
 
-Prints ONE JSON line (rank 0). Also measured in the same run and reported as extra keys:
-per-launch kernel time from HIP event pairs (-> roofline), the 1M-env HBM-bound point, and the
-CPU baseline (the float64 oracle, 1 core, bounded sample) -- see DESIGN.md "Measurement".
+Prints ONE JSON line (rank 0). A plain run does only what the headline needs: set up, warm up,
+time the K steps, write the outputs (--dump-outputs DIR) and print the line. With --full the same
+run also measures, and reports as extra keys: per-launch kernel time from HIP event pairs
+(-> roofline), the PPO rollout and end-to-end phases, the other SURVEY configs, the 1M-env and
+4M-env HBM points, and the CPU baselines (the float64 oracle, bounded samples) -- see DESIGN.md
+"Measurement". The --no-* / --*-envs / --e2e-* / --rollout-steps options select among those
+extra measurements and have no effect without --full.
 """
 from __future__ import annotations
 
@@ -32,6 +36,7 @@ METRIC = "env-steps/sec (whole node) at 65 536 hover envs, 1/2/4/8 MI355X"
 ENVS_PER_GPU = 65536
 BYTES_PER_ENV_STEP = 278  # state r/w 2x104, action 16, obs+rew+term+trunc 54
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs writes at most this much in all
 
 
 def _quad_step_fn(env):
@@ -151,7 +156,10 @@ def _run_rank(args, rank, world, local_rank):
     n_act = min(args.action_batches, args.steps + args.warmup)
     actions = [env.random_actions(k) for k in range(n_act)]  # resident in HBM
     step = _quad_step_fn(env)
-    chunk = args.graph_chunk if args.steps % args.graph_chunk == 0 else args.steps
+    # exactly --steps launches: `whole` replays of a graph of `chunk` launches, then one graph of the
+    # `rest` launches (a step count that is no multiple of --graph-chunk costs no giant graph)
+    chunk = max(1, min(args.graph_chunk, args.steps))
+    whole, rest = divmod(args.steps, chunk)
 
     def region(graphs):
         """barrier + synchronize, the replays between two HIP events (on the stream the kernels
@@ -174,12 +182,19 @@ def _run_rank(args, rank, world, local_rank):
     # run through the timed region's own host path: its first execution in a process costs ~10 us
     # of host time (event records, synchronize; profiles/r02/first_region.txt), setup, not steps
     g = _graph_of(step, actions, args.warmup, chunk)
+    timed = [g] * whole
+    if rest:
+        timed.append(_graph_of(step, actions, args.warmup + whole * chunk, rest))
     if args.warmup > 0:
-        gw = _graph_of(step, actions, 0, args.warmup)
-        region([gw])
+        wchunk = min(args.warmup, max(chunk, 100))
+        gw = _graph_of(step, actions, 0, wchunk)
+        warm = [gw] * (args.warmup // wchunk)
+        if args.warmup % wchunk:
+            warm.append(_graph_of(step, actions, 0, args.warmup % wchunk))
+        region(warm)
 
     # timed region: exactly K steps, barrier + synchronize on both sides
-    elapsed, e0, e1 = region([g] * (args.steps // chunk))
+    elapsed, e0, e1 = region(timed)
     # the closing barrier follows this rank's clock stop: its RCCL latency (tens of us against a
     # ~130 us 20-step region) is not step work; the MAX over ranks below is the slowest rank's K steps
     if world > 1:
@@ -191,10 +206,15 @@ def _run_rank(args, rank, world, local_rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    res = dict(elapsed=elapsed, region_us=region_us, kernel=_kernel_name(env), symbol=_kernel_symbol(env))
+    if args.dump_outputs:  # what the last timed step returned, before anything else steps the envs
+        _dump_outputs(env, args.dump_outputs, rank)
+    if not args.full:
+        del actions, g, timed
+        env.close()
+        return res
     # per-launch kernel time (roofline) on the same kernel, stream and data
-    res = dict(elapsed=elapsed, region_us=region_us,
-               kernel_us=_gated_kernel_us(step, actions, args.kernel_launches),
-               kernel=_kernel_name(env), symbol=_kernel_symbol(env), launch_floor_us=_launch_floor_us())
+    res.update(kernel_us=_gated_kernel_us(step, actions, args.kernel_launches), launch_floor_us=_launch_floor_us())
     if world > 1:  # every rank's own figures: a slow GPU or link shows here, not only in the MAX
         res["per_rank"] = _per_rank(dict(elapsed_s=own_elapsed, region_us=region_us, kernel_us=res["kernel_us"]),
                                     ("elapsed_s", "region_us", "kernel_us"))
@@ -213,7 +233,7 @@ def _run_rank(args, rank, world, local_rank):
             "hover_ctbr_65536": _kernel_rate(65536, "hover", "RateControlWrapper", dev, args.seed)}
         if world == 1:  # a one-process PPO (at world > 1 its construction would join the ranks' collectives)
             res["configs"]["config1_train_py_on_gpu"] = _train_py_scale(dev, args.seed)
-    del actions, g
+    del actions, g, timed
     env.close()
     if rank == 0:
         torch.cuda.empty_cache()
@@ -222,6 +242,32 @@ def _run_rank(args, rank, world, local_rank):
         if args.dram_envs > 0:  # true HBM: 1.2 GB per launch, 4.5x the 256 MB Infinity Cache
             res["dram"] = _large_point(args.dram_envs, dev, args.seed, 40)
     return res
+
+
+def _dump_outputs(env, out_dir: str, rank: int) -> None:
+    """--dump-outputs: the arrays a caller of the timed step receives from its last launch (obs,
+    reward, terminated, truncated, terminal_observation of every env: ~7 MB at 65,536 envs), one
+    float32 DIR/<name>.npy each (rank r > 0: DIR/<name>_rank<r>.npy). The envs, their seed and the
+    action batches are functions of the arguments alone, so two runs with the same arguments
+    write the same files. Past DUMP_MAX_BYTES in all, a fixed seeded sample of the env rows is
+    written instead, with its row numbers as sample_rows.npy (float64)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {"obs": env.obs, "reward": env.reward, "terminated": env.terminated,
+            "truncated": env.truncated, "terminal_observation": env.terminal_obs}
+    n = env.num_envs
+    row_bytes = 4 * sum(t[0].numel() for t in outs.values()) + 8  # + the row number
+    rows = None
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        outs["sample_rows"] = torch.from_numpy(rows.astype(np.float64))
+    sel = None if rows is None else torch.from_numpy(rows).to(env.obs.device)
+    for name, t in outs.items():
+        if sel is not None and name != "sample_rows":
+            t = t[sel]
+        a = t.detach().to(torch.float64 if name == "sample_rows" else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), np.ascontiguousarray(a))
 
 
 def _mem_floor_fn(env):
@@ -883,9 +929,16 @@ def main():
     ap.add_argument("--e2e-epochs", type=int, default=20)
     ap.add_argument("--check-launch", action="store_true",
                     help="test the rank launch only (gloo, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the kernel time and roofline, the rollout and "
+                         "end-to-end phases, the other configs, the large-batch points and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0 or args.graph_chunk < 1:
+        ap.error("--steps and --graph-chunk must be >= 1, --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(_launch_ranks(args))  # one child per GPU; this process never touches the GPU
@@ -919,9 +972,6 @@ def main():
         return
     n_total = args.envs * world
     value = n_total * args.steps / res["elapsed"]
-    kus = res["kernel_us"]
-    achieved = BYTES_PER_ENV_STEP * args.envs / (kus * 1e-6) / 1e9
-    traffic = _pmc_traffic(res["symbol"], args.envs)
     line = {
         "metric": METRIC, "value": value, "unit": "env-steps/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup,
@@ -932,14 +982,23 @@ def main():
                                "envs/GPU), hipGraph replay",
                    "envs_per_gpu": args.envs, "global_envs": n_total,
                    "parallelism": f"env-shard x{world} (no data-path collective)"},
-        "device_us_per_step": res["region_us"],
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS,
-                     "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_pmc": traffic,
-                     "kernel": res["kernel"], "kernel_symbol": res["symbol"], "kernel_us": kus,
-                     "algorithmic_bytes_per_launch": BYTES_PER_ENV_STEP * args.envs,
-                     "issue": _pmc_issue(res["symbol"], args.envs), **_launch_terms(res, args.envs)},
+        "device_us_per_step": res["region_us"], "kernel": res["kernel"], "kernel_symbol": res["symbol"],
+        "full": args.full,
     }
+    if args.dump_outputs:
+        line["dump_outputs"] = args.dump_outputs
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        return
+    kus = res["kernel_us"]
+    achieved = BYTES_PER_ENV_STEP * args.envs / (kus * 1e-6) / 1e9
+    traffic = _pmc_traffic(res["symbol"], args.envs)
+    line["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS,
+                        "traffic": traffic["bytes_per_launch"] if traffic else None, "traffic_pmc": traffic,
+                        "kernel": res["kernel"], "kernel_symbol": res["symbol"], "kernel_us": kus,
+                        "algorithmic_bytes_per_launch": BYTES_PER_ENV_STEP * args.envs,
+                        "issue": _pmc_issue(res["symbol"], args.envs), **_launch_terms(res, args.envs)}
     if "per_rank" in res:
         line["per_rank"] = res["per_rank"]
     if "rollout" in res:

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # (the rank-0-only configs run too: nothing rank 0 does alone may join a collective)
-SMALL = ["--steps", "20", "--warmup", "5", "--graph-chunk", "10", "--kernel-launches", "20",
+SMALL = ["--full", "--steps", "20", "--warmup", "5", "--graph-chunk", "10", "--kernel-launches", "20",
          "--large-envs", "0", "--dram-envs", "0", "--rollout-steps", "0",
          "--no-cpu-baseline", "--e2e-iters", "1", "--e2e-steps", "16", "--e2e-epochs", "1"]
 

@@ -20,7 +20,7 @@ run() {  # name timeout cmd...
 STEPS=${STEPS:-pytest,smoke,bench,rehearsal,prof}
 [[ $STEPS == *pytest* ]] && run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ${PYTEST_K:-}
 [[ $STEPS == *smoke* ]] && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[[ $STEPS == *bench* ]] && run bench 600 python bench.py --gpus 1 --steps 20 --warmup 5
-[[ $STEPS == *rehearsal* ]] && QUAD_BENCH_REHEARSAL=1 run rehearsal 300 python bench.py --gpus 2 --steps 20 --warmup 5 --no-configs --no-cpu-baseline --rollout-steps 0 --large-envs 0 --e2e-iters 1 --e2e-steps 64 --e2e-epochs 2
-[[ $STEPS == *prof* ]] && run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof -o run -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --e2e-iters 0 --no-configs
+[[ $STEPS == *bench* ]] && run bench 600 python bench.py --full --gpus 1 --steps 20 --warmup 5
+[[ $STEPS == *rehearsal* ]] && QUAD_BENCH_REHEARSAL=1 run rehearsal 300 python bench.py --full --gpus 2 --steps 20 --warmup 5 --no-configs --no-cpu-baseline --rollout-steps 0 --large-envs 0 --e2e-iters 1 --e2e-steps 64 --e2e-epochs 2
+[[ $STEPS == *prof* ]] && run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "${OUT:-bench_out}/prof" -o run -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --e2e-iters 0 --no-configs
 echo "=== done"
