@@ -428,7 +428,9 @@ int quad_permutation(int64_t n, uint64_t seed, int64_t* out, void* stream);
 int64_t quad_ppo_workspace_bytes(int32_t batch);
 /* Which kernel quad_ppo_grad launches: 1 = k_ppo_grad_x3 (bf16 MFMA on three-piece splits of every
  * f32 operand, f32-level error; the default), 0 = k_ppo_grad (f32-input MFMA; environment
- * QUADENV_LEARNER=f32, read on every call). Both meet the same accuracy bar. */
+ * QUADENV_LEARNER=f32, read on every call). Both meet the same accuracy bar. A captured update
+ * (ppo.py graph_update, the default) replays the launches of the form -- and of the
+ * QUADENV_LEARNER_SPLIT setting -- active at capture; a later change takes effect at the next capture. */
 int quad_ppo_grad_form(void);
 int quad_ppo_grad(const QuadPolicyParams* params, const QuadPPOBatch* b, const QuadPolicyGrads* grads,
                   void* workspace, int64_t workspace_bytes, void* stream);

@@ -551,16 +551,19 @@ def test_fused_update_two_ranks_stay_in_sync():
     env.close()
 
 
-def test_split_kernels_match_combined(monkeypatch):
+@pytest.mark.parametrize("B", [128, 4096, 32768])
+def test_split_kernels_match_combined(monkeypatch, B):
     """QUADENV_LEARNER_SPLIT=1 (one kernel per net, two streams) computes the same bits as the
-    combined k_ppo_grad_x3 launch: same block slices, same arithmetic."""
+    combined launch: same block slices, same arithmetic. At 32,768 rows the combined launch is
+    k_ppo_grad_x3; at 128 and 4,096 it is k_ppo_grad_x3_sep (2 and 64 blocks per net, train.py's
+    minibatches are the former), whose partial-slot mapping this pins."""
     from uav_reinforcement_learning_control_amd.ppo.learner import FusedLearner, _ordered
     from uav_reinforcement_learning_control_amd.ppo.ppo import PPOConfig
     monkeypatch.delenv("QUADENV_LEARNER", raising=False)
     cfg = PPOConfig()
     pol = _policy(11)
     obs, act, logp_old, adv, ret = _buffers(pol, 40000, 11, cfg.clip_range)
-    idx = _index(pol, obs, 40000, 32768, 12)
+    idx = _index(pol, obs, 40000, B, 12)
     out = []
     for split in ("0", "1"):
         monkeypatch.setenv("QUADENV_LEARNER_SPLIT", split)

@@ -33,7 +33,8 @@ def child(lib):
     adv = torch.randn(M, device="cuda", generator=g)
     ret = torch.randn(M, device="cuda", generator=g)
     perm = torch.randperm(M, device="cuda", generator=g)
-    fl = FusedLearner(pol, cfg.clip_range, cfg.ent_coef, cfg.vf_coef)
+    norm = os.environ.get("X3_BITS_NORM", "1") != "0"
+    fl = FusedLearner(pol, cfg.clip_range, cfg.ent_coef, cfg.vf_coef, normalize_advantage=norm)
     stats = torch.zeros(4, device="cuda")
     h = hashlib.sha256()
     for mb in range(3):

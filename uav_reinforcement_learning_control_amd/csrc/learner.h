@@ -41,7 +41,7 @@ struct GArgs {
   int32_t nbc, per_block_c;         // critic: nbc blocks of per_block_c rows
   float clip, inv_batch, vf_coef;
   float* dump;  // diagnostics only (k_ppo_grad*_dump): [2 nets][batch][256] hidden pre-activations
-  const void* wimg;  // bf16x3 form: the W2 fragments of every wave as bf16 pieces (k_split_w2, WIMG_BYTES)
+  const void* wimg;  // bf16x3 form: the W2 fragments of every wave as bf16 pieces (k_x3_prep, WIMG_BYTES)
 };
 
 struct Layout {
@@ -49,7 +49,7 @@ struct Layout {
   int64_t part_bytes, adv_bytes, wimg_bytes;
 };
 
-// the bf16x3 form's pre-split W2 image (learner_x3.hip k_split_w2): 2 nets x 4 waves x 2 uses x
+// the bf16x3 form's pre-split W2 image (learner_x3.hip k_x3_prep / split_w2_unit): 2 nets x 4 waves x 2 uses x
 // 8 k-steps x 3 pieces x 64 lanes x 16 bytes, after the partial image in the workspace
 constexpr int64_t WIMG_BYTES = int64_t(2) * 4 * 2 * 8 * 3 * 64 * 16;
 
@@ -132,6 +132,177 @@ __device__ __forceinline__ void adv_stats_block(const float* __restrict__ adv, c
 // arithmetic as the gradient launch
 __device__ __forceinline__ void dump_pre(float* dump, int net, int batch, int pos, int layer, int neuron, float v) {
   dump[(size_t(net) * size_t(batch) + size_t(pos)) * 256 + size_t(128 * layer + neuron)] = v;
+}
+
+// ---- What the two kernel bodies (body<> of learner.hip and learner_x3.hip) share. The products, the LDS
+// layouts and the per-row accumulation (a*b + c fuses only within one source expression) stay in the bodies.
+
+// The actor's advantage normalization constants: a fixed-order float64 tree over the pre-pass
+// partials (adv_stats_block), then mean and 1 / (std + 1e-8) as SB3 forms them. {0, 1} for the
+// critic and without normalization. Needs 256 threads and two double[LB] in LDS.
+struct AdvNorm { float mu, rden; };
+template <int NOUT>
+__device__ __forceinline__ AdvNorm adv_norm(const GArgs& g, double* red0, double* red1) {
+  const int tid = threadIdx.x;
+  float adv_mu = 0.f, adv_den = 1.f;
+  if (NOUT == ACT && g.adv_part) {
+    red0[tid] = g.adv_part[2 * tid];
+    red1[tid] = g.adv_part[2 * tid + 1];
+    __syncthreads();
+    for (int o = LB / 2; o > 0; o >>= 1) {
+      if (tid < o) { red0[tid] += red0[tid + o]; red1[tid] += red1[tid + o]; }
+      __syncthreads();
+    }
+    const double n = double(g.batch), s = red0[0], s2 = red1[0];
+    const double var = fmax((s2 - s * s / n) / (n - 1.0), 0.0);
+    adv_mu = float(s / n);
+    adv_den = float(sqrt(var)) + 1e-8f;
+  }
+  return AdvNorm{adv_mu, 1.f / adv_den};
+}
+
+// b1, b2 and the head weights neuron-major ([128][4], zero past NOUT) into LDS, at float offsets
+// o_b1 / o_b2 / o_w3t of the body's image L (indexed as the bodies index it: same address arithmetic)
+template <int NOUT>
+__device__ __forceinline__ void stage_small_weights(const NetW& W, float* L, int o_b1, int o_b2, int o_w3t) {
+  for (int i = threadIdx.x; i < H; i += LB) {
+    L[o_b1 + i] = W.b0[i];
+    L[o_b2 + i] = W.b1[i];
+#pragma unroll
+    for (int k = 0; k < 4; k++) L[o_w3t + 4 * i + k] = k < NOUT ? W.w2[k * H + i] : 0.f;
+  }
+}
+
+// Row staging, one round ahead: a block's slice [s0, s1) of the minibatch in rounds of RND rows.
+// Threads 0..191 gather the observation rows (float4 each), threads 192..255 the row scalars; the
+// minibatch indices are loaded two rounds ahead, so no gather waits on its index load. Rows past
+// the slice stage zeros (and are masked as invalid).
+template <int NOUT>
+struct RowStage {
+  const GArgs& g;
+  int tid, s0, s1, rounds, srow;
+  float4 pf;
+  float pfs[3];
+
+  __device__ __forceinline__ RowStage(const GArgs& g_, int blk) : g(g_) {
+    tid = threadIdx.x;
+    const int per_block = NOUT == ACT ? g.per_block : g.per_block_c;
+    s0 = blk * per_block;
+    s1 = min(g.batch, s0 + per_block);
+    rounds = s1 > s0 ? (s1 - s0 + RND - 1) / RND : 0;
+    srow = tid < 3 * RND ? tid / 3 : tid - 3 * RND;
+    pf = make_float4(0.f, 0.f, 0.f, 0.f);
+    pfs[0] = pfs[1] = pfs[2] = 0.f;
+  }
+  // the minibatch index of this thread's row of round rd (-1: past the slice); written as `rd < rounds &&
+  // i < s1` the round test folds into a select and three bf16x3 kernels allocate 3-12 more or fewer registers
+  __device__ __forceinline__ int64_t index_of(int rd) const {
+    if (rd >= rounds) return -1;
+    const int i = s0 + rd * RND + srow;
+    return i < s1 ? g.idx[i] : int64_t(-1);
+  }
+  __device__ __forceinline__ void gather(int64_t row) {
+    pf = make_float4(0.f, 0.f, 0.f, 0.f);
+    pfs[0] = pfs[1] = pfs[2] = 0.f;
+    if (row < 0) return;
+    if (tid < 3 * RND) {
+      pf = reinterpret_cast<const float4*>(g.obs)[size_t(row) * 3 + tid % 3];
+    } else if (NOUT == ACT) {
+      pf = reinterpret_cast<const float4*>(g.act)[row];
+      pfs[0] = g.logp_old[row];
+      pfs[1] = g.adv[row];
+    } else {
+      pfs[2] = g.ret[row];
+    }
+  }
+  // threads 192..255: the scalars into row srow of the [64][8] image `sci` (action 4, old logp, adv, return)
+  __device__ __forceinline__ void store_scalars(float* sci) const {
+    *reinterpret_cast<float4*>(sci + srow * 8) = pf;
+    sci[srow * 8 + 4] = pfs[0]; sci[srow * 8 + 5] = pfs[1]; sci[srow * 8 + 6] = pfs[2];
+  }
+};
+
+// head output of row e: the four waves' partial sums ([4][64][4] at float offset `o` of L) in a
+// fixed order, + bias
+template <int NOUT>
+__device__ __forceinline__ void head_out(const float* L, int o, int e, const float (&b3)[NOUT], float (&out)[NOUT]) {
+#pragma unroll
+  for (int k = 0; k < NOUT; k++)
+    out[k] = (((L[o + e * 4 + k] + L[o + (RND + e) * 4 + k]) + L[o + (2 * RND + e) * 4 + k]) +
+              L[o + (3 * RND + e) * 4 + k]) + b3[k];
+}
+
+// The loss of SB3's PPO.train (stable_baselines3/ppo/ppo.py, third-party) for one minibatch row:
+// what the row contributes to the gradient and to the logged statistics. `sc` is the row's 8 staged
+// scalars (action 4, old logp, adv, return), `out` the head output (mean / value).
+template <int NOUT>
+struct RowTerms {
+  float dd[NOUT];  // dL/d(head output); 0 on an invalid row
+  // actor: dL/dlogp (0 on an invalid row), (a - mean) / std, the policy loss term, 1 if |ratio - 1| > clip
+  float dlp, z[ACT], pg, clipped;
+  float diff;  // critic: value - return
+};
+template <int NOUT>
+__device__ __forceinline__ RowTerms<NOUT> row_terms(const GArgs& g, const float (&out)[NOUT], const float* sc,
+                                                    const float (&ls)[ACT], const float (&isd)[ACT], AdvNorm an,
+                                                    bool valid) {
+  RowTerms<NOUT> t;
+  if constexpr (NOUT == ACT) {
+    const float4 a4 = *reinterpret_cast<const float4*>(sc);
+    const float a4k[4] = {a4.x, a4.y, a4.z, a4.w};
+    float lp = 0.f;
+#pragma unroll
+    for (int k = 0; k < ACT; k++) {
+      t.z[k] = (a4k[k] - out[k]) * isd[k];
+      lp += -0.5f * t.z[k] * t.z[k] - ls[k] - 0.91893853320467274f;
+    }
+    // ratio = exp(logp - old) on the hardware exp2 (~1 ulp; the correctly rounded expf is ~10 VALU)
+    const float r = __builtin_amdgcn_exp2f((lp - sc[4]) * 1.44269504088896341f);
+    const float A = g.adv_part ? (sc[5] - an.mu) * an.rden : sc[5];
+    const float cr = fminf(fmaxf(r, 1.f - g.clip), 1.f + g.clip);
+    const float sa = A * r, sb = A * cr;
+    // d min(sa, sb): the unclipped branch where it is the smaller, half of each on a tie (torch.min's
+    // backward), else the clipped branch, whose derivative is r's inside the clip range only
+    const float w1 = sa < sb ? 1.f : (sa == sb ? 0.5f : 0.f);
+    const float inr = (r >= 1.f - g.clip && r <= 1.f + g.clip) ? 1.f : 0.f;
+    t.dlp = valid ? -g.inv_batch * A * (w1 + (1.f - w1) * inr) * r : 0.f;
+#pragma unroll
+    for (int k = 0; k < ACT; k++) t.dd[k] = t.dlp * t.z[k] * isd[k];
+    t.pg = -fminf(sa, sb);
+    t.clipped = fabsf(r - 1.f) > g.clip ? 1.f : 0.f;
+  } else {
+    t.diff = out[0] - sc[6];
+    t.dd[0] = valid ? 2.f * g.vf_coef * g.inv_batch * t.diff : 0.f;
+  }
+  return t;
+}
+
+// The block's per-row sums v (head bias gradient [NOUT], log_std gradient [ACT], pg sum, vf sum, clipped
+// count), already summed over wave 0's lanes, into its partial image P. The lane sum stays in the bodies: in
+// here it changes the bf16x3 round loop's FMA packing (+2.7 % time, profiles/r07/learner_shared_helpers.txt)
+template <int NOUT>
+__device__ __forceinline__ void store_row_sums(float* P, const float (&v)[NOUT + ACT + 3]) {
+  const int b3off = NOUT == ACT ? P_B3A : P_B3C;
+#pragma unroll
+  for (int k = 0; k < NOUT; k++) P[b3off + k] = v[k];
+  if (NOUT == ACT) {
+#pragma unroll
+    for (int k = 0; k < ACT; k++) P[P_LS + k] = v[NOUT + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; k++) P[P_STATS + k] = v[NOUT + ACT + k];
+}
+
+// Host: opt kernels k0 and k1 into `bytes` of dynamic LDS on the current device, once per device
+// (`once`: the current device's entry of the call site's table). False: hipFuncSetAttribute failed.
+template <class K0, class K1>
+bool opt_in_dynamic_lds(bool& once, K0* k0, K1* k1, int bytes) {
+  constexpr hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
+  if (once) return true;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k0), attr, bytes) != hipSuccess ||
+      hipFuncSetAttribute(reinterpret_cast<const void*>(k1), attr, bytes) != hipSuccess)
+    return false;
+  return once = true;
 }
 
 }  // namespace lrn

@@ -78,29 +78,10 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
 
   // ---- advantage statistics of the minibatch (actor): fixed-order tree over the pre-pass partials
   __shared__ double red[2][LB];
-  float adv_mu = 0.f, adv_den = 1.f;
-  if (NOUT == ACT && g.adv_part) {
-    red[0][tid] = g.adv_part[2 * tid];
-    red[1][tid] = g.adv_part[2 * tid + 1];
-    __syncthreads();
-    for (int o = LB / 2; o > 0; o >>= 1) {
-      if (tid < o) { red[0][tid] += red[0][tid + o]; red[1][tid] += red[1][tid + o]; }
-      __syncthreads();
-    }
-    const double n = double(g.batch), s = red[0][0], s2 = red[1][0];
-    const double var = fmax((s2 - s * s / n) / (n - 1.0), 0.0);
-    adv_mu = float(s / n);
-    adv_den = float(sqrt(var)) + 1e-8f;
-  }
-  const float adv_rden = 1.f / adv_den;
+  const AdvNorm an = adv_norm<NOUT>(g, red[0], red[1]);
 
   // ---- stage the small weights in LDS, the wave's W1 / W2 fragments in registers
-  for (int i = tid; i < H; i += LB) {
-    L[L_B1 + i] = W.b0[i];
-    L[L_B2 + i] = W.b1[i];
-#pragma unroll
-    for (int k = 0; k < 4; k++) L[L_W3T + 4 * i + k] = k < NOUT ? W.w2[k * H + i] : 0.f;
-  }
+  stage_small_weights<NOUT>(W, L, L_B1, L_B2, L_W3T);
   float b3[NOUT];
 #pragma unroll
   for (int k = 0; k < NOUT; k++) b3[k] = W.b2[k];
@@ -113,10 +94,10 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
     w2r[s] = W.w1[n_own * H + kperm(s, h)];
     w2c[s] = W.w1[kperm(s, h) * H + n_own];
   }
-  float ls[ACT], sd[ACT], isd[ACT];  // isd: the row loop multiplies (a full-precision division is ~10 VALU)
+  float ls[ACT], isd[ACT];  // isd: the row loop multiplies (a full-precision division is ~10 VALU)
   if constexpr (NOUT == ACT) {
 #pragma unroll
-    for (int k = 0; k < ACT; k++) { ls[k] = g.log_std[k]; sd[k] = expf(ls[k]); isd[k] = 1.f / sd[k]; }
+    for (int k = 0; k < ACT; k++) { ls[k] = g.log_std[k]; isd[k] = 1.f / expf(ls[k]); }
   }
 
   // accumulators (whole launch)
@@ -138,54 +119,26 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
   for (int k = 0; k < ACT; k++) dls[k] = 0.f;
   const bool acc_lane = w == 0 && h == 0;  // one lane per row accumulates the per-row sums
 
-  const int per_block = NOUT == ACT ? g.per_block : g.per_block_c;
-  const int s0 = blk * per_block;
-  const int s1 = min(g.batch, s0 + per_block);
-  const int rounds = s1 > s0 ? (s1 - s0 + RND - 1) / RND : 0;
-  // Row staging, one round ahead: threads 0..191 gather the observation rows (float4 each),
-  // threads 192..255 the row scalars; the minibatch indices are loaded two rounds ahead, so no
-  // gather waits on its index load. Rows past the slice stage zeros (and are masked as invalid).
-  const int srow = tid < 3 * RND ? tid / 3 : tid - 3 * RND;
-  auto index_of = [&](int rd) -> int64_t {
-    const int i = s0 + rd * RND + srow;
-    return (rd < rounds && i < s1) ? g.idx[i] : int64_t(-1);
-  };
-  float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
-  float pfs[3] = {0.f, 0.f, 0.f};
-  auto gather = [&](int64_t row) {
-    pf = make_float4(0.f, 0.f, 0.f, 0.f);
-    pfs[0] = pfs[1] = pfs[2] = 0.f;
-    if (row < 0) return;
-    if (tid < 3 * RND) {
-      pf = reinterpret_cast<const float4*>(g.obs)[size_t(row) * 3 + tid % 3];
-    } else if (NOUT == ACT) {
-      pf = reinterpret_cast<const float4*>(g.act)[row];
-      pfs[0] = g.logp_old[row];
-      pfs[1] = g.adv[row];
-    } else {
-      pfs[2] = g.ret[row];
-    }
-  };
-  gather(index_of(0));
-  int64_t next_row = index_of(1);
+  RowStage<NOUT> stage(g, blk);  // the block's slice of the minibatch, staged one round ahead
+  stage.gather(stage.index_of(0));
+  int64_t next_row = stage.index_of(1);
   __syncthreads();
 
-  for (int rd = 0; rd < rounds; rd++) {
-    const int base = s0 + rd * RND;
+  for (int rd = 0; rd < stage.rounds; rd++) {
+    const int base = stage.s0 + rd * RND;
     float* OBSI = L + L_OBS + (rd & 1) * RND * SO;
     float* SCI = L + L_SC + (rd & 1) * RND * 8;
     if (tid < 3 * RND) {
-      float* o = OBSI + srow * SO + 4 * (tid % 3);
-      o[0] = pf.x; o[1] = pf.y; o[2] = pf.z; o[3] = pf.w;
+      float* o = OBSI + stage.srow * SO + 4 * (tid % 3);
+      o[0] = stage.pf.x; o[1] = stage.pf.y; o[2] = stage.pf.z; o[3] = stage.pf.w;
     } else {
-      *reinterpret_cast<float4*>(SCI + srow * 8) = pf;
-      SCI[srow * 8 + 4] = pfs[0]; SCI[srow * 8 + 5] = pfs[1]; SCI[srow * 8 + 6] = pfs[2];
+      stage.store_scalars(SCI);
     }
-    gather(next_row);           // round rd + 1, in flight during this round
-    next_row = index_of(rd + 2);
+    stage.gather(next_row);     // round rd + 1, in flight during this round
+    next_row = stage.index_of(rd + 2);
     bool valid[2];
 #pragma unroll
-    for (int t = 0; t < 2; t++) valid[t] = base + 32 * t + l32 < s1;
+    for (int t = 0; t < 2; t++) valid[t] = base + 32 * t + l32 < stage.s1;
     __syncthreads();  // B1: observation image complete; the previous round's readers are done
 
     // ---- L1 (E form): h1^T block w of both tiles -> H1 image
@@ -257,39 +210,19 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
     for (int t = 0; t < 2; t++) {
       const int e = 32 * t + l32;
       float out[NOUT];
+      head_out<NOUT>(L, L_PART, e, b3, out);
+      const RowTerms<NOUT> rt = row_terms<NOUT>(g, out, SCI + e * 8, ls, isd, an, valid[t]);
 #pragma unroll
-      for (int k = 0; k < NOUT; k++)
-        out[k] = (((L[L_PART + e * 4 + k] + L[L_PART + (RND + e) * 4 + k]) + L[L_PART + (2 * RND + e) * 4 + k]) +
-                  L[L_PART + (3 * RND + e) * 4 + k]) + b3[k];
-      const float4 a4 = *reinterpret_cast<const float4*>(SCI + e * 8);
-      const float a4k[4] = {a4.x, a4.y, a4.z, a4.w};
-      if constexpr (NOUT == ACT) {
-        float z[ACT], lp = 0.f;
+      for (int k = 0; k < NOUT; k++) d[t][k] = rt.dd[k];
+      if (acc_lane && valid[t]) {  // the row sums (branch form: the select form spills here)
+        if constexpr (NOUT == ACT) {
+          st[0] += rt.pg;
+          st[2] += rt.clipped;
 #pragma unroll
-        for (int k = 0; k < ACT; k++) {
-          z[k] = (a4k[k] - out[k]) * isd[k];
-          lp += -0.5f * z[k] * z[k] - ls[k] - 0.91893853320467274f;
+          for (int k = 0; k < ACT; k++) dls[k] += rt.dlp * (rt.z[k] * rt.z[k] - 1.f);
+        } else {
+          st[1] += rt.diff * rt.diff;
         }
-        // ratio = exp(logp - old) on the hardware exp2 (~1 ulp; the correctly rounded expf is ~10 VALU)
-        const float r = __builtin_amdgcn_exp2f((lp - SCI[e * 8 + 4]) * 1.44269504088896341f);
-        const float A = g.adv_part ? (SCI[e * 8 + 5] - adv_mu) * adv_rden : SCI[e * 8 + 5];
-        const float cr = fminf(fmaxf(r, 1.f - g.clip), 1.f + g.clip);
-        const float sa = A * r, sb = A * cr;
-        const float w1 = sa < sb ? 1.f : (sa == sb ? 0.5f : 0.f);
-        const float inr = (r >= 1.f - g.clip && r <= 1.f + g.clip) ? 1.f : 0.f;
-        const float dlp = valid[t] ? -g.inv_batch * A * (w1 + (1.f - w1) * inr) * r : 0.f;
-#pragma unroll
-        for (int k = 0; k < ACT; k++) d[t][k] = dlp * z[k] * isd[k];
-        if (acc_lane && valid[t]) {
-          st[0] += -fminf(sa, sb);
-          st[2] += fabsf(r - 1.f) > g.clip ? 1.f : 0.f;
-#pragma unroll
-          for (int k = 0; k < ACT; k++) dls[k] += dlp * (z[k] * z[k] - 1.f);
-        }
-      } else {
-        const float diff = out[0] - SCI[e * 8 + 6];
-        d[t][0] = valid[t] ? 2.f * g.vf_coef * g.inv_batch * diff : 0.f;
-        if (acc_lane && valid[t]) st[1] += diff * diff;
       }
       if (acc_lane) {
 #pragma unroll
@@ -392,7 +325,8 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
 #pragma unroll
       for (int r = 0; r < NOUT; r++) P[P_W3 + r * H + 32 * w + 16 * b + lane] = dW3[b][r];
   }
-  if (w == 0) {  // lanes 0..31 hold the per-row sums (lanes 32..63 hold zeros)
+  // lanes 0..31 of wave 0 hold the per-row sums (lanes 32..63 hold zeros)
+  if (w == 0) {
     float v[NOUT + ACT + 3];
     int nv = 0;
 #pragma unroll
@@ -408,17 +342,7 @@ __device__ __forceinline__ void body(const GArgs& g, float* __restrict__ L, int 
       for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
       v[q] = x;
     }
-    if (lane == 0) {
-      const int b3off = NOUT == ACT ? P_B3A : P_B3C;
-#pragma unroll
-      for (int k = 0; k < NOUT; k++) P[b3off + k] = v[k];
-      if (NOUT == ACT) {
-#pragma unroll
-        for (int k = 0; k < ACT; k++) P[P_LS + k] = v[NOUT + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++) P[P_STATS + k] = v[NOUT + ACT + k];
-    }
+    if (lane == 0) store_row_sums<NOUT>(P, v);
   }
 }
 
@@ -650,7 +574,9 @@ int64_t quad_ppo_workspace_bytes(int32_t batch) {
 }
 
 // 1: the bf16x3 form (k_ppo_grad_x3, default), 0: the f32-input MFMA form (k_ppo_grad);
-// QUADENV_LEARNER=f32 selects the latter (read per call, so a process can A/B both)
+// QUADENV_LEARNER=f32 selects the latter. Read on every call, so a process can A/B both with eager
+// calls; a captured update (ppo.py graph_update, the default) replays the launches of the form -- and
+// of the QUADENV_LEARNER_SPLIT setting -- that were active at capture, whatever the environment says later
 int quad_ppo_grad_form(void) {
   const char* v = std::getenv("QUADENV_LEARNER");
   return (v && std::strcmp(v, "f32") == 0) ? 0 : 1;
@@ -686,14 +612,8 @@ int ppo_grad_impl(const QuadPolicyParams* p, const QuadPPOBatch* b, const QuadPo
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return lfail(QUAD_EHIP, "hipGetDevice failed");
   const int lds_bytes = L_TOTAL * int(sizeof(float));
-  if (!x3 && !opted[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds_bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_dump), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            lds_bytes) != hipSuccess)
-      return lfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    opted[dev] = true;
-  }
+  if (!x3 && !opt_in_dynamic_lds(opted[dev], &k_ppo_grad, &k_ppo_grad_dump, lds_bytes))
+    return lfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* adv_part = static_cast<double*>(workspace);
   float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.adv_bytes);

@@ -12,7 +12,7 @@
 // accuracy bar is the same as the f32 form's (tests/test_gpu_learner.py, both forms).
 //
 // Structure (per block: one net, 4 waves, wave w owns neurons 32w..32w+31 of both hidden layers,
-// rounds of 64 minibatch rows = two 32-row tiles; the loss math is learner.hip's):
+// rounds of 64 minibatch rows = two 32-row tiles; the loss math is learner.h's):
 //   L1   h1^T = W1 x^T        E form (neurons in registers, rows on lanes)  -> H1 pieces image
 //   L2   h2^T = W2 h1^T       E form: A = W2 rows (pre-split pieces from HBM, k_x3_prep), B = H1 row reads
 //   head / loss / dL/dmean    VALU, as learner.hip
@@ -45,7 +45,6 @@ namespace {
 
 using namespace x3;
 
-
 // LDS (bytes)
 constexpr int IMG = RND * RS;                  // one [64 row][128 neuron] bf16 piece
 constexpr int XROW = 32;                       // observation image row: 12 features, 1.0, 3 zeros (bf16)
@@ -62,9 +61,6 @@ constexpr int B_TOTAL = B_B2 + H * 4;          // 162,368 B
 static_assert(B_TOTAL <= 160 * 1024, "LDS budget");
 static_assert(B_XO % 16 == 0 && B_SC % 16 == 0 && B_W3T % 16 == 0, "alignment");
 static_assert(2 * LB * 8 <= 3 * IMG, "the advantage reduction aliases the DH2 image");
-
-
-
 
 // k_x3_prep: blocks 0..31 split W2 (four (net, w, u, s) units of 64 lanes per 256-thread block);
 // with adv != NULL blocks 32.. are the advantage-statistics blocks (adv_stats_block) -- one launch
@@ -95,8 +91,6 @@ __global__ __launch_bounds__(256) void k_x3_prep(const float* __restrict__ wa, c
   }
   adv_stats_block(adv, idx, batch, part, blockIdx.x - SPLIT_BLOCKS, red);
 }
-
-
 
 // The schedule below is the one measured best (round 5, profiles/r05/learner_*_ab.txt; the not-kept
 // alternatives were A/B builds and are gone from the product source): L1 issues both tiles' MFMAs
@@ -138,30 +132,11 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
   const int tr_col = 2 * ghi + (gp >> 1), tr_half = 8 * (gp & 1);
 
   // ---- advantage statistics of the minibatch (actor): fixed-order tree over the pre-pass partials
-  float adv_mu = 0.f, adv_den = 1.f;
-  if (NOUT == ACT && g.adv_part) {
-    double* red = reinterpret_cast<double*>(L + B_DH2P);  // [2][LB], before the DH2 image is used
-    red[tid] = g.adv_part[2 * tid];
-    red[LB + tid] = g.adv_part[2 * tid + 1];
-    __syncthreads();
-    for (int o = LB / 2; o > 0; o >>= 1) {
-      if (tid < o) { red[tid] += red[tid + o]; red[LB + tid] += red[LB + tid + o]; }
-      __syncthreads();
-    }
-    const double n = double(g.batch), s = red[0], s2 = red[LB];
-    const double var = fmax((s2 - s * s / n) / (n - 1.0), 0.0);
-    adv_mu = float(s / n);
-    adv_den = float(sqrt(var)) + 1e-8f;
-  }
-  const float adv_rden = 1.f / adv_den;
+  double* const red = reinterpret_cast<double*>(L + B_DH2P);  // [2][LB], before the DH2 image is used
+  const AdvNorm an = adv_norm<NOUT>(g, red, red + LB);
 
   // ---- small weights in LDS; the wave's W1 fragment split in registers
-  for (int i = tid; i < H; i += LB) {
-    Lf[B_B1 / 4 + i] = W.b0[i];
-    Lf[B_B2 / 4 + i] = W.b1[i];
-#pragma unroll
-    for (int k = 0; k < 4; k++) Lf[B_W3T / 4 + 4 * i + k] = k < NOUT ? W.w2[k * H + i] : 0.f;
-  }
+  stage_small_weights<NOUT>(W, Lf, B_B1 / 4, B_B2 / 4, B_W3T / 4);
   if (tid < 16) Lf[B_ZERO / 4 + tid] = 0.f;
   float b3[NOUT];
 #pragma unroll
@@ -176,10 +151,10 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
   // this wave's pre-split W2 fragments (k_x3_prep); the base is made opaque each round so the
   // compiler cannot hoist the 48 loads out of the round loop (their 192 VGPRs would spill)
   const int wunit0 = wimg_unit(NOUT == ACT ? 0 : 1, w, 0, 0, 0, lane);
-  float ls[ACT], sd[ACT], isd[ACT];  // isd: the row loop multiplies (a full-precision division is ~10 VALU)
+  float ls[ACT], isd[ACT];  // isd: the row loop multiplies (a full-precision division is ~10 VALU)
   if constexpr (NOUT == ACT) {
 #pragma unroll
-    for (int k = 0; k < ACT; k++) { ls[k] = g.log_std[k]; sd[k] = expf(ls[k]); isd[k] = 1.f / sd[k]; }
+    for (int k = 0; k < ACT; k++) { ls[k] = g.log_std[k]; isd[k] = 1.f / expf(ls[k]); }
   }
 
   // accumulators (whole launch)
@@ -204,33 +179,7 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
 #pragma unroll
   for (int k = 0; k < ACT; k++) dls[k] = 0.f;
 
-  const int per_block = NOUT == ACT ? g.per_block : g.per_block_c;
-  const int s0 = blk * per_block;
-  const int s1 = min(g.batch, s0 + per_block);
-  const int rounds = s1 > s0 ? (s1 - s0 + RND - 1) / RND : 0;
-  // Row staging, one round ahead: threads 0..191 gather the observation rows (float4 each),
-  // threads 192..255 the row scalars; the minibatch indices are loaded two rounds ahead.
-  const int srow = tid < 3 * RND ? tid / 3 : tid - 3 * RND;
-  auto index_of = [&](int rd) -> int64_t {
-    const int i = s0 + rd * RND + srow;
-    return (rd < rounds && i < s1) ? g.idx[i] : int64_t(-1);
-  };
-  float4 pf = make_float4(0.f, 0.f, 0.f, 0.f);
-  float pfs[3] = {0.f, 0.f, 0.f};
-  auto gather = [&](int64_t row) {
-    pf = make_float4(0.f, 0.f, 0.f, 0.f);
-    pfs[0] = pfs[1] = pfs[2] = 0.f;
-    if (row < 0) return;
-    if (tid < 3 * RND) {
-      pf = reinterpret_cast<const float4*>(g.obs)[size_t(row) * 3 + tid % 3];
-    } else if (NOUT == ACT) {
-      pf = reinterpret_cast<const float4*>(g.act)[row];
-      pfs[0] = g.logp_old[row];
-      pfs[1] = g.adv[row];
-    } else {
-      pfs[2] = g.ret[row];
-    }
-  };
+  RowStage<NOUT> stage(g, blk);  // the block's slice of the minibatch, staged one round ahead
   // features 12..15 of every observation image row: 1.0 (dW1's column 12 is db1), 0, 0, 0 -- both
   // buffers, once (the per-round staging writes features 0..11 only)
   if (tid < 2 * RND) {
@@ -240,15 +189,15 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
     *reinterpret_cast<bf16x4*>(XO + XIMG) = zero;
     *reinterpret_cast<bf16x4*>(XO + 2 * XIMG) = zero;
   }
-  gather(index_of(0));
-  int64_t next_row = index_of(1);
+  stage.gather(stage.index_of(0));
+  int64_t next_row = stage.index_of(1);
   __syncthreads();
 
 #if defined(QD_LPROBE)
   uint64_t stp[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
-  for (int rd = 0; rd < rounds; rd++) {
-    const int base = s0 + rd * RND;
+  for (int rd = 0; rd < stage.rounds; rd++) {
+    const int base = stage.s0 + rd * RND;
     uint64_t wbase = reinterpret_cast<uint64_t>(g.wimg);
     asm volatile("" : "+s"(wbase));
     typedef __attribute__((address_space(1))) const bf16x8 gbf16x8;  // global, not flat: no lgkmcnt
@@ -270,18 +219,17 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
     // constant columns 12..15 are written once before the loop, so no lane branches here (the
     // kernel's 8 spilled VGPRs went to 0)
     if (__builtin_amdgcn_readfirstlane(tid) < 3 * RND) {
-      const float v[4] = {pf.x, pf.y, pf.z, pf.w};
+      const float v[4] = {stage.pf.x, stage.pf.y, stage.pf.z, stage.pf.w};
       const X3h x = split4(v);
       const int c = tid % 3;
 #pragma unroll
-      for (int p = 0; p < 3; p++) *reinterpret_cast<bf16x4*>(XO + p * XIMG + srow * XROW + 8 * c) = x.p[p];
+      for (int p = 0; p < 3; p++) *reinterpret_cast<bf16x4*>(XO + p * XIMG + stage.srow * XROW + 8 * c) = x.p[p];
     } else {
-      *reinterpret_cast<float4*>(SCI + srow * 8) = pf;
-      SCI[srow * 8 + 4] = pfs[0]; SCI[srow * 8 + 5] = pfs[1]; SCI[srow * 8 + 6] = pfs[2];
+      stage.store_scalars(SCI);
     }
     bool valid[2];
 #pragma unroll
-    for (int t = 0; t < 2; t++) valid[t] = base + 32 * t + l32 < s1;
+    for (int t = 0; t < 2; t++) valid[t] = base + 32 * t + l32 < stage.s1;
     X3_BAR();  // B1: observation image complete; the previous round's readers are done
     LP(1);
 
@@ -370,8 +318,8 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
     // Row staging for round rd + 1, issued after L2's weight-piece loads: vmcnt retires in issue
     // order, so a gather issued before them would expose its HBM latency at L2's first wait; from
     // here it has the rest of the round (the dh1 pieces are waited ~10k cycles later)
-    gather(next_row);
-    next_row = index_of(rd + 2);
+    stage.gather(next_row);
+    next_row = stage.index_of(rd + 2);
     LP(4);
     if constexpr (DUMP) {
       LP_DUMP(for (int t = 0; t < 2; t++)
@@ -416,46 +364,23 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
       const int e = lane;
       const bool vrow = h ? valid[1] : valid[0];
       const bool acc = w == 0 && vrow;
-      float dd[NOUT];
-      const float* PT = Lf + B_PART / 4;
       float out[NOUT];
-#pragma unroll
-      for (int k = 0; k < NOUT; k++)
-        out[k] = (((PT[e * 4 + k] + PT[(RND + e) * 4 + k]) + PT[(2 * RND + e) * 4 + k]) + PT[(3 * RND + e) * 4 + k]) +
-                 b3[k];
-      const float4 a4 = *reinterpret_cast<const float4*>(SCI + e * 8);
-      const float a4k[4] = {a4.x, a4.y, a4.z, a4.w};
+      head_out<NOUT>(Lf + B_PART / 4, 0, e, b3, out);
+      const RowTerms<NOUT> rt = row_terms<NOUT>(g, out, SCI + e * 8, ls, isd, an, vrow);
+      // the row sums as selects, not branches (the same operations on the accumulating lanes)
       if constexpr (NOUT == ACT) {
-        float z[ACT], lp = 0.f;
+        st[0] = acc ? st[0] + rt.pg : st[0];
+        st[2] = acc ? st[2] + rt.clipped : st[2];
 #pragma unroll
-        for (int k = 0; k < ACT; k++) {
-          z[k] = (a4k[k] - out[k]) * isd[k];
-          lp += -0.5f * z[k] * z[k] - ls[k] - 0.91893853320467274f;
-        }
-        // ratio = exp(logp - old) on the hardware exp2 (~1 ulp; the correctly rounded expf is ~10 VALU)
-        const float r = __builtin_amdgcn_exp2f((lp - SCI[e * 8 + 4]) * 1.44269504088896341f);
-        const float A = g.adv_part ? (SCI[e * 8 + 5] - adv_mu) * adv_rden : SCI[e * 8 + 5];
-        const float cr = fminf(fmaxf(r, 1.f - g.clip), 1.f + g.clip);
-        const float sa = A * r, sb = A * cr;
-        const float w1 = sa < sb ? 1.f : (sa == sb ? 0.5f : 0.f);
-        const float inr = (r >= 1.f - g.clip && r <= 1.f + g.clip) ? 1.f : 0.f;
-        const float dlp = vrow ? -g.inv_batch * A * (w1 + (1.f - w1) * inr) * r : 0.f;
-#pragma unroll
-        for (int k = 0; k < ACT; k++) dd[k] = dlp * z[k] * isd[k];
-        // the row sums as selects, not branches (the same operations on the accumulating lanes)
-        st[0] = acc ? st[0] + -fminf(sa, sb) : st[0];
-        st[2] = acc ? st[2] + (fabsf(r - 1.f) > g.clip ? 1.f : 0.f) : st[2];
-#pragma unroll
-        for (int k = 0; k < ACT; k++) dls[k] = acc ? dls[k] + dlp * (z[k] * z[k] - 1.f) : dls[k];
+        for (int k = 0; k < ACT; k++) dls[k] = acc ? dls[k] + rt.dlp * (rt.z[k] * rt.z[k] - 1.f) : dls[k];
       } else {
-        const float diff = out[0] - SCI[e * 8 + 6];
-        dd[0] = vrow ? 2.f * g.vf_coef * g.inv_batch * diff : 0.f;
-        st[1] = acc ? st[1] + diff * diff : st[1];
+        st[1] = acc ? st[1] + rt.diff * rt.diff : st[1];
       }
 #pragma unroll
       for (int k = 0; k < NOUT; k++) {
-        db3[k] = w == 0 ? db3[k] + dd[k] : db3[k];
-        const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(dd[k]), __float_as_uint(dd[k]), false, false);
+        const uint32_t dk = __float_as_uint(rt.dd[k]);
+        db3[k] = w == 0 ? db3[k] + rt.dd[k] : db3[k];
+        const auto p = __builtin_amdgcn_permlane32_swap(dk, dk, false, false);
         d[0][k] = __uint_as_float(p[0]);  // lanes 0-31's value (tile 0's row) in every lane
         d[1][k] = __uint_as_float(p[1]);  // lanes 32-63's (tile 1's)
       }
@@ -661,7 +586,8 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
     for (int o = 16; o > 0; o >>= 1) x += __shfl_xor(x, o);
     if (l32 == 0) P[P_B2 + 32 * w + acc_row(r, h)] = x;
   }
-  if (w == 0) {  // the per-row sums (one row per lane: every lane of wave 0 holds some)
+  // the per-row sums (one row per lane: every lane of wave 0 holds some)
+  if (w == 0) {
     float v[NOUT + ACT + 3];
     int nv = 0;
 #pragma unroll
@@ -677,17 +603,7 @@ __device__ __forceinline__ void body(const GArgs& g, char* __restrict__ L, int b
       for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
       v[q] = x;
     }
-    if (lane == 0) {
-      const int b3off = NOUT == ACT ? P_B3A : P_B3C;
-#pragma unroll
-      for (int k = 0; k < NOUT; k++) P[b3off + k] = v[k];
-      if (NOUT == ACT) {
-#pragma unroll
-        for (int k = 0; k < ACT; k++) P[P_LS + k] = v[NOUT + k];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; k++) P[P_STATS + k] = v[NOUT + ACT + k];
-    }
+    if (lane == 0) store_row_sums<NOUT>(P, v);
   }
 }
 
@@ -739,17 +655,11 @@ int launch_prep(const GArgs& g, hipStream_t s, double* adv_stats, const float* a
 }
 
 int launch_ppo_grad_x3(const GArgs& g, hipStream_t s, double* adv_stats, const float* adv) {
-  static bool opted[64] = {};
+  static bool opted[64] = {}, opted_net[64] = {};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(QUAD_EHIP, "hipGetDevice failed");
-  if (!opted[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_x3), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            B_TOTAL) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_x3_sep),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, B_TOTAL) != hipSuccess)
-      return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    opted[dev] = true;
-  }
+  if (!opt_in_dynamic_lds(opted[dev], &k_ppo_grad_x3, &k_ppo_grad_x3_sep, B_TOTAL))
+    return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   if (int rc = launch_prep(g, s, adv_stats, adv)) return rc;
   const char* sp = std::getenv("QUADENV_LEARNER_SPLIT");
   if (sp && std::atoi(sp) != 0) {
@@ -757,10 +667,7 @@ int launch_ppo_grad_x3(const GArgs& g, hipStream_t s, double* adv_stats, const f
     static hipEvent_t ev[64][2] = {};
     static bool ready[64] = {};
     if (!ready[dev]) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_x3_net<ACT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, B_TOTAL) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_x3_net<1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, B_TOTAL) != hipSuccess ||
+      if (!opt_in_dynamic_lds(opted_net[dev], &k_ppo_grad_x3_net<ACT>, &k_ppo_grad_x3_net<1>, B_TOTAL) ||
           hipStreamCreateWithFlags(&s2[dev], hipStreamNonBlocking) != hipSuccess ||
           hipEventCreateWithFlags(&ev[dev][0], hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&ev[dev][1], hipEventDisableTiming) != hipSuccess)
