@@ -3,7 +3,9 @@
 library build -- so a refactor or a schedule change can be shown to give identical bits. One
 process per library: 40 quad_step launches (each step form, pinned: k_step_h in 64/256-env blocks,
 the 64-env nt form, k_step_hd; hover, hover + CTBR, trajectory + CTBR) with random actions and auto-resets, every
-obs / reward / flag / terminal obs and the final state; and a 32-step quad_rollout (one launch).
+obs / reward / flag / terminal obs and the final state; a 40-step quad_step_random launch in 64- and
+256-env blocks (hover, hover + CTBR); 40 steps, the reset rows and quad_observe of the one-kernel kinds
+(RelPos, CTBR + RelPos, trajectory + RelPos, the two brax kinds); and a 32-step quad_rollout (one launch).
 Usage: env_digest.py lib1.so [lib2.so ...]"""
 import hashlib
 import os
@@ -43,6 +45,41 @@ def child(lib):
             out[f"step {fname} {kind} {wrapper}"] = h.hexdigest()[:16]
     for k in ("QUADENV_HBLOCK", "QUADENV_NT", "QUADENV_HD"):
         os.environ.pop(k, None)
+    # the K-step launch (quad_step_random), 64- and 256-env blocks: every row of 40 steps + the final state
+    for hb in ("64", "256"):
+        os.environ["QUADENV_HBLOCK"] = hb
+        for kind, wrapper in (("hover", None), ("hover", "RateControlWrapper")):
+            h = hashlib.sha256()
+            e = QuadVecEnv(5000, env=kind, wrapper=wrapper, device="cuda:0", seed=3)
+            h.update(e.reset().cpu().numpy().tobytes())
+            r = e.step_random(40, actions=True)
+            for k in sorted(r):
+                h.update(r[k].cpu().numpy().tobytes())
+            for k, v in sorted(e.get_state().items()):
+                h.update(v.tobytes())
+            e.close()
+            out[f"kstep h{hb} {kind} {wrapper}"] = h.hexdigest()[:16]
+    os.environ.pop("QUADENV_HBLOCK", None)
+    # the one-kernel kinds: the RelPos wrappers (7-D step and reset rows, quad_observe) and the brax kinds
+    for kind, wrapper in (("hover", "RelPosActWrapper"), ("hover", "RelPosActWrapper(RateControlWrapper)"),
+                          ("trajectory", "RelPosActWrapper"), ("brax_hover", None), ("brax_jax_mjx", None)):
+        h = hashlib.sha256()
+        e = QuadVecEnv(5000, env=kind, wrapper=wrapper, device="cuda:0", seed=3)
+        h.update(e.reset().cpu().numpy().tobytes())
+        for t in range(40):
+            a = e.random_actions(t)
+            obs, rew, te, tr, inf = e.step(a, info="basic" if e.brax else "full")
+            for x in (obs, rew, te, tr, inf["terminal_observation"]):
+                h.update(x.cpu().numpy().tobytes())
+            if not e.brax:
+                h.update(inf["state"].cpu().numpy().tobytes())
+                h.update(inf["motor_commands"].cpu().numpy().tobytes())
+        if wrapper:
+            h.update(e.observe().cpu().numpy().tobytes())
+        for k, v in sorted(e.get_state().items()):
+            h.update(v.tobytes())
+        e.close()
+        out[f"step one-kernel {kind} {wrapper}"] = h.hexdigest()[:16]
     from uav_reinforcement_learning_control_amd.ppo.fused import FusedPolicy
     from uav_reinforcement_learning_control_amd.ppo.policy import ActorCritic
     torch.manual_seed(0)

@@ -1,19 +1,25 @@
 // quadenv.hip -- gfx950 kernels + the extern "C" ABI declared in include/quadenv.h.
 //
-// Data layout in HBM (one allocation per handle, field-major SoA, stride N):
-//   soa[f * N + i], f = 0..10 qpos, 11..20 qvel, 21 voltage, 22..24 target, 25..27 CTBR integral
-//   step[N] int32, episode[N] uint32
+// Data layout in HBM (one allocation per handle): tiles of 64 envs, each NFT fields x 64 lanes of 4 B -- qpos,
+// qvel, voltage, target, CTBR integral, previous action, step count, episode counter (table: env_tiles.h).
 // One thread owns one env for a whole step; every per-field access of a wave is a coalesced
 // 256-B line. The [N,12] row-major observation rows (48 B per env, what the policy GEMM wants)
-// are transposed through LDS so that each wave-store instruction writes 1 KiB contiguously.
+// are transposed through LDS so that each wave-store instruction writes 1 KiB contiguously
+// (256-env blocks), or stored by their lanes as three 16-byte stores (64-env blocks).
 //
 // Kernels
 //   k_step_h<KIND, CTBR> fused: (CTBR) -> mixer -> voltage -> mj_step -> obs -> reward ->
 //   (k_step_hd)          termination/truncation -> SB3 auto-reset -> obs, with helper waves
 //                        (control path, next-reset rows); k_step_hd: its >= 4M-env DRAM form
 //   k_step_random_h      config 2: K random-action steps per launch
+//   k_step_relpos        the step under RelPosActWrapper (7-D obs rows), one thread per env
 //   k_reset<KIND>        HoverEnv.reset for all / masked envs
 //   k_observe            HoverEnv._get_obs of the current state
+//   k_step_brax, k_reset_brax, k_observe_brax   the two brax kinds (21-D obs rows)
+//   k_terminated         HoverEnv._is_terminated of caller-given states
+//   k_waypoints_begin, k_waypoints_update       batched waypoint evaluation
+//   k_state_io, k_fill_field                    get / set_state, quad_seed
+//   k_mem_floor          the step's loads and stores alone (bench.py's DRAM floor)
 //   k_random_actions     action_space.sample() stand-in (Philox), config 2
 //   k_gae                SB3 GAE(lambda) reverse scan, one thread per env
 #include <hip/hip_runtime.h>
@@ -27,6 +33,7 @@
 #include "../../include/quadenv.h"
 #include "quad_model.h"
 #include "quad_physics.h"
+#include "dispatch.h"
 #include "env_tiles.h"
 #include "kconsts_default.h"
 #include "rollout.h"
@@ -94,6 +101,12 @@ __device__ __forceinline__ void store_row12(float* __restrict__ base, uint32_t i
   }
 }
 
+// the [N,7] RelPosActWrapper row of env i: obs[0:3], then the previous action
+__device__ __forceinline__ void store_obs7(float* __restrict__ out, int i, const float obs[3], const float prev[4]) {
+#pragma unroll
+  for (int j = 0; j < 7; j++) out[size_t(i) * 7 + j] = j < 3 ? obs[j] : prev[j - 3];
+}
+
 // info["target", "target_vel", "target_acc"] of the step just taken (before any auto-reset);
 // `ep` is the episode counter as loaded (the running episode is ep - 1)
 template <int KIND>
@@ -149,8 +162,76 @@ constexpr bool obs_direct() { return HB == 64 && !NT; }
 template <bool CTBR>
 constexpr bool ct_rows() { return !CTBR; }
 constexpr int CT_STRIDE = 8;  // words per env row of CT (6 used)
-constexpr int HROW = 28;  // floats per env in the helper image: pos 3, quat 4, v 3, w 3, target 3, obs 12
 constexpr int HCTL = 9;   // floats per env from the control helper: Fsum, taum 3, volt, bad ctrl, rint 3
+template <bool CTBR>
+constexpr int ct_words() { return ct_rows<CTBR>() ? CT_STRIDE : (CTBR ? HCTL : HCTL - 3); }
+
+// The helper image: every env's NEXT reset (the state a reset draws + the reset observation), kept in
+// LDS by the helper waves of k_step_h / k_step_hd / k_step_random_h; a resetting step lane copies its
+// row. ROWS = env-major rows of HROW words (seven 16-byte accesses), else field-major [f][HB].
+constexpr int HROW = 28;  // floats per env in the helper image: pos 3, quat 4, v 3, w 3, target 3, obs 12
+constexpr int H_POS = 0, H_Q = 3, H_V = 7, H_W = 10, H_TGT = 13, H_OBS = 16;
+// the uniforms of Philox block b of the reset draw of (seed, gid, ep): u16[4b .. 4b + 3]
+__device__ __forceinline__ void image_block(uint64_t seed, uint64_t gid, uint32_t ep, uint32_t b, float* u4) {
+  uint32_t cw[4];
+  reset_block(seed, gid, ep, b, cw);
+  u4[0] = u01(cw[0]); u4[1] = u01(cw[1]); u4[2] = u01(cw[2]); u4[3] = u01(cw[3]);
+}
+// HoverEnv.reset / TrajectoryFollowEnv.reset from the 16 uniforms of the draw
+template <int KIND>
+__device__ __forceinline__ void reset_from_u16(const KConsts<float>& K, const float u16[16], EnvRegs<float>& e,
+                                               float obs[12]) {
+  float init12[12], tgt[3], s12[12];
+  reset_affine_u(K.init_lo, K.init_span, K.tgt_lo, K.tgt_span, u16, init12, tgt);
+  env_reset_from<float, KIND>(K, e, init12, tgt, obs, s12);
+}
+template <bool ROWS, int HB>
+__device__ __forceinline__ void image_put(float* H, int l, const EnvRegs<float>& e, const float obs[12]) {
+  float row[HROW];
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    row[H_POS + j] = e.pos[j]; row[H_V + j] = e.v[j]; row[H_W + j] = e.w[j]; row[H_TGT + j] = e.target[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) row[H_Q + j] = e.q[j];
+#pragma unroll
+  for (int j = 0; j < 12; j++) row[H_OBS + j] = obs[j];
+  if constexpr (ROWS) {
+#pragma unroll
+    for (int q = 0; q < HROW / 4; q++)
+      reinterpret_cast<float4*>(H)[l * (HROW / 4) + q] = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int f = 0; f < HROW; f++) H[f * HB + l] = row[f];
+  }
+}
+// a resetting step lane's state from its row, and what a reset sets without a draw
+__device__ __forceinline__ void image_unpack(const KConsts<float>& K, const float (&row)[HROW], EnvRegs<float>& e,
+                                             float obs[12]) {
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    e.pos[j] = row[H_POS + j]; e.v[j] = row[H_V + j]; e.w[j] = row[H_W + j]; e.target[j] = row[H_TGT + j];
+    e.rint[j] = 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; j++) { e.q[j] = row[H_Q + j]; e.th[j] = 0.f; e.s[j] = 0.f; }
+#pragma unroll
+  for (int j = 0; j < 12; j++) obs[j] = row[H_OBS + j];
+  e.volt = float(K.vnom);
+  e.step = 0;
+}
+
+// The field-major row of env l, taken and unpacked (k_step_random_h). step_h_body reads its row in its own
+// body: inside a helper the reads moved its kernels' registers and spills (profiles/r07/quadenv_dispatch_refactor.txt).
+template <int HB>
+__device__ __forceinline__ void image_take(const KConsts<float>& K, const float* H, int l, EnvRegs<float>& e,
+                                           float obs[12]) {
+  float row[HROW];
+#pragma unroll
+  for (int f = 0; f < HROW; f++) row[f] = H[f * HB + l];
+  image_unpack(K, row, e, obs);
+}
+
 template <int KIND, bool CTBR, int HB, bool NT>
 __device__ __forceinline__ void step_h_body(const KConsts<float>& K, KParams p, const float4* __restrict__ act,
                                             QuadStepOut out, float4* lds, float* H, float* CT) {
@@ -218,34 +299,23 @@ __device__ __forceinline__ void step_h_body(const KConsts<float>& K, KParams p, 
     }
     // (R) env i's next reset, into H[f][l]: the first PRE Philox blocks before barrier (C), at
     // normal priority, in the slack the helper has while the step wave accumulates forward_base
-    constexpr int PRE = H_PRE;
+    constexpr uint32_t PRE = H_PRE;
     float u16[16];
     if (PRE > 0) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-    for (uint32_t b = 0; b < uint32_t(PRE); b++) {
-      uint32_t cw[4];
-      reset_block(p.seed, p.gid_base + uint64_t(i), ep, b, cw);
-#pragma unroll
-      for (int j = 0; j < 4; j++) u16[4 * b + j] = u01(cw[j]);
-    }
+    for (uint32_t b = 0; b < PRE; b++) image_block(p.seed, p.gid_base + uint64_t(i), ep, b, u16 + 4 * b);
     __syncthreads();  // (C) the control results are staged
     QD_STAMP(stamps, 3);
     __builtin_amdgcn_s_setprio(0);
 #pragma unroll
-    for (uint32_t b = uint32_t(PRE); b < 4; b++) {
-      uint32_t cw[4];
-      reset_block(p.seed, p.gid_base + uint64_t(i), ep, b, cw);
-#pragma unroll
-      for (int j = 0; j < 4; j++) u16[4 * b + j] = u01(cw[j]);
-    }
+    for (uint32_t b = PRE; b < 4; b++) image_block(p.seed, p.gid_base + uint64_t(i), ep, b, u16 + 4 * b);
 #if defined(QD_ABL_HDRAW0)  // cost ablation (tools only): the helper's reset row without its Philox words
 #pragma unroll
     for (int j = 0; j < 16; j++) u16[j] = u01(uint32_t(i) * 0x9E3779B9u + ep * 0x85EBCA6Bu + uint32_t(j) * 0xC2B2AE35u);
 #endif
-    float init12[12], tgt[3], obs[12], s12[12];
-    reset_affine_u(K.init_lo, K.init_span, K.tgt_lo, K.tgt_span, u16, init12, tgt);
+    float obs[12];
     EnvRegs<float> e;
-    env_reset_from<float, KIND>(K, e, init12, tgt, obs, s12);
+    reset_from_u16<KIND>(K, u16, e, obs);
 #if defined(QD_ABL_HROW0)  // cost ablation (tools only): no reset row at all (zeros)
 #pragma unroll
     for (int j = 0; j < 3; j++) { e.pos[j] = e.v[j] = e.w[j] = e.target[j] = 0.f; }
@@ -254,19 +324,7 @@ __device__ __forceinline__ void step_h_body(const KConsts<float>& K, KParams p, 
 #pragma unroll
     for (int j = 0; j < 12; j++) obs[j] = 0.f;
 #endif
-    const float row[HROW] = {e.pos[0], e.pos[1], e.pos[2], e.q[0], e.q[1], e.q[2], e.q[3],
-                             e.v[0], e.v[1], e.v[2], e.w[0], e.w[1], e.w[2],
-                             e.target[0], e.target[1], e.target[2],
-                             obs[0], obs[1], obs[2], obs[3], obs[4], obs[5], obs[6], obs[7], obs[8], obs[9],
-                             obs[10], obs[11]};
-    if constexpr (ct_rows<CTBR>()) {  // env-major rows (112 B, 16-byte aligned): seven 16-byte writes
-#pragma unroll
-      for (int q = 0; q < HROW / 4; q++)
-        reinterpret_cast<float4*>(H)[l * (HROW / 4) + q] = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
-    } else {
-#pragma unroll
-      for (int f = 0; f < HROW; f++) H[f * HB + l] = row[f];
-    }
+    image_put<ct_rows<CTBR>(), HB>(H, l, e, obs);  // rows: 112 B, seven 16-byte writes
     QD_STAMP(stamps, 4);
     __syncthreads();  // (1) the image is complete
     QD_STAMP(stamps, 5);
@@ -363,17 +421,7 @@ __device__ __forceinline__ void step_h_body(const KConsts<float>& K, KParams p, 
 #pragma unroll
         for (int f = 0; f < HROW; f++) row[f] = H[f * HB + l];
       }
-#pragma unroll
-      for (int j = 0; j < 3; j++) {
-        e.pos[j] = row[j]; e.v[j] = row[7 + j]; e.w[j] = row[10 + j]; e.target[j] = row[13 + j];
-        e.rint[j] = 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 4; j++) { e.q[j] = row[3 + j]; e.th[j] = 0.f; e.s[j] = 0.f; }
-#pragma unroll
-      for (int j = 0; j < 12; j++) obs[j] = row[16 + j];
-      e.volt = float(K.vnom);
-      e.step = 0;
+      image_unpack(K, row, e, obs);
       S.stu(F_EP, fresh_off(vo), ep + 1u);
       if constexpr (obs_direct<HB, NT>()) store_row12(out.obs, uint32_t(i), obs);
     }
@@ -421,7 +469,7 @@ __global__ __launch_bounds__(2 * HB) void k_step_h(float* tiles, const float4* _
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
   __shared__ float4 lds[HB * 3];
   __shared__ __attribute__((aligned(16))) float H[HROW * HB];
-  __shared__ __attribute__((aligned(16))) float CT[(ct_rows<CTBR>() ? CT_STRIDE : (CTBR ? HCTL : HCTL - 3)) * HB];
+  __shared__ __attribute__((aligned(16))) float CT[ct_words<CTBR>() * HB];
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
     step_h_body<KIND, CTBR, HB, NT>(K, p, act, out, lds, H, CT);
@@ -446,7 +494,7 @@ void k_step_hd(float* tiles, const float4* __restrict__ act, uint32_t tile_bytes
   p.kc = kc;
   __shared__ float4 lds[64 * 3];
   __shared__ __attribute__((aligned(16))) float H[HROW * 64];
-  __shared__ __attribute__((aligned(16))) float CT[(ct_rows<CTBR>() ? CT_STRIDE : (CTBR ? HCTL : HCTL - 3)) * 64];
+  __shared__ __attribute__((aligned(16))) float CT[ct_words<CTBR>() * 64];
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
     step_h_body<KIND, CTBR, 64, true>(K, p, act, out, lds, H, CT);
@@ -499,48 +547,16 @@ __global__ __launch_bounds__(256) void k_mem_floor(KParams p, const float4* __re
 // Per step: barrier A (flags known; the image is current) -> resets copied, obs rows staged ->
 // barrier B -> obs rows stored by all 512 threads, helpers redraw. Same env_step code as k_step_h, so
 // the same bits as K single steps.
-template <int KIND, bool CTBR, int RB>
+// The image is field-major here for every kind (the row form was measured on k_step_h only).
+template <int KIND, int RB>
 __device__ __forceinline__ void helper_reset_row(const KConsts<float>& K, const KParams& p, int i, uint32_t ep,
                                                  float* H, int l) {
-  float u16[16];
+  float u16[16], obs[12];
 #pragma unroll
-  for (uint32_t b = 0; b < 4; b++) {
-    uint32_t c[4];
-    reset_block(p.seed, p.gid_base + uint64_t(i), ep, b, c);
-#pragma unroll
-    for (int j = 0; j < 4; j++) u16[4 * b + j] = u01(c[j]);
-  }
-  float init12[12], tgt[3], obs[12], s12[12];
-  reset_affine_u(K.init_lo, K.init_span, K.tgt_lo, K.tgt_span, u16, init12, tgt);
+  for (uint32_t b = 0; b < 4; b++) image_block(p.seed, p.gid_base + uint64_t(i), ep, b, u16 + 4 * b);
   EnvRegs<float> e;
-  env_reset_from<float, KIND>(K, e, init12, tgt, obs, s12);
-  const float row[HROW] = {e.pos[0], e.pos[1], e.pos[2], e.q[0], e.q[1], e.q[2], e.q[3],
-                           e.v[0], e.v[1], e.v[2], e.w[0], e.w[1], e.w[2],
-                           e.target[0], e.target[1], e.target[2],
-                           obs[0], obs[1], obs[2], obs[3], obs[4], obs[5], obs[6], obs[7], obs[8], obs[9],
-                           obs[10], obs[11]};
-#pragma unroll
-  for (int f = 0; f < HROW; f++) H[f * RB + l] = row[f];
-}
-
-// a resetting step lane takes its row of the helper image (k_step_h, k_step_random_h)
-template <int KIND, int RB>
-__device__ __forceinline__ void take_reset_row(const KConsts<float>& K, const float* H, int l, EnvRegs<float>& e,
-                                               float obs[12]) {
-  float row[HROW];
-#pragma unroll
-  for (int f = 0; f < HROW; f++) row[f] = H[f * RB + l];
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    e.pos[j] = row[j]; e.v[j] = row[7 + j]; e.w[j] = row[10 + j]; e.target[j] = row[13 + j];
-    e.rint[j] = 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; j++) { e.q[j] = row[3 + j]; e.th[j] = 0.f; e.s[j] = 0.f; }
-#pragma unroll
-  for (int j = 0; j < 12; j++) obs[j] = row[16 + j];
-  e.volt = float(K.vnom);
-  e.step = 0;
+  reset_from_u16<KIND>(K, u16, e, obs);
+  image_put<false, RB>(H, l, e, obs);
 }
 
 __device__ __forceinline__ float4 random_action4(uint64_t seed, uint64_t gid, uint32_t step) {
@@ -571,7 +587,7 @@ __device__ __forceinline__ void step_random_h_body(const KConsts<float>& K, KPar
     ep = S.ldu(F_EP, vo);
     A[l] = random_action4(p.seed, gid, step0);
     if (steps > 1) A[RB + l] = random_action4(p.seed, gid, step0 + 1u);
-    helper_reset_row<KIND, CTBR, RB>(K, p, i, ep, H, l);
+    helper_reset_row<KIND, RB>(K, p, i, ep, H, l);
   } else {
     load_env(p, i, e, CTBR);
   }
@@ -595,7 +611,7 @@ __device__ __forceinline__ void step_random_h_body(const KConsts<float>& K, KPar
       __syncthreads();  // (A) the image holds every env's next reset
       if (rs) {
         if (out.terminal_obs) store_row12(out.terminal_obs, row, r.obs);
-        take_reset_row<KIND, RB>(K, H, l, e, obs);
+        image_take<RB>(K, H, l, e, obs);
       }
       R[l] = rs ? 1u : 0u;
       lds[3 * l + 0] = make_float4(obs[0], obs[1], obs[2], obs[3]);
@@ -608,7 +624,7 @@ __device__ __forceinline__ void step_random_h_body(const KConsts<float>& K, KPar
       __syncthreads();  // (B)
       if (R[l]) {  // this env reset at step t: its next episode's row
         ep += 1u;
-        helper_reset_row<KIND, CTBR, RB>(K, p, i, ep, H, l);
+        helper_reset_row<KIND, RB>(K, p, i, ep, H, l);
       }
       if (t + 2 < steps) A[(t & 1) * RB + l] = random_action4(p.seed, gid, step0 + uint32_t(t + 2));
     }
@@ -679,10 +695,7 @@ __global__ __launch_bounds__(BLOCK) void k_step_relpos(const KConsts<float>* __r
   }
   if (out.target_info) store_target_info(out.target_info, i, info);
   if (rs) {
-    if (out.terminal_obs) {
-#pragma unroll
-      for (int j = 0; j < 7; j++) out.terminal_obs[size_t(i) * 7 + j] = o7[j];
-    }
+    if (out.terminal_obs) store_obs7(out.terminal_obs, i, o7, o7 + 3);
     S.stu(F_EP, vo, ep + 1u);
     o7[0] = obs12[0]; o7[1] = obs12[1]; o7[2] = obs12[2];
 #pragma unroll
@@ -691,8 +704,7 @@ __global__ __launch_bounds__(BLOCK) void k_step_relpos(const KConsts<float>* __r
   store_env(p, i, e, CTBR);
 #pragma unroll
   for (int j = 0; j < 4; j++) S.st(F_PREV + j, vo, prev[j]);
-#pragma unroll
-  for (int j = 0; j < 7; j++) out.obs[size_t(i) * 7 + j] = o7[j];
+  store_obs7(out.obs, i, o7, o7 + 3);
 }
 
 template <int KIND, bool RELPOS>
@@ -713,8 +725,8 @@ __global__ __launch_bounds__(BLOCK) void k_reset(KParams p, const uint8_t* __res
   for (int j = 0; j < 4; j++) S.st(F_PREV + j, vo, 0.f);  // hover_env.py:212
   if (obs_out) {
     if (RELPOS) {
-#pragma unroll
-      for (int j = 0; j < 7; j++) obs_out[size_t(i) * 7 + j] = j < 3 ? obs[j] : 0.f;
+      const float prev[4] = {0.f, 0.f, 0.f, 0.f};
+      store_obs7(obs_out, i, obs, prev);
     } else {
 #pragma unroll
       for (int j = 0; j < 12; j++) obs_out[size_t(i) * 12 + j] = obs[j];
@@ -804,9 +816,10 @@ __global__ __launch_bounds__(BLOCK) void k_observe(KParams p, float* __restrict_
   float obs[12], s12[12];
   observe(*p.kc, e, obs, s12);
   if (RELPOS) {
+    float prev[4];
 #pragma unroll
-    for (int j = 0; j < 7; j++)
-      obs_out[size_t(i) * 7 + j] = j < 3 ? obs[j] : Tiles(p).ld(F_PREV + j - 3, env_off(uint32_t(i)));
+    for (int j = 0; j < 4; j++) prev[j] = Tiles(p).ld(F_PREV + j, env_off(uint32_t(i)));
+    store_obs7(obs_out, i, obs, prev);
   } else {
 #pragma unroll
     for (int j = 0; j < 12; j++) obs_out[size_t(i) * 12 + j] = obs[j];
@@ -867,8 +880,10 @@ __global__ __launch_bounds__(BLOCK) void k_waypoints_begin(KParams p, QuadWaypoi
   float obs[12], s12[12];
   observe(*p.kc, e, obs, s12);
   if (RELPOS) {
+    float prev[4];
 #pragma unroll
-    for (int j = 0; j < 7; j++) obs_out[size_t(i) * 7 + j] = j < 3 ? obs[j] : S.ld(F_PREV + j - 3, vo);
+    for (int j = 0; j < 4; j++) prev[j] = S.ld(F_PREV + j, vo);
+    store_obs7(obs_out, i, obs, prev);
   } else {
 #pragma unroll
     for (int j = 0; j < 12; j++) obs_out[size_t(i) * 12 + j] = obs[j];
@@ -946,11 +961,7 @@ __global__ __launch_bounds__(BLOCK) void k_random_actions(int32_t n, uint64_t se
                                                           uint32_t step, float4* __restrict__ act) {
   const int i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
-  const uint64_t gid = gid_base + uint64_t(i);
-  uint32_t c[4] = {uint32_t(gid), uint32_t(gid >> 32), step, 0x100u};
-  philox4x32_10(c, uint32_t(seed), uint32_t(seed >> 32));
-  act[i] = make_float4(float(c[0] >> 8) * 0x1p-23f - 1.0f, float(c[1] >> 8) * 0x1p-23f - 1.0f,
-                       float(c[2] >> 8) * 0x1p-23f - 1.0f, float(c[3] >> 8) * 0x1p-23f - 1.0f);
+  act[i] = random_action4(seed, gid_base + uint64_t(i), step);
 }
 
 // SB3 RolloutBuffer.compute_returns_and_advantage, time-major [T, N]
@@ -1039,6 +1050,29 @@ bool hd_form(const QuadHandle* h, int64_t count) {
   return count >= (int64_t(1) << 22) && h->cfg.env_kind == QUAD_ENV_HOVER && h->cfg.wrapper == QUAD_WRAP_NONE;
 }
 
+// launch geometry of the helper-wave forms: blocks of hb envs, one step and one helper thread per env
+struct HGeom {
+  dim3 grid, block;
+  HGeom(int64_t count, bool wide) : grid(unsigned((count + (wide ? 255 : 63)) / (wide ? 256 : 64))), block(wide ? 512 : 128) {}
+};
+
+int check_kind_wrapper(int32_t env_kind, int32_t wrapper) {
+  if (env_kind < QUAD_ENV_HOVER || env_kind > QUAD_ENV_BRAX_TRAJ) return fail(QUAD_EINVAL, "unknown env_kind");
+  if (wrapper < QUAD_WRAP_NONE || wrapper > QUAD_WRAP_CTBR_RELPOS) return fail(QUAD_EINVAL, "unknown wrapper");
+  if (env_kind >= QUAD_ENV_BRAX_HOVER && wrapper != QUAD_WRAP_NONE)
+    return fail(QUAD_EINVAL, "the brax env kinds take no wrapper");
+  return QUAD_OK;
+}
+
+// what every step entry point asks of its QuadStepOut; `pair` names obs and `other` (the actions in or out)
+int check_step_out(const QuadStepOut* out, const void* other, const char* pair = "actions and obs") {
+  if (!out->obs || !out->reward || !out->terminated || !out->truncated)
+    return fail(QUAD_EINVAL, "obs, reward, terminated and truncated are required");
+  if ((reinterpret_cast<uintptr_t>(other) | reinterpret_cast<uintptr_t>(out->obs)) & 15u)
+    return fail(QUAD_EINVAL, std::string(pair) + " must be 16-byte aligned");
+  return QUAD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1049,11 +1083,7 @@ const char* quad_last_error(void) { return g_err.c_str(); }
 
 int quad_default_cfg(int32_t env_kind, int32_t wrapper, QuadCfg* c) {
   if (!c) return fail(QUAD_EINVAL, "cfg is NULL");
-  if (env_kind < QUAD_ENV_HOVER || env_kind > QUAD_ENV_BRAX_TRAJ)
-    return fail(QUAD_EINVAL, "unknown env_kind");
-  if (wrapper < QUAD_WRAP_NONE || wrapper > QUAD_WRAP_CTBR_RELPOS) return fail(QUAD_EINVAL, "unknown wrapper");
-  if (env_kind >= QUAD_ENV_BRAX_HOVER && wrapper != QUAD_WRAP_NONE)
-    return fail(QUAD_EINVAL, "the brax env kinds take no wrapper");
+  if (int rc = check_kind_wrapper(env_kind, wrapper)) return rc;
   default_cfg_fill(env_kind, wrapper, c);
   return QUAD_OK;
 }
@@ -1066,12 +1096,7 @@ int quad_create(const QuadCfg* cfg, int32_t device, uint64_t seed, uint64_t env_
   // the tiles are one buffer resource (32-bit byte range); row outputs use 32-bit byte offsets
   if ((int64_t(n_envs) + 63) / 64 * TILE_BYTES > int64_t(UINT32_MAX))
     return fail(QUAD_EINVAL, "n_envs too large (max 31,580,608)");
-  if (cfg->env_kind < QUAD_ENV_HOVER || cfg->env_kind > QUAD_ENV_BRAX_TRAJ)
-    return fail(QUAD_EINVAL, "unknown env_kind");
-  if (cfg->wrapper < QUAD_WRAP_NONE || cfg->wrapper > QUAD_WRAP_CTBR_RELPOS)
-    return fail(QUAD_EINVAL, "unknown wrapper");
-  if (cfg->env_kind >= QUAD_ENV_BRAX_HOVER && cfg->wrapper != QUAD_WRAP_NONE)
-    return fail(QUAD_EINVAL, "the brax env kinds take no wrapper");
+  if (int rc = check_kind_wrapper(cfg->env_kind, cfg->wrapper)) return rc;
   if (cfg->max_episode_steps <= 0) return fail(QUAD_EINVAL, "max_episode_steps must be > 0");
   if (!(cfg->max_motor_thrust >= 0.0 && cfg->max_motor_thrust <= 1e30))
     return fail(QUAD_EINVAL, "max_motor_thrust must be finite and >= 0");
@@ -1089,9 +1114,9 @@ int quad_create(const QuadCfg* cfg, int32_t device, uint64_t seed, uint64_t env_
   make_kconsts<float>(*cfg, h->pd, h->kh);
   h->spec = is_default_block(h->kh, cfg->env_kind, cfg->wrapper == QUAD_WRAP_CTBR);
   if (const char* v = std::getenv("QUADENV_SPEC")) h->spec = h->spec && std::atoi(v) != 0;
-  // QUADENV_HBLOCK=64|256 pins the helper form's block size (tests run the 256-env blocks at small N)
   if (const char* v = std::getenv("QUADENV_NT")) h->nt = std::atoi(v) != 0 ? 1 : 0;
   if (const char* v = std::getenv("QUADENV_HD")) h->hd = std::atoi(v) != 0 ? 1 : 0;
+  // QUADENV_HBLOCK=64|256 pins the helper form's block size (tests run the 256-env blocks at small N)
   if (const char* v = std::getenv("QUADENV_HBLOCK")) {
     const int b = std::atoi(v);
     if (b == 64 || b == 256) h->hblock = b;
@@ -1163,18 +1188,16 @@ int quad_reset(QuadHandle* h, const uint8_t* mask, float* obs, void* stream) {
   if (!h) return fail(QUAD_EINVAL, "handle is NULL");
   DeviceGuard g(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->cfg.env_kind == QUAD_ENV_BRAX_HOVER)
-    hipLaunchKernelGGL(k_reset_brax<QUAD_ENV_BRAX_HOVER>, dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
-  else if (h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ)
-    hipLaunchKernelGGL(k_reset_brax<QUAD_ENV_BRAX_TRAJ>, dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
-  else if (wrap_relpos(h->cfg.wrapper) && h->cfg.env_kind == QUAD_ENV_TRAJ)
-    hipLaunchKernelGGL((k_reset<QUAD_ENV_TRAJ, true>), dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
-  else if (wrap_relpos(h->cfg.wrapper))
-    hipLaunchKernelGGL((k_reset<QUAD_ENV_HOVER, true>), dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
-  else if (h->cfg.env_kind == QUAD_ENV_TRAJ)
-    hipLaunchKernelGGL((k_reset<QUAD_ENV_TRAJ, false>), dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
+  const dim3 grid(grid_of(h->n)), blk(BLOCK);
+  if (h->cfg.env_kind >= QUAD_ENV_BRAX_HOVER)
+    with_bool(h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ, [&](auto tr) {
+      constexpr int kind = decltype(tr)::value ? QUAD_ENV_BRAX_TRAJ : QUAD_ENV_BRAX_HOVER;
+      hipLaunchKernelGGL(k_reset_brax<kind>, grid, blk, 0, s, h->kp, mask, obs);
+    });
   else
-    hipLaunchKernelGGL((k_reset<QUAD_ENV_HOVER, false>), dim3(grid_of(h->n)), dim3(BLOCK), 0, s, h->kp, mask, obs);
+    with_kind(h->cfg.env_kind == QUAD_ENV_TRAJ, wrap_relpos(h->cfg.wrapper), [&](auto kind, auto relpos) {
+      hipLaunchKernelGGL((k_reset<decltype(kind)::value, decltype(relpos)::value>), grid, blk, 0, s, h->kp, mask, obs);
+    });
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }
@@ -1189,75 +1212,47 @@ int quad_step_range(QuadHandle* h, int32_t first, int32_t count, const float* ac
   if (first < 0 || count < 0 || int64_t(first) + count > h->n)
     return fail(QUAD_EINVAL, "env range out of bounds");
   if (count == 0) return QUAD_OK;
-  if (!out->obs || !out->reward || !out->terminated || !out->truncated)
-    return fail(QUAD_EINVAL, "obs, reward, terminated and truncated are required");
-  if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(out->obs)) & 15u)
-    return fail(QUAD_EINVAL, "actions and obs must be 16-byte aligned");
+  if (int rc = check_step_out(out, actions)) return rc;
   if (out->motor_commands && (reinterpret_cast<uintptr_t>(out->motor_commands) & 15u))
     return fail(QUAD_EINVAL, "motor_commands must be 16-byte aligned");
   DeviceGuard g(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const float4* a = reinterpret_cast<const float4*>(actions);
-  const bool traj = h->cfg.env_kind == QUAD_ENV_TRAJ, ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
-  const dim3 blk(BLOCK);
+  const bool traj = h->cfg.env_kind == QUAD_ENV_TRAJ, ctbr = wrap_ctbr(h->cfg.wrapper);
+  const dim3 grid(grid_of(count)), blk(BLOCK);  // the one-thread-per-env kernels
   KParams kp = h->kp;
   kp.first = first;
   kp.count = count;
   if (wrap_relpos(h->cfg.wrapper)) {
-    const dim3 grid(grid_of(count));
-    const bool rc = h->cfg.wrapper == QUAD_WRAP_CTBR_RELPOS;
-    if (traj && rc)
-      hipLaunchKernelGGL((k_step_relpos<QUAD_ENV_TRAJ, true>), grid, blk, 0, s, h->kdev, kp, a, *out);
-    else if (traj)
-      hipLaunchKernelGGL((k_step_relpos<QUAD_ENV_TRAJ, false>), grid, blk, 0, s, h->kdev, kp, a, *out);
-    else if (rc)
-      hipLaunchKernelGGL((k_step_relpos<QUAD_ENV_HOVER, true>), grid, blk, 0, s, h->kdev, kp, a, *out);
-    else
-      hipLaunchKernelGGL((k_step_relpos<QUAD_ENV_HOVER, false>), grid, blk, 0, s, h->kdev, kp, a, *out);
+    with_kind(traj, ctbr, [&](auto kind, auto cb) {
+      hipLaunchKernelGGL((k_step_relpos<decltype(kind)::value, decltype(cb)::value>), grid, blk, 0, s, h->kdev, kp, a, *out);
+    });
   } else if (h->cfg.env_kind >= QUAD_ENV_BRAX_HOVER) {
-    const dim3 grid(grid_of(count));
-    if (h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ)
-      hipLaunchKernelGGL((k_step_brax<QUAD_ENV_BRAX_TRAJ>), grid, blk, 0, s, h->kdev, kp, a, *out);
-    else
-      hipLaunchKernelGGL((k_step_brax<QUAD_ENV_BRAX_HOVER>), grid, blk, 0, s, h->kdev, kp, a, *out);
+    with_bool(h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ, [&](auto tr) {
+      constexpr int kind = decltype(tr)::value ? QUAD_ENV_BRAX_TRAJ : QUAD_ENV_BRAX_HOVER;
+      hipLaunchKernelGGL(k_step_brax<kind>, grid, blk, 0, s, h->kdev, kp, a, *out);
+    });
   } else {  // one thread per env, helper waves beside the step waves
-#define QD_KARGS kp.tiles, a, kp.tile_bytes, kp.first, kp.count, h->kdev, kp, *out
-#define QD_LAUNCH_H2(SP, HB, NT)                                                                       \
-  if (traj && ctbr)                                                                             \
-    hipLaunchKernelGGL((k_step_h<QUAD_ENV_TRAJ, true, SP, HB, NT>), grid, blk2, 0, s, QD_KARGS);      \
-  else if (traj)                                                                                \
-    hipLaunchKernelGGL((k_step_h<QUAD_ENV_TRAJ, false, SP, HB, NT>), grid, blk2, 0, s, QD_KARGS);     \
-  else if (ctbr)                                                                                \
-    hipLaunchKernelGGL((k_step_h<QUAD_ENV_HOVER, true, SP, HB, NT>), grid, blk2, 0, s, QD_KARGS);     \
-  else                                                                                          \
-    hipLaunchKernelGGL((k_step_h<QUAD_ENV_HOVER, false, SP, HB, NT>), grid, blk2, 0, s, QD_KARGS);
-#define QD_LAUNCH_H(SP, HB) \
-  if (nt) { QD_LAUNCH_H2(SP, HB, true) } else { QD_LAUNCH_H2(SP, HB, false) }
-#define QD_LAUNCH_HD(SP)                                                                        \
-  if (traj && ctbr)                                                                             \
-    hipLaunchKernelGGL((k_step_hd<QUAD_ENV_TRAJ, true, SP>), grid, blk2, 0, s, QD_KARGS);       \
-  else if (traj)                                                                                \
-    hipLaunchKernelGGL((k_step_hd<QUAD_ENV_TRAJ, false, SP>), grid, blk2, 0, s, QD_KARGS);      \
-  else if (ctbr)                                                                                \
-    hipLaunchKernelGGL((k_step_hd<QUAD_ENV_HOVER, true, SP>), grid, blk2, 0, s, QD_KARGS);      \
-  else                                                                                          \
-    hipLaunchKernelGGL((k_step_hd<QUAD_ENV_HOVER, false, SP>), grid, blk2, 0, s, QD_KARGS);
-    const bool wide = h_wide(h, count);
-    const bool nt = nt_state(h, count);
-    if (hd_form(h, count)) {
-      const dim3 grid(unsigned((int64_t(count) + 63) / 64)), blk2(128);
-      if (h->spec) { QD_LAUNCH_HD(true) } else { QD_LAUNCH_HD(false) }
-    } else if (!wide) {
-      const dim3 grid(unsigned((int64_t(count) + 63) / 64)), blk2(128);
-      if (h->spec) { QD_LAUNCH_H(true, 64) } else { QD_LAUNCH_H(false, 64) }
-    } else {
-      const dim3 grid(unsigned((int64_t(count) + 255) / 256)), blk2(512);
-      if (h->spec) { QD_LAUNCH_H(true, 256) } else { QD_LAUNCH_H(false, 256) }
-    }
-#undef QD_LAUNCH_H
-#undef QD_LAUNCH_H2
-#undef QD_LAUNCH_HD
-#undef QD_KARGS
+    const bool wide = h_wide(h, count), nt = nt_state(h, count), hd = hd_form(h, count);
+    const HGeom hg(count, wide);
+    with_kind(traj, ctbr, [&](auto kind, auto cb) {
+      with_bool(h->spec, [&](auto sp) {
+        constexpr int KIND = decltype(kind)::value;
+        constexpr bool CTBR = decltype(cb)::value, SPEC = decltype(sp)::value;
+        // the kernels' leading arguments are the preloaded ones (k_step_h)
+        if (hd)
+          hipLaunchKernelGGL((k_step_hd<KIND, CTBR, SPEC>), hg.grid, hg.block, 0, s, kp.tiles, a, kp.tile_bytes,
+                             kp.first, kp.count, h->kdev, kp, *out);
+        else
+          with_bool(wide, [&](auto w) {
+            with_bool(nt, [&](auto n) {
+              hipLaunchKernelGGL((k_step_h<KIND, CTBR, SPEC, decltype(w)::value ? 256 : 64, decltype(n)::value>),
+                                 hg.grid, hg.block, 0, s, kp.tiles, a, kp.tile_bytes, kp.first, kp.count, h->kdev,
+                                 kp, *out);
+            });
+          });
+      });
+    });
   }
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
@@ -1295,22 +1290,17 @@ int quad_observe(QuadHandle* h, float* obs, float* state12, void* stream) {
     HIP_TRY(hipGetLastError());
     return QUAD_OK;
   }
-  if (wrap_relpos(h->cfg.wrapper))
-    hipLaunchKernelGGL(k_observe<true>, dim3(grid_of(h->n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       h->kp, obs, state12);
-  else
-    hipLaunchKernelGGL(k_observe<false>, dim3(grid_of(h->n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                       h->kp, obs, state12);
+  with_bool(wrap_relpos(h->cfg.wrapper), [&](auto relpos) {
+    hipLaunchKernelGGL(k_observe<decltype(relpos)::value>, dim3(grid_of(h->n)), dim3(BLOCK), 0,
+                       static_cast<hipStream_t>(stream), h->kp, obs, state12);
+  });
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }
 
 int quad_mem_floor(QuadHandle* h, const float* actions, const QuadStepOut* out, void* stream) {
   if (!h || !actions || !out) return fail(QUAD_EINVAL, "handle/actions/out is NULL");
-  if (!out->obs || !out->reward || !out->terminated || !out->truncated)
-    return fail(QUAD_EINVAL, "obs, reward, terminated and truncated are required");
-  if ((reinterpret_cast<uintptr_t>(actions) | reinterpret_cast<uintptr_t>(out->obs)) & 15u)
-    return fail(QUAD_EINVAL, "actions and obs must be 16-byte aligned");
+  if (int rc = check_step_out(out, actions)) return rc;
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
     return fail(QUAD_EINVAL, "quad_mem_floor: hover / trajectory kinds");
   if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_mem_floor: no RELPOS (7-D obs rows)");
@@ -1318,10 +1308,9 @@ int quad_mem_floor(QuadHandle* h, const float* actions, const QuadStepOut* out, 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid(unsigned((int64_t(h->n) + 255) / 256)), blk(256);
   const float4* a = reinterpret_cast<const float4*>(actions);
-  if (nt_state(h, h->n))
-    hipLaunchKernelGGL(k_mem_floor<2>, grid, blk, 0, s, h->kp, a, *out);
-  else
-    hipLaunchKernelGGL(k_mem_floor<0>, grid, blk, 0, s, h->kp, a, *out);
+  with_bool(nt_state(h, h->n), [&](auto nt) {
+    hipLaunchKernelGGL(k_mem_floor<decltype(nt)::value ? 2 : 0>, grid, blk, 0, s, h->kp, a, *out);
+  });
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }
@@ -1334,40 +1323,29 @@ int quad_step_random(QuadHandle* h, uint32_t step0, int32_t steps, const QuadSte
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
     return fail(QUAD_EINVAL, "quad_step_random drives the hover / trajectory kinds");
   if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_step_random: wrapper NONE or CTBR");
-  if (!out->obs || !out->reward || !out->terminated || !out->truncated)
-    return fail(QUAD_EINVAL, "obs, reward, terminated and truncated are required");
+  if (int rc = check_step_out(out, actions_out, "obs and actions_out")) return rc;
   if (out->motor_commands || out->voltage_scale || out->state12 || out->target_info)
     return fail(QUAD_EINVAL, "quad_step_random writes obs, reward, flags and terminal_obs only");
-  if ((reinterpret_cast<uintptr_t>(out->obs) | reinterpret_cast<uintptr_t>(actions_out)) & 15u)
-    return fail(QUAD_EINVAL, "obs and actions_out must be 16-byte aligned");
   if (int64_t(steps) * h->n * 48 > int64_t(UINT32_MAX))
     return fail(QUAD_EINVAL, "steps * N too large for one launch (time-major rows use 32-bit byte offsets)");
   DeviceGuard g(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   float4* ao = reinterpret_cast<float4*>(actions_out);
-  const bool traj = h->cfg.env_kind == QUAD_ENV_TRAJ, ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
-#define QD_LAUNCH_RH(SP, RB)                                                                                     \
-  if (traj && ctbr)                                                                                      \
-    hipLaunchKernelGGL((k_step_random_h<QUAD_ENV_TRAJ, true, SP, RB>), grid, blk2, 0, s, h->kdev, h->kp, *out, ao, step0, steps);   \
-  else if (traj)                                                                                         \
-    hipLaunchKernelGGL((k_step_random_h<QUAD_ENV_TRAJ, false, SP, RB>), grid, blk2, 0, s, h->kdev, h->kp, *out, ao, step0, steps);  \
-  else if (ctbr)                                                                                         \
-    hipLaunchKernelGGL((k_step_random_h<QUAD_ENV_HOVER, true, SP, RB>), grid, blk2, 0, s, h->kdev, h->kp, *out, ao, step0, steps);  \
-  else                                                                                                   \
-    hipLaunchKernelGGL((k_step_random_h<QUAD_ENV_HOVER, false, SP, RB>), grid, blk2, 0, s, h->kdev, h->kp, *out, ao, step0, steps);
   // 64-env blocks up to H_SMALL envs, 256 above at every size: the K-step form reads and writes its
   // state once per launch, so k_step_h's reason for 64-env blocks from 2M envs (nt state streams)
   // does not apply -- 2M envs 93.6 vs 97.4 us per step, 4M 182.9 vs 195.7 with 64-env blocks
   // (profiles/r06/kstep_random_block_ab.txt). QUADENV_HBLOCK pins it.
   const bool wide = h->hblock ? h->hblock == 256 : h->n > H_SMALL;
-  if (!wide) {
-    const dim3 grid(unsigned((int64_t(h->n) + 63) / 64)), blk2(128);
-    if (h->spec) { QD_LAUNCH_RH(true, 64) } else { QD_LAUNCH_RH(false, 64) }
-  } else {
-    const dim3 grid(unsigned((int64_t(h->n) + 255) / 256)), blk2(512);
-    if (h->spec) { QD_LAUNCH_RH(true, 256) } else { QD_LAUNCH_RH(false, 256) }
-  }
-#undef QD_LAUNCH_RH
+  const HGeom hg(h->n, wide);
+  with_kind(h->cfg.env_kind == QUAD_ENV_TRAJ, h->cfg.wrapper == QUAD_WRAP_CTBR, [&](auto kind, auto cb) {
+    with_bool(h->spec, [&](auto sp) {
+      with_bool(wide, [&](auto w) {
+        hipLaunchKernelGGL((k_step_random_h<decltype(kind)::value, decltype(cb)::value, decltype(sp)::value,
+                                            decltype(w)::value ? 256 : 64>),
+                           hg.grid, hg.block, 0, s, h->kdev, h->kp, *out, ao, step0, steps);
+      });
+    });
+  });
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }
@@ -1455,10 +1433,10 @@ int quad_waypoints_begin(QuadHandle* h, const QuadWaypoints* w, const QuadWaypoi
   if (!obs) return fail(QUAD_EINVAL, "obs is NULL");
   DeviceGuard g(h->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (wrap_relpos(h->cfg.wrapper))
-    hipLaunchKernelGGL(k_waypoints_begin<true>, dim3(grid_of(h->n)), dim3(BLOCK), 0, st, h->kp, *w, *s, obs);
-  else
-    hipLaunchKernelGGL(k_waypoints_begin<false>, dim3(grid_of(h->n)), dim3(BLOCK), 0, st, h->kp, *w, *s, obs);
+  with_bool(wrap_relpos(h->cfg.wrapper), [&](auto relpos) {
+    hipLaunchKernelGGL(k_waypoints_begin<decltype(relpos)::value>, dim3(grid_of(h->n)), dim3(BLOCK), 0, st, h->kp,
+                       *w, *s, obs);
+  });
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }

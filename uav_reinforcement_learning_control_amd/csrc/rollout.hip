@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "../../include/quadenv.h"
+#include "dispatch.h"
 #include "env_tiles.h"
 #include "kconsts_default.h"
 #include "policy_net.h"
@@ -99,6 +100,7 @@ __device__ __forceinline__ void reset_words_shfl(const KParams& p, uint32_t (&re
   __builtin_amdgcn_wave_barrier();
 }
 
+// (quadenv.hip's store_row12 takes 32-bit byte offsets; the time-major rows here can lie past 4 GiB)
 __device__ __forceinline__ void store_row(float* __restrict__ base, size_t row, const float v[12]) {
   float4* b4 = reinterpret_cast<float4*>(base + row * 12);
   b4[0] = make_float4(v[0], v[1], v[2], v[3]);
@@ -239,7 +241,7 @@ __device__ __forceinline__ void rollout_body(const KConsts<float>& K, KParams p,
     const bool rs = ok && done;
     float u16[16];
     reset_words_shfl<NT == 2 ? 63 : 31>(p, renv[w], rep[w], uint32_t(i), ep, owner && done, rs, u16);
-    if (rs) {
+    if (rs) {  // (quadenv.hip's reset_from_u16, written out: as a call it moved this kernel's spills)
       float init12[12], tgt[3], s12[12];
       reset_affine_u(K.init_lo, K.init_span, K.tgt_lo, K.tgt_span, u16, init12, tgt);
       env_reset_from<float, KIND>(K, e, init12, tgt, ob, s12);
@@ -305,24 +307,18 @@ hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* pack
 
 }  // namespace
 
-template <int NT, bool SPEC>
-hipError_t launch_nt(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, const float* packed,
-                     const RollArgs& a, hipStream_t s) {
-  if (env_kind == QUAD_ENV_TRAJ)
-    return ctbr ? launch<QUAD_ENV_TRAJ, true, NT, SPEC>(kc, kp, packed, a, s)
-                : launch<QUAD_ENV_TRAJ, false, NT, SPEC>(kc, kp, packed, a, s);
-  return ctbr ? launch<QUAD_ENV_HOVER, true, NT, SPEC>(kc, kp, packed, a, s)
-              : launch<QUAD_ENV_HOVER, false, NT, SPEC>(kc, kp, packed, a, s);
-}
-
 hipError_t launch_rollout(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
                           const float* packed, const RollArgs& a, hipStream_t s) {
   const char* v = std::getenv("QUADENV_ROLLOUT_NT");  // A/B override: 1 or 2 tiles per wave
   const int nt = v && std::atoi(v) == 1 ? 1 : (v && std::atoi(v) == 2 ? 2 : ROLLOUT_NT_DEFAULT);
-  if (nt == 1) return spec ? launch_nt<1, true>(kc, kp, env_kind, ctbr, packed, a, s)
-                           : launch_nt<1, false>(kc, kp, env_kind, ctbr, packed, a, s);
-  return spec ? launch_nt<2, true>(kc, kp, env_kind, ctbr, packed, a, s)
-              : launch_nt<2, false>(kc, kp, env_kind, ctbr, packed, a, s);
+  return with_kind(env_kind == QUAD_ENV_TRAJ, ctbr, [&](auto kind, auto cb) {
+    return with_bool(nt == 1, [&](auto one) {
+      return with_bool(spec, [&](auto sp) {
+        return launch<decltype(kind)::value, decltype(cb)::value, decltype(one)::value ? 1 : 2, decltype(sp)::value>(
+            kc, kp, packed, a, s);
+      });
+    });
+  });
 }
 
 }  // namespace quadenv
