@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define QUADENV_ABI_VERSION 5
+#define QUADENV_ABI_VERSION 6
 
 enum { QUAD_OK = 0, QUAD_EINVAL = -1, QUAD_EHIP = -2, QUAD_ENOMEM = -3, QUAD_EMODEL = -4 };
 /* QUAD_ENV_BRAX_HOVER / QUAD_ENV_BRAX_TRAJ: the brax Env API siblings of the same path
@@ -248,6 +248,88 @@ int quad_waypoints_begin(QuadHandle* h, const QuadWaypoints* w, const QuadWaypoi
 int quad_waypoints_update(QuadHandle* h, const QuadWaypoints* w, const QuadWaypointState* s,
                           const float* state12, const float* reward, const uint8_t* terminated,
                           const uint8_t* truncated, void* stream);
+
+/* ---- Cascaded PID baseline: the reference's hover controller (pid_controller.py:40-191) and its
+ * trajectory-following sibling (pid_controller_world_frame.py:86-283), batched, with one gain set per
+ * env. Hover / trajectory kinds, wrapper NONE (the law emits the normalized thrust / torque action). */
+enum { QUAD_PID_YAW_FRAME = 0,     /* pid_controller.py: no feed-forward, yaw-only rotation, yaw setpoint 0 */
+       QUAD_PID_WORLD_FRAME = 1 }; /* _world_frame.py: velocity-error D term, acceleration feed-forward,
+                                      Z-Y-X Euler rotation, yaw toward the target velocity's heading */
+/* The 21 numbers CascadedPIDController.__init__ reads from pid_gains.json, in its order, and the one
+ * plant constant of the law the handle's QuadCfg does not hold (drone_config.py MASS). The others come
+ * from the handle: G = -gravity[2], DT = timestep, MAX_TOTAL_THRUST = 4 max_motor_thrust, MAX_TORQUE =
+ * max_torque, ARM_LENGTH = arm_length, IXX / IYY / IZZ = inertia[]. */
+typedef struct QuadPidGains {
+  double kp_xy, kd_xy, ki_xy;               /* position_xy */
+  double kp_z, kd_z, ki_z;                  /* position_z */
+  double kp_att, kd_att;                    /* attitude */
+  double kp_yaw, kd_yaw;                    /* yaw */
+  double ki_rate_torque, rate_int_max;      /* rate: ki_torque, integral_max */
+  double axy_max, az_min, az_max, tilt_max; /* limits */
+  double z_int_max, xy_int_max;             /* limits: z_integral_max, xy_integral_max */
+  double torque_motor_frac, torque_abs_max, yaw_torque_scale; /* limits: torque_motor_fraction, ... */
+  double mass;                              /* drone_config.py MASS (0.2227) */
+} QuadPidGains;
+/* pid_gains.json's committed values and MASS. */
+int quad_pid_default_gains(QuadPidGains* g);
+
+/* One CascadedPIDController.compute per row, float64 on the float32 inputs: state12 [n,12] (info["state"]),
+ * target9 [n,9] (info["target"], ["target_vel"], ["target_acc"]; the yaw-frame law reads the first three),
+ * row i with gain set set_of[i] (0 if set_of is NULL) of the device table gains[n_sets]. integ: device
+ * float64 [6][n], field-major (xy integral 2, z integral, rate-torque integral 3), read and updated
+ * (zero it where the reference calls controller.reset()). actions: [n,4] float32, clipped to [-1, 1].
+ * diag (NULL to skip): float64 [n,6] = des_rate 3, des_att 3. A row whose set_of entry is outside
+ * [0, n_sets) reads no gain set: its action is zero and its integrators are left as they were. */
+int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of, int32_t mode,
+                 const float* state12, const float* target9, int32_t n, double* integ, float* actions,
+                 double* diag, void* stream);
+
+/* info["target"], ["target_vel"], ["target_acc"] as the env's reset / last step reported them, for the
+ * current step count (target_info [N,9]; hover / trajectory kinds): what a host loop hands the law
+ * before its first quad_step, next to quad_observe's state12. */
+int quad_target_info(QuadHandle* h, float* target_info, void* stream);
+
+/* Per-env episode metrics (device [N] arrays, all required), accumulated as auto_tune_pid.py:66-124
+ * reads them from info["state"] after each step. status: 0 still running after max_steps iterations,
+ * 1 terminated, 2 truncated, 3 invalid (set_of out of range: no step taken). */
+enum { QUAD_PID_RUNNING = 0, QUAD_PID_TERMINATED = 1, QUAD_PID_TRUNCATED = 2, QUAD_PID_INVALID = 3 };
+typedef struct QuadPidMetrics {
+  int32_t* steps;
+  int32_t* status;
+  double* total_reward;
+  double* pos_err_sum;      /* sum of |pos after the step - target read before it| (float32 difference) */
+  double* pos_err_sq;       /* sum of its squares */
+  double* pos_err_max;
+  double* yaw_rate_abs_sum; /* yaw rate = state[11] */
+  double* yaw_rate_sum;
+  double* yaw_rate_sq;
+  double* yaw_rate_abs_max;
+  int32_t* yaw_rate_sign_changes; /* steps whose np.sign(yaw rate) differs from the step before (zeros count) */
+  double* yaw_rate_delta_sum;     /* sum of |yaw rate - yaw rate of the step before| */
+} QuadPidMetrics;
+
+/* The fused closed loop, ONE launch: every env runs (law -> HoverEnv.step) until its first terminated or
+ * truncated step or for max_steps iterations, its state in registers throughout; it is then frozen (no
+ * reset) and its state after its last step is stored. The law's inputs are what quad_observe /
+ * quad_target_info report before the first step and the step's own state12 / target_info afterwards --
+ * the loop of pid_controller.py:434-439. Bit-identical to quad_pid_act + quad_step per step on a handle
+ * with auto_reset = 0. integ (NULL: start from zero, not stored): float64 [6][N] in / out.
+ * Traces (NULL to skip) are time-major for the first trace_envs envs: trace_actions
+ * [max_steps][trace_envs,4], trace_state12 [max_steps][trace_envs,12]; rows past an env's last step are
+ * not written; max_steps * trace_envs * 48 < 2^32. */
+typedef struct QuadPidRun {
+  const QuadPidGains* gains; /* device [n_sets] */
+  const int32_t* set_of;     /* device [N] or NULL (set 0) */
+  int32_t n_sets;            /* >= 1 */
+  int32_t mode;              /* QUAD_PID_YAW_FRAME | QUAD_PID_WORLD_FRAME */
+  int32_t max_steps;         /* >= 1 */
+  int32_t trace_envs;        /* 0 .. N */
+  double* integ;
+  float* trace_actions;
+  float* trace_state12;
+  QuadPidMetrics metrics;
+} QuadPidRun;
+int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream);
 
 /* PPO rollout support (row P of the scope table): generalized advantage estimation over a
  * time-major rollout, SB3 RolloutBuffer.compute_returns_and_advantage semantics.

@@ -20,7 +20,9 @@ QUAD_ADV_GIVEN = 3        # ... : the sums are in QuadPPOBatch.adv_sums (quad_pp
 ADV_SUM_DOUBLES = 512     # QUAD_ADV_SUM_DOUBLES: one minibatch's block sums
 ENV_HOVER, ENV_TRAJ, ENV_BRAX_HOVER, ENV_BRAX_TRAJ = 0, 1, 2, 3
 WRAP_NONE, WRAP_CTBR, WRAP_RELPOS, WRAP_CTBR_RELPOS = 0, 1, 2, 3
-ABI_VERSION = 5
+ABI_VERSION = 6
+PID_YAW_FRAME, PID_WORLD_FRAME = 0, 1
+PID_RUNNING, PID_TERMINATED, PID_TRUNCATED, PID_INVALID = 0, 1, 2, 3
 
 
 class QuadCfg(C.Structure):
@@ -76,6 +78,34 @@ class QuadWaypointState(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wp_idx", "reached", "laps", "steps", "status", "total_reward")]
 
 
+# QuadPidGains: the 21 numbers of pid_gains.json in CascadedPIDController.__init__'s order, then MASS
+PID_GAIN_FIELDS = ("kp_xy", "kd_xy", "ki_xy", "kp_z", "kd_z", "ki_z", "kp_att", "kd_att", "kp_yaw", "kd_yaw",
+                   "ki_rate_torque", "rate_int_max", "axy_max", "az_min", "az_max", "tilt_max", "z_int_max",
+                   "xy_int_max", "torque_motor_frac", "torque_abs_max", "yaw_torque_scale", "mass")
+
+
+class QuadPidGains(C.Structure):
+    _fields_ = [(n, C.c_double) for n in PID_GAIN_FIELDS]
+
+
+# QuadPidMetrics: device [N] arrays; (name, torch dtype name)
+PID_METRIC_FIELDS = (("steps", "int32"), ("status", "int32"), ("total_reward", "float64"),
+                     ("pos_err_sum", "float64"), ("pos_err_sq", "float64"), ("pos_err_max", "float64"),
+                     ("yaw_rate_abs_sum", "float64"), ("yaw_rate_sum", "float64"), ("yaw_rate_sq", "float64"),
+                     ("yaw_rate_abs_max", "float64"), ("yaw_rate_sign_changes", "int32"),
+                     ("yaw_rate_delta_sum", "float64"))
+
+
+class QuadPidMetrics(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _ in PID_METRIC_FIELDS]
+
+
+class QuadPidRun(C.Structure):
+    _fields_ = [("gains", C.c_void_p), ("set_of", C.c_void_p), ("n_sets", C.c_int32), ("mode", C.c_int32),
+                ("max_steps", C.c_int32), ("trace_envs", C.c_int32), ("integ", C.c_void_p),
+                ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("metrics", QuadPidMetrics)]
+
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -103,7 +133,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_policy_packed_floats", "quad_policy_pack", "quad_policy_act", "quad_rollout_post", "quad_rollout",
            "quad_waypoints_begin", "quad_waypoints_update", "quad_ppo_workspace_bytes", "quad_ppo_grad",
            "quad_ppo_grad_form", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_permutation", "quad_adam_workspace_bytes",
-           "quad_clip_adam")
+           "quad_clip_adam",
+           "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info")
 
 
 class QuadRollout(C.Structure):
@@ -190,6 +221,12 @@ def _declare(L):
     L.quad_adam_workspace_bytes.argtypes = [C.POINTER(QuadAdam)]
     L.quad_adam_workspace_bytes.restype = C.c_int64
     L.quad_clip_adam.argtypes = [C.POINTER(QuadAdam), vp, C.c_int64, vp]
+    L.quad_pid_default_gains.argtypes = [C.POINTER(QuadPidGains)]
+    L.quad_pid_act.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.quad_pid_episode.argtypes = [vp, C.POINTER(QuadPidRun), vp]
+    L.quad_target_info.argtypes = [vp, vp, vp]
+    for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info"):
+        getattr(L, n).restype = C.c_int
     for n in ("quad_clip_adam", "quad_ppo_grad", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_default_cfg", "quad_create", "quad_seed", "quad_reset", "quad_step", "quad_step_range", "quad_observe", "quad_terminated", "quad_step_random",
               "quad_random_actions", "quad_get_state", "quad_set_state", "quad_gae",
               "quad_policy_pack", "quad_policy_act", "quad_rollout_post", "quad_rollout",

@@ -1,0 +1,223 @@
+"""Batched cascaded-PID baseline (the reference's pid_controller.py / pid_controller_world_frame.py).
+
+  * ``PIDGains``      one gain set: the 21 numbers ``CascadedPIDController.__init__`` reads from
+                      ``pid_gains.json`` (+ MASS), with ``from_json`` / ``to_json`` in that file's layout,
+                      so tuned gains drop into the reference.
+  * ``gain_table``    gain sets stacked into the device table the kernels index per env.
+  * ``pid_act``       the law alone (``quad_pid_act``): the building block of host loops.
+  * ``pid_episode``   the fused closed loop (``quad_pid_episode``): every env runs law -> env step until
+                      it terminates, truncates or ``max_steps`` pass; per-env metrics as tensors.
+  * ``pid_score``     ``compute_performance_score`` (auto_tune_pid.py:127-157), vectorised.
+
+``QuadVecEnv.pid_act`` / ``QuadVecEnv.pid_episode`` are these functions bound as methods.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+from dataclasses import dataclass, fields
+from typing import Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _native as N
+
+MODES = {"yaw_frame": N.PID_YAW_FRAME, "pid_controller": N.PID_YAW_FRAME, N.PID_YAW_FRAME: N.PID_YAW_FRAME,
+         "world_frame": N.PID_WORLD_FRAME, "pid_controller_world_frame": N.PID_WORLD_FRAME,
+         N.PID_WORLD_FRAME: N.PID_WORLD_FRAME}
+STATUS = {N.PID_RUNNING: "running", N.PID_TERMINATED: "terminated", N.PID_TRUNCATED: "truncated",
+          N.PID_INVALID: "invalid"}
+
+# field -> (pid_gains.json section, key), in QuadPidGains order
+_JSON = (("kp_xy", "position_xy", "kp"), ("kd_xy", "position_xy", "kd"), ("ki_xy", "position_xy", "ki"),
+         ("kp_z", "position_z", "kp"), ("kd_z", "position_z", "kd"), ("ki_z", "position_z", "ki"),
+         ("kp_att", "attitude", "kp"), ("kd_att", "attitude", "kd"), ("kp_yaw", "yaw", "kp"), ("kd_yaw", "yaw", "kd"),
+         ("ki_rate_torque", "rate", "ki_torque"), ("rate_int_max", "rate", "integral_max"),
+         ("axy_max", "limits", "axy_max"), ("az_min", "limits", "az_min"), ("az_max", "limits", "az_max"),
+         ("tilt_max", "limits", "tilt_max"), ("z_int_max", "limits", "z_integral_max"),
+         ("xy_int_max", "limits", "xy_integral_max"), ("torque_motor_frac", "limits", "torque_motor_fraction"),
+         ("torque_abs_max", "limits", "torque_abs_max"), ("yaw_torque_scale", "limits", "yaw_torque_scale"),
+         ("mass", "drone_params", "mass_kg"))
+
+
+@dataclass
+class PIDGains:
+    """Defaults: the reference's committed pid_gains.json and drone_config.py MASS."""
+    kp_xy: float = 4.0
+    kd_xy: float = 3.5
+    ki_xy: float = 0.25
+    kp_z: float = 6.0
+    kd_z: float = 6.5
+    ki_z: float = 0.8
+    kp_att: float = 180.0
+    kd_att: float = 26.0
+    kp_yaw: float = 80.0
+    kd_yaw: float = 30.0
+    ki_rate_torque: float = 0.025
+    rate_int_max: float = 0.01
+    axy_max: float = 4.5
+    az_min: float = -5.0
+    az_max: float = 12.0
+    tilt_max: float = 0.25
+    z_int_max: float = 2.0
+    xy_int_max: float = 0.4
+    torque_motor_frac: float = 0.7
+    torque_abs_max: float = 0.05
+    yaw_torque_scale: float = 0.6
+    mass: float = 0.2227
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "PIDGains":
+        g = cls()
+        for f, sec, key in _JSON:
+            if sec in d and key in d[sec]:
+                setattr(g, f, float(d[sec][key]))
+        return g
+
+    @classmethod
+    def from_json(cls, path: str) -> "PIDGains":
+        with open(path) as fh:
+            return cls.from_dict(json.load(fh))
+
+    def to_dict(self, notes: Optional[dict] = None) -> dict:
+        d: dict = {}
+        for f, sec, key in _JSON:
+            d.setdefault(sec, {})[key] = float(getattr(self, f))
+        if notes:
+            d["tuning_notes"] = notes
+        return d
+
+    def to_json(self, path: str, notes: Optional[dict] = None) -> None:
+        """pid_gains.json's layout: CascadedPIDController(json.load(open(path))) accepts it."""
+        with open(path, "w") as fh:
+            json.dump(self.to_dict(notes), fh, indent=2)
+
+    def vector(self) -> np.ndarray:
+        return np.array([getattr(self, f) for f in N.PID_GAIN_FIELDS], np.float64)
+
+
+assert tuple(f.name for f in fields(PIDGains)) == N.PID_GAIN_FIELDS
+
+GainsLike = Union[None, PIDGains, Sequence[PIDGains], np.ndarray, torch.Tensor]
+
+
+def gain_table(gains: GainsLike, device) -> torch.Tensor:
+    """[n_sets, 22] float64 on `device`: rows are QuadPidGains structs. Accepts one PIDGains, a sequence
+    of them, or an array / tensor already in that layout (the tuner builds its population that way)."""
+    if gains is None:
+        gains = PIDGains()
+    if isinstance(gains, PIDGains):
+        gains = [gains]
+    if isinstance(gains, torch.Tensor):
+        t = gains.to(device=device, dtype=torch.float64)
+    elif isinstance(gains, np.ndarray):
+        t = torch.from_numpy(np.asarray(gains, np.float64)).to(device)
+    else:
+        t = torch.from_numpy(np.stack([g.vector() for g in gains])).to(device)
+    t = t.reshape(-1, len(N.PID_GAIN_FIELDS)).contiguous()
+    if t.shape[0] < 1:
+        raise ValueError("at least one gain set is required")
+    return t
+
+
+def _set_of(set_of, n: int, device) -> Optional[torch.Tensor]:
+    if set_of is None:
+        return None
+    t = torch.as_tensor(set_of).to(device=device, dtype=torch.int32).contiguous()
+    if tuple(t.shape) != (n,):
+        raise ValueError(f"set_of must have shape ({n},)")
+    return t
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def pid_act(env, state12: torch.Tensor, target9: torch.Tensor, integ: torch.Tensor, gains: GainsLike = None,
+            set_of=None, mode="yaw_frame", out: Optional[torch.Tensor] = None, diag: Optional[torch.Tensor] = None):
+    """One CascadedPIDController.compute per row. state12 [n,12], target9 [n,9] float32; integ float64
+    [6,n] (field-major; read and updated in place; zero it at an episode start); gains: see gain_table;
+    set_of [n] int32 or None (set 0). Returns the actions [n,4] (and fills diag [n,6] float64 when given)."""
+    n = int(state12.shape[0])
+    env._check(state12, (n, 12), torch.float32)
+    env._check(target9, (n, 9), torch.float32)
+    env._check(integ, (6, n), torch.float64)
+    out = torch.empty(n, 4, dtype=torch.float32, device=env.device) if out is None else out
+    env._check(out, (n, 4), torch.float32)
+    if diag is not None:
+        env._check(diag, (n, 6), torch.float64)
+    tab = gain_table(gains, env.device)
+    so = _set_of(set_of, n, env.device)
+    N.check(N.lib().quad_pid_act(env._h, _ptr(tab), tab.shape[0], _ptr(so), MODES[mode], _ptr(state12), _ptr(target9),
+                                 n, _ptr(integ), _ptr(out), _ptr(diag), env._stream()), "quad_pid_act")
+    return out
+
+
+def target_info(env, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """info["target"], ["target_vel"], ["target_acc"] ([N,9]) for the envs' current step count."""
+    out = torch.empty(env.num_envs, 9, dtype=torch.float32, device=env.device) if out is None else out
+    env._check(out, (env.num_envs, 9), torch.float32)
+    N.check(N.lib().quad_target_info(env._h, _ptr(out), env._stream()), "quad_target_info")
+    return out
+
+
+def pid_episode(env, gains: GainsLike = None, set_of=None, mode="yaw_frame", max_steps: Optional[int] = None,
+                trace_envs: int = 0, integ: Optional[torch.Tensor] = None) -> dict:
+    """The fused closed loop from the envs' current state (call env.reset() first). Every env runs until
+    its first terminated / truncated step or `max_steps` (default: the env's max_episode_steps) and is
+    then frozen, not reset. Returns the QuadPidMetrics arrays as tensors ([N]; status codes in STATUS);
+    with trace_envs = M > 0 also "actions" [max_steps, M, 4] and "state12" [max_steps, M, 12] of the
+    first M envs (rows past an env's last step stay zero)."""
+    n, dev = env.num_envs, env.device
+    T = int(env.max_episode_steps if max_steps is None else max_steps)
+    M = int(trace_envs)
+    tab = gain_table(gains, dev)
+    so = _set_of(set_of, n, dev)
+    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+    if M > 0 and T > 0:
+        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
+        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
+    if integ is not None:
+        env._check(integ, (6, n), torch.float64)
+    run = N.QuadPidRun(gains=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
+                       mode=MODES[mode], max_steps=T, trace_envs=M,
+                       integ=None if integ is None else integ.data_ptr(),
+                       trace_actions=res["actions"].data_ptr() if "actions" in res else None,
+                       trace_state12=res["state12"].data_ptr() if "state12" in res else None,
+                       metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
+    N.check(N.lib().quad_pid_episode(env._h, C.byref(run), env._stream()), "quad_pid_episode")
+    return res
+
+
+def pid_score(metrics: dict) -> dict:
+    """compute_performance_score (auto_tune_pid.py:127-157) for every episode of `metrics` (the tensors
+    pid_episode returns): the analyses it reads -- oscillation energy, max |yaw rate|, sign-change
+    frequency (analyze_yaw_oscillation), mean position error (analyze_position_tracking) -- from the
+    per-episode sums. Episodes with no step (status invalid) score 0."""
+    steps = metrics["steps"].to(torch.float64)
+    ok = steps > 0
+    n = torch.where(ok, steps, torch.ones_like(steps))
+    dt = 0.01  # drone_config.DT: the reference's oscillation_freq uses it whatever the env's timestep
+    osc_energy = metrics["yaw_rate_delta_sum"].to(torch.float64)
+    rate_max = metrics["yaw_rate_abs_max"].to(torch.float64)
+    osc_freq = metrics["yaw_rate_sign_changes"].to(torch.float64) / (n * dt)
+    pos_err_mean = metrics["pos_err_sum"].to(torch.float64) / n
+    yaw_score = 0.5 * (1.0 - torch.clamp(osc_energy / 1.0, max=1.0)) \
+        + 0.3 * (1.0 - torch.clamp(rate_max / 3.0, max=1.0)) \
+        + 0.2 * torch.clamp(1.0 - osc_freq / 5.0, min=0.0)
+    pos_score = 1.0 / (1.0 + pos_err_mean)
+    total = 0.6 * yaw_score + 0.4 * pos_score
+    zero = torch.zeros_like(total)
+    return {"yaw_score": torch.where(ok, yaw_score, zero), "pos_score": torch.where(ok, pos_score, zero),
+            "total_score": torch.where(ok, total, zero), "oscillation_energy": osc_energy,
+            "pos_error_mean": pos_err_mean, "rate_max": rate_max}
+
+
+def gains_from_vector(v) -> PIDGains:
+    v = np.asarray(v, np.float64).reshape(-1)
+    return PIDGains(**{f: float(x) for f, x in zip(N.PID_GAIN_FIELDS, v)})
+
+
+__all__ = ["PIDGains", "gain_table", "pid_act", "pid_episode", "pid_score", "target_info", "gains_from_vector",
+           "MODES", "STATUS"]

@@ -125,6 +125,20 @@ __device__ __forceinline__ void load_env_motion(const KParams& p, int i, EnvRegs
   e.step = int32_t(S.ldu(F_STEP, o));
 }
 
+// info["target", "target_vel", "target_acc"] for step count e.step of the running episode: of the step
+// just taken (before any auto-reset), or what reset() reported when e.step == 0. `ep` is the episode
+// counter as loaded (the running episode is ep - 1). One definition for the step kernels (quadenv.hip)
+// and the PID kernels (pid.hip), whose fused loop must hand the law the same words quad_step reports.
+template <int KIND>
+__device__ __forceinline__ void target_info_of(const KConsts<float>& K, const KParams& p, int i,
+                                               const EnvRegs<float>& e, uint32_t ep, float o[9]) {
+  o[0] = e.target[0]; o[1] = e.target[1]; o[2] = e.target[2];
+#pragma unroll
+  for (int j = 3; j < 9; j++) o[j] = 0.f;
+  if (KIND == QUAD_ENV_TRAJ)  // the target register holds the start position (= traj_pos[0])
+    traj_spline_info(K, p.seed, p.gid_base + uint64_t(i), ep - 1u, e.target, e.step, o);
+}
+
 // A per-lane offset made opaque in the block that uses it (fresh_off): the field offsets o + f * 256
 // are then formed in THIS basic block, where instruction selection folds them into the store's
 // immediate. Without it the compiler CSEs them with the load burst's (a different block), and

@@ -22,6 +22,7 @@
 //   k_mem_floor          the step's loads and stores alone (bench.py's DRAM floor)
 //   k_random_actions     action_space.sample() stand-in (Philox), config 2
 //   k_gae                SB3 GAE(lambda) reverse scan, one thread per env
+// The cascaded PID baseline's kernels (k_pid_act, k_pid_episode, k_target_info) are in pid.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -36,6 +37,7 @@
 #include "dispatch.h"
 #include "env_tiles.h"
 #include "kconsts_default.h"
+#include "pid.h"
 #include "rollout.h"
 
 using namespace quadenv;
@@ -105,18 +107,6 @@ __device__ __forceinline__ void store_row12(float* __restrict__ base, uint32_t i
 __device__ __forceinline__ void store_obs7(float* __restrict__ out, int i, const float obs[3], const float prev[4]) {
 #pragma unroll
   for (int j = 0; j < 7; j++) out[size_t(i) * 7 + j] = j < 3 ? obs[j] : prev[j - 3];
-}
-
-// info["target", "target_vel", "target_acc"] of the step just taken (before any auto-reset);
-// `ep` is the episode counter as loaded (the running episode is ep - 1)
-template <int KIND>
-__device__ __forceinline__ void target_info_of(const KConsts<float>& K, const KParams& p, int i,
-                                               const EnvRegs<float>& e, uint32_t ep, float o[9]) {
-  o[0] = e.target[0]; o[1] = e.target[1]; o[2] = e.target[2];
-#pragma unroll
-  for (int j = 3; j < 9; j++) o[j] = 0.f;
-  if (KIND == QUAD_ENV_TRAJ)  // the target register holds the start position (= traj_pos[0])
-    traj_spline_info(K, p.seed, p.gid_base + uint64_t(i), ep - 1u, e.target, e.step, o);
 }
 
 __device__ __forceinline__ void store_target_info(float* __restrict__ out, int i, const float o[9]) {
@@ -1277,6 +1267,74 @@ int quad_rollout(QuadHandle* h, const float* packed, const QuadRollout* r, void*
              r->deterministic, r->seed, r->gamma};
   HIP_TRY(launch_rollout(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, packed, a,
                          static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- cascaded PID baseline (kernels: pid.hip)
+int quad_pid_default_gains(QuadPidGains* g) {
+  if (!g) return fail(QUAD_EINVAL, "gains is NULL");
+  pid_default_gains_fill(g);
+  return QUAD_OK;
+}
+
+// what quad_pid_act and quad_pid_episode ask of the handle and of the gain table
+static int check_pid(const QuadHandle* h, const char* who, const QuadPidGains* gains, int32_t n_sets, int32_t mode) {
+  const std::string w(who);
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
+  if (h->cfg.wrapper != QUAD_WRAP_NONE)
+    return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
+  if (mode != QUAD_PID_YAW_FRAME && mode != QUAD_PID_WORLD_FRAME) return fail(QUAD_EINVAL, w + ": unknown mode");
+  if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
+  if (!gains) return fail(QUAD_EINVAL, w + ": gains is NULL");
+  return QUAD_OK;
+}
+
+int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of, int32_t mode,
+                 const float* state12, const float* target9, int32_t n, double* integ, float* actions,
+                 double* diag, void* stream) {
+  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
+  if (int rc = check_pid(h, "quad_pid_act", gains, n_sets, mode)) return rc;
+  if (!state12 || !target9 || !integ || !actions)
+    return fail(QUAD_EINVAL, "quad_pid_act: state12, target9, integ and actions are required");
+  if (n < 1) return fail(QUAD_EINVAL, "quad_pid_act: n must be >= 1");
+  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, "quad_pid_act: actions must be 16-byte aligned");
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_pid_act(make_pid_plant(h->cfg), gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag,
+                         static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream) {
+  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
+  if (int rc = check_pid(h, "quad_pid_episode", r->gains, r->n_sets, r->mode)) return rc;
+  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_pid_episode: max_steps must be >= 1");
+  const QuadPidMetrics& m = r->metrics;
+  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
+      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
+      !m.yaw_rate_delta_sum)
+    return fail(QUAD_EINVAL, "quad_pid_episode: every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_pid_episode: trace_envs must be in [0, N]");
+  if ((r->trace_actions || r->trace_state12) && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
+      return fail(QUAD_EINVAL, "quad_pid_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
+      return fail(QUAD_EINVAL, "quad_pid_episode: traces must be 16-byte aligned");
+  }
+  DeviceGuard g(h->device);
+  QuadPidRun run = *r;
+  if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
+  HIP_TRY(launch_pid_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
+                             static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_target_info(QuadHandle* h, float* target_info, void* stream) {
+  if (!h || !target_info) return fail(QUAD_EINVAL, "handle/target_info is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_target_info: env_kind must be HOVER or TRAJ");
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_target_info(h->kdev, h->kp, h->cfg.env_kind, target_info, static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

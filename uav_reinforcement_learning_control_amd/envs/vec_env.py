@@ -233,6 +233,24 @@ class QuadVecEnv:
         return out
 
     # ------------------------------------------------------------------------------------
+    # the cascaded PID baseline (controllers.py): the law alone, the envs' current info["target*"],
+    # and the fused closed loop
+    def pid_act(self, state12, target9, integ, gains=None, set_of=None, mode="yaw_frame", out=None, diag=None):
+        from .. import controllers
+        return controllers.pid_act(self, state12, target9, integ, gains, set_of, mode, out, diag)
+
+    def current_target_info(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """info["target" / "target_vel" / "target_acc"] [N,9] for the current step count (what reset's
+        info holds before the first step; step(info="full") reports it afterwards)."""
+        from .. import controllers
+        return controllers.target_info(self, out)
+
+    def pid_episode(self, gains=None, set_of=None, mode="yaw_frame", max_steps: Optional[int] = None,
+                    trace_envs: int = 0, integ=None) -> dict:
+        from .. import controllers
+        return controllers.pid_episode(self, gains, set_of, mode, max_steps, trace_envs, integ)
+
+    # ------------------------------------------------------------------------------------
     _FIELDS = (("qpos", 11, np.float32), ("qvel", 10, np.float32), ("voltage", 1, np.float32),
                ("target", 3, np.float32), ("rate_int", 3, np.float32),
                ("step_count", 1, np.int32), ("episode", 1, np.uint32),

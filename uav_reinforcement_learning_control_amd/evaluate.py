@@ -11,6 +11,10 @@ waypoint lap (:440-612). Here N evaluations run at once on the GPU:
     count, waypoint switching within ``reach_radius``, lap completion, target update -- is the
     ``quad_waypoints_update`` kernel after each step.
 
+  * ``evaluate_pid_episodes`` -- the same N episodes flown by the cascaded PID baseline
+    (``controllers.py``; one fused launch), and ``compare_controllers`` -- a policy and the PID on the
+    same Philox episodes, side by side (the reference's controller comparison, batched).
+
 Actions are ``model.predict(obs, deterministic=True)``: the Gaussian mean clipped to the action
 box (SB3 clips Box actions in predict), computed by the MFMA policy kernel for 12-D obs and by the
 torch policy otherwise (RelPosActWrapper's 7-D obs). The model is an SB3 archive (the reference's
@@ -185,9 +189,101 @@ def evaluate_episodes(model, num_episodes: int = 1024, wrapper: Optional[str] = 
             "mean_length": float(l.mean()), "std_length": float(l.std())}
 
 
+def _summary(rewards, lengths, terminated, **extra) -> dict:
+    r, l = np.asarray(rewards, np.float64), np.asarray(lengths)
+    return {"rewards": r, "lengths": l, "terminated": np.asarray(terminated, bool),
+            "mean_reward": float(r.mean()), "std_reward": float(r.std()),
+            "mean_length": float(l.mean()), "std_length": float(l.std()), **extra}
+
+
+def _pid_mode(env: str, mode: Optional[str]) -> str:
+    """The reference flies HoverEnv with pid_controller.py and TrajectoryFollowEnv with the world-frame law."""
+    return mode or ("world_frame" if env in ("trajectory", "TrajectoryFollowEnv") else "yaw_frame")
+
+
+@torch.no_grad()
+def evaluate_pid_episodes(gains=None, num_episodes: int = 1024, env: str = "hover", mode: Optional[str] = None,
+                          max_episode_steps: Optional[int] = None, device="cuda", seed: int = 0,
+                          env_id_base: int = 0) -> dict:
+    """``evaluate_episodes`` with the cascaded PID baseline as the controller: the same resets (same seed
+    and env ids), each episode to termination or truncation, in one fused launch. `gains`: a PIDGains, a
+    pid_gains.json path, or None (the reference's committed gains). Returns evaluate_episodes' keys plus
+    pos_errors (per-episode mean position error), mean_pos_error, survival (fraction that reached the
+    time limit), reset_obs and the raw metrics."""
+    from .controllers import PIDGains, pid_episode
+    device = torch.device(device)
+    if isinstance(gains, str):
+        gains = PIDGains.from_json(gains)
+    e = QuadVecEnv(num_episodes, env=env, wrapper=None, device=device, seed=seed, env_id_base=env_id_base,
+                   max_episode_steps=max_episode_steps, auto_reset=False)
+    reset_obs = e.reset().clone()
+    m = pid_episode(e, gains, mode=_pid_mode(env, mode))
+    torch.cuda.synchronize(device)
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    e.close()
+    pe = m["pos_err_sum"] / np.maximum(m["steps"], 1)
+    return _summary(m["total_reward"], m["steps"], m["status"] == N.PID_TERMINATED, pos_errors=pe,
+                    mean_pos_error=float(pe.mean()), survival=float((m["status"] == N.PID_TRUNCATED).mean()),
+                    reset_obs=reset_obs.cpu().numpy(), metrics=m)
+
+
+@torch.no_grad()
+def compare_controllers(model, gains=None, num_episodes: int = 256, wrapper: Optional[str] = "auto",
+                        env: str = "hover", mode: Optional[str] = None, max_episode_steps: Optional[int] = None,
+                        device="cuda", seed: int = 0) -> dict:
+    """A policy and the PID baseline on the same Philox episodes (same seed and env ids, so identical
+    start states and targets): {"policy": ..., "pid": ...}, each with evaluate_episodes' keys plus
+    pos_errors / mean_pos_error, survival and reset_obs; "table" is the side-by-side text."""
+    device = torch.device(device)
+    policy, cfg_wrapper = load_policy(model, device)
+    wrapper = cfg_wrapper if wrapper == "auto" else wrapper
+    e = QuadVecEnv(num_episodes, env=env, wrapper=wrapper, device=device, seed=seed,
+                   max_episode_steps=max_episode_steps, auto_reset=False)
+    obs = e.reset().clone()
+    reset_obs = obs.clone()
+    act = _Actor(policy, num_episodes, device)
+    n = num_episodes
+    ret = torch.zeros(n, dtype=torch.float64, device=device)
+    perr = torch.zeros(n, dtype=torch.float64, device=device)
+    length = torch.zeros(n, dtype=torch.int32, device=device)
+    running = torch.ones(n, dtype=torch.bool, device=device)
+    terminated = torch.zeros(n, dtype=torch.bool, device=device)
+    target = e.current_target_info()[:, 0:3].clone()  # the target in hand before the step, as the PID metric reads it
+    for t in range(e.max_episode_steps):
+        a = act(obs)
+        _, rew, te, tr, info = e.step(a, obs=obs, info="full")
+        d = (info["state"][:, 0:3] - target).double().norm(dim=1)
+        target.copy_(info["target"])
+        ret += torch.where(running, rew.double(), 0.0)
+        perr += torch.where(running, d, 0.0)
+        length += running.int()
+        terminated |= running & te
+        running &= ~(te | tr)
+        if (t + 1) % 64 == 0 and not bool(running.any()):
+            break
+    l = length.cpu().numpy()
+    pe = perr.cpu().numpy() / np.maximum(l, 1)
+    te_np = terminated.cpu().numpy()
+    pol = _summary(ret.cpu().numpy(), l, te_np, pos_errors=pe, mean_pos_error=float(pe.mean()),
+                   survival=float((~te_np).mean()), reset_obs=reset_obs.cpu().numpy())
+    max_steps = e.max_episode_steps
+    e.close()
+    pid = evaluate_pid_episodes(gains, num_episodes, env=env, mode=mode, max_episode_steps=max_steps,
+                                device=device, seed=seed)
+    rows = [f"{'controller':>10} {'reward':>18} {'length':>16} {'survival':>9} {'pos error':>10}"]
+    for name, r in (("policy", pol), ("pid", pid)):
+        rows.append(f"{name:>10} {r['mean_reward']:9.2f} +/- {r['std_reward']:5.2f} {r['mean_length']:8.1f} +/- "
+                    f"{r['std_length']:5.1f} {100 * r['survival']:8.1f}% {r['mean_pos_error']:9.3f}m")
+    return {"policy": pol, "pid": pid, "table": "\n".join(rows)}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
-    ap.add_argument("--model", required=True)
+    ap.add_argument("--model", default=None, help="policy archive / state dict (not needed with --controller pid)")
+    ap.add_argument("--controller", choices=["policy", "pid", "both"], default="policy",
+                    help="pid: the cascaded PID baseline; both: policy and PID on the same episodes")
+    ap.add_argument("--gains", default=None, help="pid_gains.json-shaped file (default: the reference's gains)")
+    ap.add_argument("--env", default="hover", choices=["hover", "trajectory"])
     ap.add_argument("--mode", choices=["episodes", "trajectory"], default="trajectory")
     ap.add_argument("--trajectory", nargs="+", default=["eight"], choices=["eight", "circle", "square"])
     ap.add_argument("--spacing", nargs="+", type=float, default=[0.5])
@@ -196,6 +292,18 @@ def main(argv=None):
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--num-episodes", type=int, default=1024)
     a = ap.parse_args(argv)
+    if a.controller == "pid":
+        r = evaluate_pid_episodes(a.gains, a.num_episodes, env=a.env)
+        print(f"Episodes: {a.num_episodes}\nSurvival: {100 * r['survival']:.0f}%\n"
+              f"Mean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
+              f"Mean length: {r['mean_length']:.1f} +/- {r['std_length']:.1f}\nMean error: {r['mean_pos_error']:.3f}m")
+        return r
+    if a.model is None:
+        ap.error("--model is required unless --controller pid")
+    if a.controller == "both":
+        r = compare_controllers(a.model, a.gains, a.num_episodes, env=a.env)
+        print(r["table"])
+        return r
     if a.mode == "episodes":
         r = evaluate_episodes(a.model, a.num_episodes)
         print(f"Episodes: {a.num_episodes}\nMean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
