@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define QUADENV_ABI_VERSION 6
+#define QUADENV_ABI_VERSION 7
 
 enum { QUAD_OK = 0, QUAD_EINVAL = -1, QUAD_EHIP = -2, QUAD_ENOMEM = -3, QUAD_EMODEL = -4 };
 /* QUAD_ENV_BRAX_HOVER / QUAD_ENV_BRAX_TRAJ: the brax Env API siblings of the same path
@@ -330,6 +330,56 @@ typedef struct QuadPidRun {
   QuadPidMetrics metrics;
 } QuadPidRun;
 int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream);
+
+/* ---- The controller family: the reference's other three classical controllers beside the PID, as
+ * fused batched laws of the same shape. Each law is one compute() call of its reference class, quirks
+ * included. The two PID ids run quad_pid_act's law, so this family is a superset. */
+enum { QUAD_CTRL_PID_YAW = 0,   /* = QUAD_PID_YAW_FRAME */
+       QUAD_CTRL_PID_WORLD = 1, /* = QUAD_PID_WORLD_FRAME */
+       QUAD_CTRL_SE3 = 2,       /* se3_geometric_controller.py:247-426 */
+       QUAD_CTRL_SMC = 3,       /* smc_controller_world_frame.py:146-322 */
+       QUAD_CTRL_LQR = 4 };     /* lqr_controller_world_frame.py:139-289 */
+#define QUAD_CTRL_NSTATE 8 /* rows of the controller-state block */
+#define QUAD_CTRL_NDIAG 7  /* diag columns */
+/* 33 doubles: the shared gain set, then what only one law reads. */
+typedef struct QuadCtrlParams {
+  QuadPidGains base;
+  double lqr_k[3];                   /* LQR: K[0,0], K[0,1], K[0,2]; default [1 + sqrt 2, 1 + sqrt 2, 1] */
+  double yaw_stw_k1, yaw_stw_k2;     /* SMC super-twisting yaw loop: 1.2, 2.0 */
+  double yaw_stw_boundary;           /* 0.05 */
+  double yaw_deadband;               /* deg2rad(1) */
+  double yaw_v_int_max;              /* 2.0 */
+  double yaw_rate_max;               /* 3.0 */
+  double yaw_rate_lpf_alpha;         /* 0.2 */
+  double se3_reorthonormalize;       /* SE(3): non-zero (default 1) passes R_desired through np.linalg.qr's
+                                        Householder Q as the reference does; 0 uses [x_d y_d z_d] as built */
+} QuadCtrlParams;
+int quad_ctrl_default_params(QuadCtrlParams* p);
+
+/* quad_pid_act for any law. state: device float64 [8][n], field-major: the six integrators in
+ * quad_pid_act's order, then v_yaw and des_wz_prev (SMC; the other laws leave rows 6-7 untouched).
+ * diag (NULL to skip): float64 [n,7] = des_rate 3, des_att 3, |e_R| (SE(3); 0 otherwise). A row whose
+ * set_of entry is outside [0, n_sets) reads no parameter set: zero action, state left as it was. */
+int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of, int32_t law,
+                  const float* state12, const float* target9, int32_t n, double* state, float* actions,
+                  double* diag, void* stream);
+
+/* quad_pid_episode for any law: QuadPidRun's fields and rules, with the law, the parameter table and the
+ * [8][N] state block (NULL: start from zero, not stored). Bit-identical to quad_ctrl_act + quad_step per
+ * step on a handle with auto_reset = 0, and, with a PID law, to quad_pid_episode. */
+typedef struct QuadCtrlRun {
+  const QuadCtrlParams* params; /* device [n_sets] */
+  const int32_t* set_of;        /* device [N] or NULL (set 0) */
+  int32_t n_sets;               /* >= 1 */
+  int32_t law;                  /* QUAD_CTRL_* */
+  int32_t max_steps;            /* >= 1 */
+  int32_t trace_envs;           /* 0 .. N */
+  double* state;
+  float* trace_actions;
+  float* trace_state12;
+  QuadPidMetrics metrics;
+} QuadCtrlRun;
+int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream);
 
 /* PPO rollout support (row P of the scope table): generalized advantage estimation over a
  * time-major rollout, SB3 RolloutBuffer.compute_returns_and_advantage semantics.

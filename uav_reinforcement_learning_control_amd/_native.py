@@ -20,7 +20,7 @@ QUAD_ADV_GIVEN = 3        # ... : the sums are in QuadPPOBatch.adv_sums (quad_pp
 ADV_SUM_DOUBLES = 512     # QUAD_ADV_SUM_DOUBLES: one minibatch's block sums
 ENV_HOVER, ENV_TRAJ, ENV_BRAX_HOVER, ENV_BRAX_TRAJ = 0, 1, 2, 3
 WRAP_NONE, WRAP_CTBR, WRAP_RELPOS, WRAP_CTBR_RELPOS = 0, 1, 2, 3
-ABI_VERSION = 6
+ABI_VERSION = 7
 PID_YAW_FRAME, PID_WORLD_FRAME = 0, 1
 PID_RUNNING, PID_TERMINATED, PID_TRUNCATED, PID_INVALID = 0, 1, 2, 3
 
@@ -106,6 +106,24 @@ class QuadPidRun(C.Structure):
                 ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("metrics", QuadPidMetrics)]
 
 
+# the controller family: law ids (the PID ids equal the PID modes), QuadCtrlParams = QuadPidGains + extras
+CTRL_PID_YAW, CTRL_PID_WORLD, CTRL_SE3, CTRL_SMC, CTRL_LQR = 0, 1, 2, 3, 4
+CTRL_NSTATE, CTRL_NDIAG = 8, 7
+CTRL_EXTRA_FIELDS = ("lqr_k0", "lqr_k1", "lqr_k2", "yaw_stw_k1", "yaw_stw_k2", "yaw_stw_boundary", "yaw_deadband",
+                     "yaw_v_int_max", "yaw_rate_max", "yaw_rate_lpf_alpha", "se3_reorthonormalize")
+CTRL_PARAM_FIELDS = PID_GAIN_FIELDS + CTRL_EXTRA_FIELDS
+
+
+class QuadCtrlParams(C.Structure):
+    _fields_ = [("base", QuadPidGains), ("lqr_k", C.c_double * 3)] + [(n, C.c_double) for n in CTRL_EXTRA_FIELDS[3:]]
+
+
+class QuadCtrlRun(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("set_of", C.c_void_p), ("n_sets", C.c_int32), ("law", C.c_int32),
+                ("max_steps", C.c_int32), ("trace_envs", C.c_int32), ("state", C.c_void_p),
+                ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("metrics", QuadPidMetrics)]
+
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -134,7 +152,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_waypoints_begin", "quad_waypoints_update", "quad_ppo_workspace_bytes", "quad_ppo_grad",
            "quad_ppo_grad_form", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_permutation", "quad_adam_workspace_bytes",
            "quad_clip_adam",
-           "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info")
+           "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
+           "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode")
 
 
 class QuadRollout(C.Structure):
@@ -225,7 +244,11 @@ def _declare(L):
     L.quad_pid_act.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     L.quad_pid_episode.argtypes = [vp, C.POINTER(QuadPidRun), vp]
     L.quad_target_info.argtypes = [vp, vp, vp]
-    for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info"):
+    L.quad_ctrl_default_params.argtypes = [C.POINTER(QuadCtrlParams)]
+    L.quad_ctrl_act.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    L.quad_ctrl_episode.argtypes = [vp, C.POINTER(QuadCtrlRun), vp]
+    for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
+              "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode"):
         getattr(L, n).restype = C.c_int
     for n in ("quad_clip_adam", "quad_ppo_grad", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_default_cfg", "quad_create", "quad_seed", "quad_reset", "quad_step", "quad_step_range", "quad_observe", "quad_terminated", "quad_step_random",
               "quad_random_actions", "quad_get_state", "quad_set_state", "quad_gae",

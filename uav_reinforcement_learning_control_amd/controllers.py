@@ -9,7 +9,13 @@
                       it terminates, truncates or ``max_steps`` pass; per-env metrics as tensors.
   * ``pid_score``     ``compute_performance_score`` (auto_tune_pid.py:127-157), vectorised.
 
-``QuadVecEnv.pid_act`` / ``QuadVecEnv.pid_episode`` are these functions bound as methods.
+  * ``CtrlParams``    one parameter set of the controller family (the reference's SE(3), sliding-mode and
+                      LQR controllers beside the PID): ``PIDGains`` plus the LQR gain row, the seven
+                      super-twisting constants and ``se3_reorthonormalize``.
+  * ``ctrl_act`` / ``ctrl_episode``  ``pid_act`` / ``pid_episode`` for any law of ``LAWS``
+                      (``quad_ctrl_act`` / ``quad_ctrl_episode``).
+
+``QuadVecEnv.pid_act`` / ``pid_episode`` / ``ctrl_act`` / ``ctrl_episode`` are these functions bound as methods.
 """
 from __future__ import annotations
 
@@ -114,7 +120,7 @@ def gain_table(gains: GainsLike, device) -> torch.Tensor:
     elif isinstance(gains, np.ndarray):
         t = torch.from_numpy(np.asarray(gains, np.float64)).to(device)
     else:
-        t = torch.from_numpy(np.stack([g.vector() for g in gains])).to(device)
+        t = torch.from_numpy(np.stack([PIDGains.vector(g) for g in gains])).to(device)  # a CtrlParams' PID part
     t = t.reshape(-1, len(N.PID_GAIN_FIELDS)).contiguous()
     if t.shape[0] < 1:
         raise ValueError("at least one gain set is required")
@@ -219,5 +225,133 @@ def gains_from_vector(v) -> PIDGains:
     return PIDGains(**{f: float(x) for f, x in zip(N.PID_GAIN_FIELDS, v)})
 
 
+# ---------------------------------------------------------------------------------------------------
+# the controller family
+LAWS = {"pid": N.CTRL_PID_YAW, "pid_yaw": N.CTRL_PID_YAW, "yaw_frame": N.CTRL_PID_YAW,
+        "pid_world": N.CTRL_PID_WORLD, "world_frame": N.CTRL_PID_WORLD,
+        "se3": N.CTRL_SE3, "smc": N.CTRL_SMC, "lqr": N.CTRL_LQR}
+LAWS.update({v: v for v in list(LAWS.values())})
+
+# extra field -> (json section, key); every one optional in a file
+_JSON_EXTRA = (("lqr_k0", "lqr", "k0"), ("lqr_k1", "lqr", "k1"), ("lqr_k2", "lqr", "k2"),
+               ("yaw_stw_k1", "smc_yaw", "stw_k1"), ("yaw_stw_k2", "smc_yaw", "stw_k2"),
+               ("yaw_stw_boundary", "smc_yaw", "stw_boundary"), ("yaw_deadband", "smc_yaw", "deadband"),
+               ("yaw_v_int_max", "smc_yaw", "v_int_max"), ("yaw_rate_max", "smc_yaw", "rate_max"),
+               ("yaw_rate_lpf_alpha", "smc_yaw", "rate_lpf_alpha"),
+               ("se3_reorthonormalize", "se3", "reorthonormalize"))
+
+
+@dataclass
+class CtrlParams(PIDGains):
+    """QuadCtrlParams. Defaults: PIDGains', control.lqr's gain row of lqr_controller_world_frame.py:129 in
+    closed form, smc_controller_world_frame.py:124-130, and the reference's QR step switched on."""
+    lqr_k0: float = 1.0 + 2.0 ** 0.5
+    lqr_k1: float = 1.0 + 2.0 ** 0.5
+    lqr_k2: float = 1.0
+    yaw_stw_k1: float = 1.2
+    yaw_stw_k2: float = 2.0
+    yaw_stw_boundary: float = 0.05
+    yaw_deadband: float = float(np.deg2rad(1.0))
+    yaw_v_int_max: float = 2.0
+    yaw_rate_max: float = 3.0
+    yaw_rate_lpf_alpha: float = 0.2
+    se3_reorthonormalize: float = 1.0
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "CtrlParams":
+        """A pid_gains.json-shaped dict; the sections "lqr", "smc_yaw" and "se3" are optional."""
+        g = cls()
+        for f, sec, key in _JSON + _JSON_EXTRA:
+            if sec in d and key in d[sec]:
+                setattr(g, f, float(d[sec][key]))
+        return g
+
+    def to_dict(self, notes: Optional[dict] = None) -> dict:
+        d = super().to_dict(notes)
+        for f, sec, key in _JSON_EXTRA:
+            d.setdefault(sec, {})[key] = float(getattr(self, f))
+        return d
+
+    def vector(self) -> np.ndarray:
+        return np.array([getattr(self, f) for f in N.CTRL_PARAM_FIELDS], np.float64)
+
+
+assert tuple(f.name for f in fields(CtrlParams)) == N.CTRL_PARAM_FIELDS
+assert C.sizeof(N.QuadCtrlParams) == 8 * len(N.CTRL_PARAM_FIELDS)
+
+ParamsLike = Union[None, PIDGains, Sequence[PIDGains], np.ndarray, torch.Tensor]
+
+
+def params_from_vector(v) -> CtrlParams:
+    v = np.asarray(v, np.float64).reshape(-1)
+    return CtrlParams(**{f: float(x) for f, x in zip(N.CTRL_PARAM_FIELDS, v)})
+
+
+def _as_ctrl(g: PIDGains) -> CtrlParams:
+    """A plain PIDGains takes the default extras."""
+    return g if isinstance(g, CtrlParams) else CtrlParams(**{f: getattr(g, f) for f in N.PID_GAIN_FIELDS})
+
+
+def param_table(params: ParamsLike, device) -> torch.Tensor:
+    """[n_sets, 33] float64 on `device`: rows are QuadCtrlParams structs. Accepts one CtrlParams (or PIDGains),
+    a sequence of them, or an array / tensor already in that layout."""
+    if params is None:
+        params = CtrlParams()
+    if isinstance(params, PIDGains):
+        params = [params]
+    if isinstance(params, torch.Tensor):
+        t = params.to(device=device, dtype=torch.float64)
+    elif isinstance(params, np.ndarray):
+        t = torch.from_numpy(np.asarray(params, np.float64)).to(device)
+    else:
+        t = torch.from_numpy(np.stack([_as_ctrl(g).vector() for g in params])).to(device)
+    t = t.reshape(-1, len(N.CTRL_PARAM_FIELDS)).contiguous()
+    if t.shape[0] < 1:
+        raise ValueError("at least one parameter set is required")
+    return t
+
+
+def ctrl_act(env, state12: torch.Tensor, target9: torch.Tensor, state: torch.Tensor, params: ParamsLike = None,
+             set_of=None, law="se3", out: Optional[torch.Tensor] = None, diag: Optional[torch.Tensor] = None):
+    """One compute() of the law's reference class per row. As pid_act, with `state` float64 [8,n] (the six
+    integrators, v_yaw, des_wz_prev; zero it at an episode start) and diag [n,7] (des_rate 3, des_att 3, |e_R|)."""
+    n = int(state12.shape[0])
+    env._check(state12, (n, 12), torch.float32)
+    env._check(target9, (n, 9), torch.float32)
+    env._check(state, (N.CTRL_NSTATE, n), torch.float64)
+    out = torch.empty(n, 4, dtype=torch.float32, device=env.device) if out is None else out
+    env._check(out, (n, 4), torch.float32)
+    if diag is not None:
+        env._check(diag, (n, N.CTRL_NDIAG), torch.float64)
+    tab = param_table(params, env.device)
+    so = _set_of(set_of, n, env.device)
+    N.check(N.lib().quad_ctrl_act(env._h, _ptr(tab), tab.shape[0], _ptr(so), LAWS[law], _ptr(state12), _ptr(target9),
+                                  n, _ptr(state), _ptr(out), _ptr(diag), env._stream()), "quad_ctrl_act")
+    return out
+
+
+def ctrl_episode(env, params: ParamsLike = None, set_of=None, law="se3", max_steps: Optional[int] = None,
+                 trace_envs: int = 0, state: Optional[torch.Tensor] = None) -> dict:
+    """pid_episode for any law of LAWS: the same metrics, traces and freezing rules, one launch."""
+    n, dev = env.num_envs, env.device
+    T = int(env.max_episode_steps if max_steps is None else max_steps)
+    M = int(trace_envs)
+    tab = param_table(params, dev)
+    so = _set_of(set_of, n, dev)
+    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+    if M > 0 and T > 0:
+        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
+        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
+    if state is not None:
+        env._check(state, (N.CTRL_NSTATE, n), torch.float64)
+    run = N.QuadCtrlRun(params=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
+                        law=LAWS[law], max_steps=T, trace_envs=M, state=None if state is None else state.data_ptr(),
+                        trace_actions=res["actions"].data_ptr() if "actions" in res else None,
+                        trace_state12=res["state12"].data_ptr() if "state12" in res else None,
+                        metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
+    N.check(N.lib().quad_ctrl_episode(env._h, C.byref(run), env._stream()), "quad_ctrl_episode")
+    return res
+
+
 __all__ = ["PIDGains", "gain_table", "pid_act", "pid_episode", "pid_score", "target_info", "gains_from_vector",
-           "MODES", "STATUS"]
+           "MODES", "STATUS", "CtrlParams", "LAWS", "param_table", "params_from_vector", "ctrl_act", "ctrl_episode"]

@@ -23,6 +23,7 @@
 //   k_random_actions     action_space.sample() stand-in (Philox), config 2
 //   k_gae                SB3 GAE(lambda) reverse scan, one thread per env
 // The cascaded PID baseline's kernels (k_pid_act, k_pid_episode, k_target_info) are in pid.hip.
+// The controller family's kernels (k_ctrl_act, k_ctrl_episode) are in ctrl.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -37,6 +38,7 @@
 #include "dispatch.h"
 #include "env_tiles.h"
 #include "kconsts_default.h"
+#include "ctrl.h"
 #include "pid.h"
 #include "rollout.h"
 
@@ -1326,6 +1328,64 @@ int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream) {
   if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
   HIP_TRY(launch_pid_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
                              static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- controller family (kernels: ctrl.hip); quad_pid_*'s rules with a law id in place of the mode
+int quad_ctrl_default_params(QuadCtrlParams* p) {
+  if (!p) return fail(QUAD_EINVAL, "params is NULL");
+  ctrl_default_params_fill(p);
+  return QUAD_OK;
+}
+
+static int check_ctrl(const QuadHandle* h, const char* who, const QuadCtrlParams* params, int32_t n_sets, int32_t law) {
+  const std::string w(who);
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
+  if (h->cfg.wrapper != QUAD_WRAP_NONE)
+    return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
+  if (law < QUAD_CTRL_PID_YAW || law > QUAD_CTRL_LQR) return fail(QUAD_EINVAL, w + ": unknown law");
+  if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
+  if (!params) return fail(QUAD_EINVAL, w + ": params is NULL");
+  return QUAD_OK;
+}
+
+int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of, int32_t law,
+                  const float* state12, const float* target9, int32_t n, double* state, float* actions,
+                  double* diag, void* stream) {
+  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
+  if (int rc = check_ctrl(h, "quad_ctrl_act", params, n_sets, law)) return rc;
+  if (!state12 || !target9 || !state || !actions)
+    return fail(QUAD_EINVAL, "quad_ctrl_act: state12, target9, state and actions are required");
+  if (n < 1) return fail(QUAD_EINVAL, "quad_ctrl_act: n must be >= 1");
+  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, "quad_ctrl_act: actions must be 16-byte aligned");
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_ctrl_act(make_pid_plant(h->cfg), params, n_sets, set_of, law, state12, target9, n, state, actions, diag,
+                          static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream) {
+  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
+  if (int rc = check_ctrl(h, "quad_ctrl_episode", r->params, r->n_sets, r->law)) return rc;
+  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_ctrl_episode: max_steps must be >= 1");
+  const QuadPidMetrics& m = r->metrics;
+  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
+      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
+      !m.yaw_rate_delta_sum)
+    return fail(QUAD_EINVAL, "quad_ctrl_episode: every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_ctrl_episode: trace_envs must be in [0, N]");
+  if ((r->trace_actions || r->trace_state12) && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
+      return fail(QUAD_EINVAL, "quad_ctrl_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
+      return fail(QUAD_EINVAL, "quad_ctrl_episode: traces must be 16-byte aligned");
+  }
+  DeviceGuard g(h->device);
+  QuadCtrlRun run = *r;
+  if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
+  HIP_TRY(launch_ctrl_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
+                              static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

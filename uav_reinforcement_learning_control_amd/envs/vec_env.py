@@ -250,6 +250,16 @@ class QuadVecEnv:
         from .. import controllers
         return controllers.pid_episode(self, gains, set_of, mode, max_steps, trace_envs, integ)
 
+    # the controller family (SE(3), sliding mode, LQR and the PID again): the same two calls with a law name
+    def ctrl_act(self, state12, target9, state, params=None, set_of=None, law="se3", out=None, diag=None):
+        from .. import controllers
+        return controllers.ctrl_act(self, state12, target9, state, params, set_of, law, out, diag)
+
+    def ctrl_episode(self, params=None, set_of=None, law="se3", max_steps: Optional[int] = None,
+                     trace_envs: int = 0, state=None) -> dict:
+        from .. import controllers
+        return controllers.ctrl_episode(self, params, set_of, law, max_steps, trace_envs, state)
+
     # ------------------------------------------------------------------------------------
     _FIELDS = (("qpos", 11, np.float32), ("qvel", 10, np.float32), ("voltage", 1, np.float32),
                ("target", 3, np.float32), ("rate_int", 3, np.float32),

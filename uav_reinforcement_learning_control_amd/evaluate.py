@@ -14,6 +14,8 @@ waypoint lap (:440-612). Here N evaluations run at once on the GPU:
   * ``evaluate_pid_episodes`` -- the same N episodes flown by the cascaded PID baseline
     (``controllers.py``; one fused launch), and ``compare_controllers`` -- a policy and the PID on the
     same Philox episodes, side by side (the reference's controller comparison, batched).
+  * ``evaluate_ctrl_episodes`` / ``compare_pair`` -- the same for the SE(3), sliding-mode and LQR
+    controllers: any two of pid / se3 / smc / lqr / model on the same episodes (``--compare A B``).
 
 Actions are ``model.predict(obs, deterministic=True)``: the Gaussian mean clipped to the action
 box (SB3 clips Box actions in predict), computed by the MFMA policy kernel for 12-D obs and by the
@@ -235,12 +237,29 @@ def compare_controllers(model, gains=None, num_episodes: int = 256, wrapper: Opt
     start states and targets): {"policy": ..., "pid": ...}, each with evaluate_episodes' keys plus
     pos_errors / mean_pos_error, survival and reset_obs; "table" is the side-by-side text."""
     device = torch.device(device)
+    pol, max_steps = _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, device, seed)
+    pid = evaluate_pid_episodes(gains, num_episodes, env=env, mode=mode, max_episode_steps=max_steps,
+                                device=device, seed=seed)
+    return {"policy": pol, "pid": pid, "table": _table((("policy", pol), ("pid", pid)))}
+
+
+def _table(rows_in) -> str:
+    rows = [f"{'controller':>10} {'reward':>18} {'length':>16} {'survival':>9} {'pos error':>10}"]
+    for name, r in rows_in:
+        rows.append(f"{name:>10} {r['mean_reward']:9.2f} +/- {r['std_reward']:5.2f} {r['mean_length']:8.1f} +/- "
+                    f"{r['std_length']:5.1f} {100 * r['survival']:8.1f}% {r['mean_pos_error']:9.3f}m")
+    return "\n".join(rows)
+
+
+def _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, device, seed) -> tuple:
+    """The policy's episodes with the PID metric's position error: (summary, the env's time limit)."""
     policy, cfg_wrapper = load_policy(model, device)
     wrapper = cfg_wrapper if wrapper == "auto" else wrapper
     e = QuadVecEnv(num_episodes, env=env, wrapper=wrapper, device=device, seed=seed,
                    max_episode_steps=max_episode_steps, auto_reset=False)
     obs = e.reset().clone()
     reset_obs = obs.clone()
+    digests = episode_digests(e)
     act = _Actor(policy, num_episodes, device)
     n = num_episodes
     ret = torch.zeros(n, dtype=torch.float64, device=device)
@@ -265,23 +284,91 @@ def compare_controllers(model, gains=None, num_episodes: int = 256, wrapper: Opt
     pe = perr.cpu().numpy() / np.maximum(l, 1)
     te_np = terminated.cpu().numpy()
     pol = _summary(ret.cpu().numpy(), l, te_np, pos_errors=pe, mean_pos_error=float(pe.mean()),
-                   survival=float((~te_np).mean()), reset_obs=reset_obs.cpu().numpy())
+                   survival=float((~te_np).mean()), reset_obs=reset_obs.cpu().numpy(), digests=digests)
     max_steps = e.max_episode_steps
     e.close()
-    pid = evaluate_pid_episodes(gains, num_episodes, env=env, mode=mode, max_episode_steps=max_steps,
-                                device=device, seed=seed)
-    rows = [f"{'controller':>10} {'reward':>18} {'length':>16} {'survival':>9} {'pos error':>10}"]
-    for name, r in (("policy", pol), ("pid", pid)):
-        rows.append(f"{name:>10} {r['mean_reward']:9.2f} +/- {r['std_reward']:5.2f} {r['mean_length']:8.1f} +/- "
-                    f"{r['std_length']:5.1f} {100 * r['survival']:8.1f}% {r['mean_pos_error']:9.3f}m")
-    return {"policy": pol, "pid": pid, "table": "\n".join(rows)}
+    return pol, max_steps
+
+
+CONTROLLERS = ("pid", "se3", "smc", "lqr")
+
+
+@torch.no_grad()
+def evaluate_ctrl_episodes(law: str, params=None, num_episodes: int = 1024, env: str = "hover",
+                           max_episode_steps: Optional[int] = None, device="cuda", seed: int = 0,
+                           env_id_base: int = 0) -> dict:
+    """evaluate_pid_episodes for any law of the controller family ("pid": the PID the reference flies on
+    `env`; "se3", "smc", "lqr"), one fused launch. `params`: a CtrlParams / PIDGains, a pid_gains.json-shaped
+    path, or None (the reference's values, SE(3)'s QR step included: see DESIGN 15 before flying it on hover)."""
+    from .controllers import CtrlParams, ctrl_episode
+    device = torch.device(device)
+    if isinstance(params, str):
+        params = CtrlParams.from_json(params)
+    law = _pid_mode(env, None) if law == "pid" else law
+    e = QuadVecEnv(num_episodes, env=env, wrapper=None, device=device, seed=seed, env_id_base=env_id_base,
+                   max_episode_steps=max_episode_steps, auto_reset=False)
+    reset_obs = e.reset().clone()
+    digests = episode_digests(e)
+    m = ctrl_episode(e, params, law=law)
+    torch.cuda.synchronize(device)
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    e.close()
+    pe = m["pos_err_sum"] / np.maximum(m["steps"], 1)
+    return _summary(m["total_reward"], m["steps"], m["status"] == N.PID_TERMINATED, pos_errors=pe,
+                    mean_pos_error=float(pe.mean()), survival=float((m["status"] == N.PID_TRUNCATED).mean()),
+                    reset_obs=reset_obs.cpu().numpy(), metrics=m, digests=digests)
+
+
+def episode_digests(e: QuadVecEnv) -> list:
+    """One digest per env of its state right after reset() (qpos, qvel, target: whatever wrapper shapes the
+    observation): two runs with equal digests flew the same resets."""
+    import hashlib
+    st = e.get_state()
+    rows = np.concatenate([np.ascontiguousarray(st[k], np.float32).reshape(e.num_envs, -1)
+                           for k in ("qpos", "qvel", "target")], axis=1)
+    return [hashlib.sha256(row.tobytes()).hexdigest()[:16] for row in rows]
+
+
+@torch.no_grad()
+def compare_pair(a: str, b: str, model=None, params=None, num_episodes: int = 256, env: str = "hover",
+                 wrapper: Optional[str] = "auto", max_episode_steps: Optional[int] = None, device="cuda",
+                 seed: int = 0, survive_steps: int = 512) -> dict:
+    """The reference's compare_controllers.py, batched: controllers `a` and `b` (any of CONTROLLERS, or
+    "model" for the policy `model`) on the same Philox episodes. {a: ..., b: ..., "table"}; each entry has
+    evaluate_pid_episodes' keys plus "digests" and "survival_rate" (episodes of at least `survive_steps`
+    steps, compare_controllers.py's measure); the table prints its four metrics."""
+    device = torch.device(device)
+    out = {}
+    for name in (a, b):
+        if name == "model":
+            if model is None:
+                raise ValueError("comparing against \"model\" needs a policy")
+            r, _ = _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, device, seed)
+        elif name in CONTROLLERS:
+            r = evaluate_ctrl_episodes(name, params, num_episodes, env, max_episode_steps, device, seed)
+        else:
+            raise ValueError(f"unknown controller {name!r}: one of {CONTROLLERS + ('model',)}")
+        r["survival_rate"] = float((r["lengths"] >= survive_steps).mean())
+        out[name] = r
+    rows = [f"{'controller':>10} {'mean reward':>12} {'mean length':>12} {'pos error':>10} {'survival':>9}"]
+    for name in dict.fromkeys((a, b)):
+        r = out[name]
+        rows.append(f"{name:>10} {r['mean_reward']:12.2f} {r['mean_length']:12.1f} {r['mean_pos_error']:9.3f}m "
+                    f"{100 * r['survival_rate']:8.1f}%")
+    out["table"] = "\n".join(rows)
+    return out
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--model", default=None, help="policy archive / state dict (not needed with --controller pid)")
-    ap.add_argument("--controller", choices=["policy", "pid", "both"], default="policy",
-                    help="pid: the cascaded PID baseline; both: policy and PID on the same episodes")
+    ap.add_argument("--controller", choices=["policy", "pid", "both", "se3", "smc", "lqr"], default="policy",
+                    help="pid: the cascaded PID baseline; both: policy and PID on the same episodes; "
+                         "se3 / smc / lqr: the reference's other classical controllers")
+    ap.add_argument("--compare", nargs=2, metavar=("A", "B"), default=None,
+                    help="fly two controllers (pid, se3, smc, lqr or model) on the same episodes")
+    ap.add_argument("--se3-reorthonormalize", type=int, choices=[0, 1], default=1,
+                    help="0: skip the SE(3) controller's np.linalg.qr step (as written it does not hover)")
     ap.add_argument("--gains", default=None, help="pid_gains.json-shaped file (default: the reference's gains)")
     ap.add_argument("--env", default="hover", choices=["hover", "trajectory"])
     ap.add_argument("--mode", choices=["episodes", "trajectory"], default="trajectory")
@@ -292,6 +379,21 @@ def main(argv=None):
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--num-episodes", type=int, default=1024)
     a = ap.parse_args(argv)
+    if a.compare or a.controller in ("se3", "smc", "lqr"):
+        from .controllers import CtrlParams
+        params = CtrlParams.from_json(a.gains) if a.gains else CtrlParams()
+        params.se3_reorthonormalize = float(a.se3_reorthonormalize)
+        if a.compare:
+            if "model" in a.compare and a.model is None:
+                ap.error("--compare with model needs --model")
+            r = compare_pair(a.compare[0], a.compare[1], a.model, params, a.num_episodes, env=a.env)
+            print(r["table"])
+            return r
+        r = evaluate_ctrl_episodes(a.controller, params, a.num_episodes, env=a.env)
+        print(f"Episodes: {a.num_episodes}\nSurvival: {100 * r['survival']:.0f}%\n"
+              f"Mean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
+              f"Mean length: {r['mean_length']:.1f} +/- {r['std_length']:.1f}\nMean error: {r['mean_pos_error']:.3f}m")
+        return r
     if a.controller == "pid":
         r = evaluate_pid_episodes(a.gains, a.num_episodes, env=a.env)
         print(f"Episodes: {a.num_episodes}\nSurvival: {100 * r['survival']:.0f}%\n"
