@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define QUADENV_ABI_VERSION 7
+#define QUADENV_ABI_VERSION 8
 
 enum { QUAD_OK = 0, QUAD_EINVAL = -1, QUAD_EHIP = -2, QUAD_ENOMEM = -3, QUAD_EMODEL = -4 };
 /* QUAD_ENV_BRAX_HOVER / QUAD_ENV_BRAX_TRAJ: the brax Env API siblings of the same path
@@ -380,6 +380,52 @@ typedef struct QuadCtrlRun {
   QuadPidMetrics metrics;
 } QuadCtrlRun;
 int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream);
+
+/* ---- The deployed observation path and the policy's fused episode. The reference deploys the
+ * policy through ros2_ws policy_node.py, which does not feed it the env's observation: the linear velocity
+ * is state_estimator.VelocityEstimator's -- a first-order low-pass (velocity_alpha, default 0.8) on finite
+ * differences of the mocap position -- and observation_builder.build_observation clips the normalised
+ * vector to [-1, 1]. QuadVelEst is one estimator per env. */
+enum { QUAD_OBS_ENV = 0, QUAD_OBS_DEPLOYED = 1 };
+#define QUAD_EST_NSTATE 8 /* rows of the estimator block: prev_pos 3, prev_time, velocity 3, has_prev (0 / 1) */
+typedef struct QuadVelEst {
+  const double* alpha;  /* device [N] or NULL (alpha_all for every env) */
+  double alpha_all;     /* policy_node.py default 0.8 */
+  double max_dt;        /* 0.1 */
+  double* state;        /* device float64 [8][N] field-major in/out; NULL: start empty, not stored */
+} QuadVelEst;
+
+/* One VelocityEstimator.update(position, timestamp) and one build_observation per row: state12 [n,12]
+ * (position, attitude, velocity, body rates; the velocity columns are NOT read), target3 [n,3]; writes
+ * obs [n,12] and, unless NULL, vel_est [n,3] (the estimate rounded to float32, as obs holds it before
+ * normalisation). The observation bounds are the handle's. est->state is required (zero it to start). */
+int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream);
+
+/* The deterministic policy's whole episodes in ONE launch from the envs' current state: per step the actor
+ * (MFMA), clip(mean, -1, 1), the env step, QuadPidRun's metrics, the estimator update and its error. Every
+ * env runs until its first terminated / truncated step or max_steps and is then frozen, never reset (the
+ * handle's auto_reset setting is not consulted). The estimator sees the position in hand before the first
+ * action at timestamp step_count * est_dt, then each step's position at the new step count.
+ * vel_err_sq[i] = sum over env i's steps of |v_est - state12[6:9]|^2 after the step (float64).
+ * Traces, time-major [max_steps, trace_envs, .] of the first trace_envs envs, rows past an env's last step
+ * untouched: actions (the clipped action, 16-byte aligned), obs (the observation that action was taken
+ * from), state12 and vel_est (after the step). Requires env_kind HOVER or TRAJ, wrapper NONE or CTBR.
+ * Contract: bit-identical, for every env up to its last step, to this loop on a second handle:
+ * quad_observe, then quad_deploy_obs at the reset step count, once; per step quad_policy_act with
+ * deterministic = 1, quad_step, and quad_deploy_obs on the step's state12 (target3 = the env's target)
+ * at the new step count -- the act reading quad_observe's / quad_step's obs in QUAD_OBS_ENV and
+ * quad_deploy_obs's in QUAD_OBS_DEPLOYED. */
+typedef struct QuadPolicyRun {
+  int32_t obs_mode;     /* QUAD_OBS_ENV: the policy sees the env's observation, the estimator runs beside it;
+                           QUAD_OBS_DEPLOYED: the policy sees deploy_obs */
+  int32_t max_steps, trace_envs;
+  QuadVelEst est; double est_dt;            /* timestamp of step count k = k * est_dt */
+  float *trace_actions, *trace_state12, *trace_obs, *trace_vel_est;  /* time-major, first trace_envs envs, NULL to skip */
+  QuadPidMetrics metrics;                   /* all required, QuadPidRun's rules and status codes */
+  double* vel_err_sq;                       /* [N] or NULL */
+} QuadPolicyRun;
+int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream);
 
 /* PPO rollout support (row P of the scope table): generalized advantage estimation over a
  * time-major rollout, SB3 RolloutBuffer.compute_returns_and_advantage semantics.

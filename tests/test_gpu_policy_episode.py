@@ -1,0 +1,516 @@
+"""quad_policy_episode (the fused policy episode) and quad_deploy_obs (the deployed observation law) on the GPU.
+
+The fused launch must equal, bit for bit and for every env up to its last step, the per-step loop of the
+public calls on a second handle: quad_observe + quad_deploy_obs once, then per step quad_policy_act
+(deterministic) -> quad_step -> quad_deploy_obs. The loop side records everything per step (get_state
+included); the metrics are re-accumulated from its records in pid_acc_step's operation order (float64, IEEE
+operations only, so numpy gives the kernel's bits).
+
+Early terminations are injected by set_state (positions just inside a bound, moving outward) in three
+patterns: single lanes of a tile, one whole 32-env tile of a wave at step 1 beside a live sibling tile
+(envs 64..95), and one whole 64-env wave beside the block's other waves (envs 128..191). Which of them is "a
+tile" or "a wave" depends on the launch shape, so the cases pin k_rollout's shape (256-env blocks of two-tile
+waves), the 64-env shapes, and the default choice. Time-limit cases (limit 7 inside 12 steps) end every env
+terminated or truncated; the default-limit cases leave envs running.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import deploy_ref
+from test_gpu_rollout import _policy
+from uav_reinforcement_learning_control_amd import _native as N
+from uav_reinforcement_learning_control_amd import evaluate as EV
+from uav_reinforcement_learning_control_amd.envs import QuadVecEnv
+from uav_reinforcement_learning_control_amd.ppo.fused import FusedPolicy, episode_supported
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "golden_deploy.npz")
+STATE_TOL = 1e-12
+ALPHAS3 = np.array([0.0, 0.5, 0.8])
+
+
+@pytest.fixture(scope="module")
+def fp():
+    f = FusedPolicy(_policy())
+    f.pack()
+    return f
+
+
+def _hover_policy():
+    """A linear hover law under RateControlWrapper written into the 12-128-128-4 actor (the small-weight
+    _policy saturates the thrust and leaves the box within a dozen steps): the first twelve hidden units of each
+    layer carry obs + 2 (> 0 for every live observation, so the ReLUs pass it), the head applies
+      thrust = m (g + 6 e_z - 4 v_z),  pitch rate = 6 ((2 e_x - 2.5 v_x) / g - pitch),
+      roll rate = 6 (-(2 e_y - 2.5 v_y) / g - roll),  yaw rate = -2 yaw
+    on the denormalised observation (the cascade of the reference's PID in linear form, its sign conventions)."""
+    pol = _policy()
+    A = np.zeros((4, 12))
+    g, m, rmax = 9.81, 0.2227, 2.0 * np.pi
+    A[0, 2], A[0, 8] = (m / 26.0) * 6.0 * 2.0, -(m / 26.0) * 4.0 * 10.0
+    A[2, 0], A[2, 6], A[2, 4] = 6.0 * 2.0 * 4.0 / g / rmax, -6.0 * 2.5 * 10.0 / g / rmax, -6.0 * np.pi / rmax
+    A[1, 1], A[1, 7], A[1, 3] = -6.0 * 2.0 * 4.0 / g / rmax, 6.0 * 2.5 * 10.0 / g / rmax, -6.0 * np.pi / rmax
+    A[3, 5] = -2.0 * np.pi / rmax
+    b = np.array([m * g / 26.0 - 1.0, 0.0, 0.0, 0.0]) - 2.0 * A.sum(axis=1)
+    ex = pol.mlp_extractor
+    with torch.no_grad():
+        for lin in (ex.policy_net[0], ex.policy_net[2], pol.action_net):
+            lin.weight.zero_(); lin.bias.zero_()
+        for i in range(12):
+            ex.policy_net[0].weight[i, i] = 1.0
+            ex.policy_net[0].bias[i] = 2.0
+            ex.policy_net[2].weight[i, i] = 1.0
+        pol.action_net.weight[:, 0:12] = torch.from_numpy(A).float()
+        pol.action_net.bias.copy_(torch.from_numpy(b).float())
+    return pol
+
+
+def _np(d):
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [130, 514])
+def test_deploy_obs_matches_the_fixture_and_the_ref(n):
+    """Rows = fixture estimator sequences laid side by side (row i flies sequence i % runs with alpha
+    ALPHAS3[(5 i) % 3]), stepped call by call; then the fixture's builder calls in one launch."""
+    fx = dict(np.load(GOLDEN))
+    run = int(fx["est_run"])
+    runs = len(fx["est_t"]) // run
+    env = QuadVecEnv(n, device=DEV, auto_reset=False)
+    seq = np.arange(n) % runs
+    alpha = ALPHAS3[(np.arange(n) * 5) % 3]
+    refs = [deploy_ref.VelEstRef(a, 0.1) for a in alpha]
+    al = torch.from_numpy(alpha).to(DEV)
+    st = torch.zeros(8, n, dtype=torch.float64, device=DEV)
+    tg = torch.zeros(n, 3, device=DEV)
+    vel32 = torch.zeros(n, 3, device=DEV)
+    # every row of one call shares the timestamp: the clock of run 1 (a repeated stamp) for the first 20 calls,
+    # then, a second later (a gap), ten stamps of run 2 around its gap above max_dt
+    clock = np.concatenate([fx["est_t"][run:run + 20] - fx["est_t"][run], fx["est_t"][2 * run:3 * run][20:30]
+                            - fx["est_t"][2 * run + 20] + 1.0])
+    branches = {"first": 0, "bad_dt": 0, "filter": 0}
+    for k, t in enumerate(clock):
+        s12 = np.zeros((n, 12), np.float32)
+        s12[:, 0:3] = fx["est_pos"][seq * run + k]
+        s12[:, 3:6] = 0.1
+        s12[:, 6:9] = 55.0  # not read
+        obs = env.deploy_obs(torch.from_numpy(s12).to(DEV), tg, float(t), st, alpha=al, vel_est=vel32)
+        got, gs, gv = obs.cpu().numpy(), st.cpu().numpy(), vel32.cpu().numpy()
+        for i in range(n):
+            v = refs[i].update(s12[i, 0:3].astype(np.float64), float(t))
+            assert np.abs(gs[:, i] - refs[i].state()).max() <= STATE_TOL, (k, i)
+            want = deploy_ref.build_obs(s12[i, 0:3], np.zeros(3), s12[i, 3:6], v, s12[i, 9:12])
+            assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32)), (k, i)
+            assert np.array_equal(gv[i], refs[i].vel.astype(np.float32))
+    for r in refs:
+        for b in branches:
+            branches[b] += r.branches[b]
+    assert branches["first"] == n and branches["bad_dt"] >= 3 * n and branches["filter"] >= 24 * n
+    # the fixture's builder calls (600 rows: one launch, three blocks), velocity handed in through the state block
+    m = len(fx["obs_out"])
+    s = np.zeros((m, 12), np.float32)
+    s[:, 0:3], s[:, 3:6], s[:, 9:12] = fx["obs_drone_pos"], fx["obs_attitude"], fx["obs_angular_vel"]
+    big = QuadVecEnv(m, device=DEV, auto_reset=False)
+    # alpha = 1 keeps the stored velocity: v = 1 * v + 0 * raw (raw = 0: same position, dt = 0.01)
+    blk = np.zeros((8, m))
+    blk[0:3], blk[3], blk[4:7], blk[7] = s[:, 0:3].T, 1.0, fx["obs_linear_vel"].T, 1.0
+    stb = torch.from_numpy(blk).to(DEV)
+    obs = big.deploy_obs(torch.from_numpy(s).to(DEV), torch.from_numpy(fx["obs_target"]).to(DEV), 1.01, stb, alpha_all=1.0)
+    assert np.array_equal(obs.cpu().numpy().view(np.uint32), fx["obs_out"].view(np.uint32))
+    assert np.array_equal(stb.cpu().numpy()[4:7], fx["obs_linear_vel"].T)
+    env.close(); big.close()
+
+
+# ---------------------------------------------------------------------------------------------
+def _inject(env, kind, n):
+    """Envs just inside the x / y position bound, moving outward at 1.5 m/s (0.015 m per step)."""
+    st = env.get_state()
+    bound = 3.0 if kind == "trajectory" else 2.0
+
+    def put(i, steps, ax=0):
+        st["qpos"][i, ax] = bound - 0.015 * steps + 0.0075
+        st["qvel"][i, ax] = 1.5
+        st["qpos"][i, 3:7] = (1, 0, 0, 0)
+
+    singles = [(3, 1), (17, 3), (32, 5)] + ([(40, 2), (129, 4)] if n >= 130 else []) + \
+              ([(300, 3), (513, 2)] if n >= 514 else [])
+    for j, (i, k) in enumerate(singles):
+        put(i, k, j % 2)
+    if n >= 130:
+        for i in range(64, 96):  # one whole tile at step 1; its sibling tile 96..127 flies on
+            put(i, 1)
+    if n >= 514:
+        for i in range(128, 192):  # one whole wave at step 2; the block's other waves fly on
+            put(i, 2, 1)
+    env.set_state(qpos=st["qpos"], qvel=st["qvel"])
+    return len({i for i, _ in singles} | set(range(64, 96 if n >= 130 else 64)) | set(range(128, 192 if n >= 514 else 128)))
+
+
+def _loop(fp, env, mode, T, alpha):
+    """The per-step loop of the public calls, every env stepped T times; everything recorded per step."""
+    n = env.num_envs
+    obs, s12 = env.observe(state=True)
+    obs, s12 = obs.clone(), s12.clone()
+    tgt3 = torch.from_numpy(np.ascontiguousarray(env.get_state()["target"], np.float32)).to(DEV)
+    est = torch.zeros(8, n, dtype=torch.float64, device=DEV)
+    dob = torch.zeros(n, 12, device=DEV)
+    v32 = torch.zeros(n, 3, device=DEV)
+    act = torch.zeros(n, 4, device=DEV)
+    env.deploy_obs(s12, tgt3, 0 * env.dt, est, alpha=alpha, out=dob, vel_est=v32)
+    tbefore = env.current_target_info()[:, 0:3].clone()
+    rec = {k: [] for k in ("actions", "obs", "state12", "vel_est", "est", "reward", "terminated", "truncated", "tbefore")}
+    states = []
+    for t in range(T):
+        x = dob if mode == "deployed" else obs
+        fp.act(x, act, deterministic=True)
+        rec["obs"].append(x.clone()); rec["actions"].append(act.clone()); rec["tbefore"].append(tbefore)
+        _, rew, te, tr, info = env.step(act, obs=obs, info="full")
+        env.deploy_obs(info["state"], tgt3, (t + 1) * env.dt, est, alpha=alpha, out=dob, vel_est=v32)
+        tbefore = info["target"].clone()
+        rec["state12"].append(info["state"].clone()); rec["vel_est"].append(v32.clone()); rec["est"].append(est.clone())
+        rec["reward"].append(rew.clone()); rec["terminated"].append(te.clone()); rec["truncated"].append(tr.clone())
+        states.append(env.get_state())
+    return {k: torch.stack(v).cpu().numpy() for k, v in rec.items()}, states
+
+
+def _lengths(term, trunc):
+    done = term | trunc
+    T = done.shape[0]
+    first = np.where(done.any(0), done.argmax(0) + 1, T)
+    status = np.where(~done.any(0), N.PID_RUNNING,
+                      np.where(term[first - 1, np.arange(done.shape[1])], N.PID_TERMINATED, N.PID_TRUNCATED))
+    return first.astype(np.int32), status.astype(np.int32)
+
+
+def _metrics(u, length):
+    """QuadPidMetrics and vel_err_sq from the loop's records, in pid_acc_step's order (csrc/quad_pid.h)."""
+    T, n = u["reward"].shape
+    f64 = lambda: np.zeros(n, np.float64)
+    m = {k: f64() for k in ("total_reward", "pos_err_sum", "pos_err_sq", "pos_err_max", "yaw_rate_abs_sum", "yaw_rate_sum",
+                            "yaw_rate_sq", "yaw_rate_abs_max", "yaw_rate_delta_sum", "vel_err_sq")}
+    m["yaw_rate_sign_changes"] = np.zeros(n, np.int32)
+    prev = np.zeros(n, np.float32)
+    for t in range(T):
+        live = t < length
+        s, tg = u["state12"][t], u["tbefore"][t]
+        d = (s[:, 0:3] - tg).astype(np.float64)  # float32 difference
+        pe = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        yr = s[:, 11]
+        y = yr.astype(np.float64)
+        upd = {"total_reward": m["total_reward"] + u["reward"][t].astype(np.float64), "pos_err_sum": m["pos_err_sum"] + pe,
+               "pos_err_sq": m["pos_err_sq"] + pe * pe, "pos_err_max": np.where(pe > m["pos_err_max"], pe, m["pos_err_max"]),
+               "yaw_rate_abs_sum": m["yaw_rate_abs_sum"] + np.abs(y), "yaw_rate_sum": m["yaw_rate_sum"] + y,
+               "yaw_rate_sq": m["yaw_rate_sq"] + y * y,
+               "yaw_rate_abs_max": np.where(np.abs(y) > m["yaw_rate_abs_max"], np.abs(y), m["yaw_rate_abs_max"])}
+        if t > 0:
+            upd["yaw_rate_sign_changes"] = m["yaw_rate_sign_changes"] + (np.sign(yr) != np.sign(prev)).astype(np.int32)
+            upd["yaw_rate_delta_sum"] = m["yaw_rate_delta_sum"] + np.abs(y - prev.astype(np.float64))
+        e = u["est"][t][4:7].T - s[:, 6:9].astype(np.float64)
+        upd["vel_err_sq"] = m["vel_err_sq"] + ((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])
+        for k, v in upd.items():
+            m[k] = np.where(live, v, m[k])
+        prev = np.where(live, yr, prev)
+    return m
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64, 1: np.uint8}[a.dtype.itemsize])
+
+
+CASES = [
+    # kind, wrapper, mode, n, T, limit, env pins
+    ("hover", None, "env", 33, 12, 7, {}),
+    ("hover", None, "deployed", 130, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    ("hover", "RateControlWrapper", "env", 130, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    ("hover", "RateControlWrapper", "deployed", 514, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    ("hover", "RateControlWrapper", "deployed", 514, 12, 7, {}),
+    ("hover", "RateControlWrapper", "env", 130, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "64"}),
+    ("trajectory", "RateControlWrapper", "env", 130, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    ("trajectory", "RateControlWrapper", "deployed", 33, 12, 7, {}),
+    ("trajectory", "RateControlWrapper", "deployed", 514, 12, 7, {"QUADENV_ROLLOUT_NT": "1"}),
+    ("trajectory", "RateControlWrapper", "env", 514, 12, 7, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    # the default limit: the kernels with compiled-in constants, envs still running at the end; then the same
+    # handle settings through the generic kernels
+    # (8 steps: the small-weight policy saturates the thrust and leaves the box after 11 or 12)
+    ("hover", None, "env", 130, 8, None, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+    ("hover", "RateControlWrapper", "deployed", 130, 8, None, {"QUADENV_SPEC": "0"}),
+    # one long flight, with a policy that hovers (_hover_policy) to the 512-step limit
+    ("hover", "RateControlWrapper", "deployed", 514, 512, None, {"QUADENV_ROLLOUT_NT": "2", "QUADENV_EPISODE_BLOCK": "256"}),
+]
+
+
+@pytest.mark.parametrize("kind,wrapper,mode,n,T,limit,pins", CASES)
+def test_fused_episode_equals_the_per_step_loop(fp, monkeypatch, kind, wrapper, mode, n, T, limit, pins):
+    for k, v in pins.items():
+        monkeypatch.setenv(k, v)
+    if T == 512:
+        fp = FusedPolicy(_hover_policy())
+        fp.pack()
+    envs = [QuadVecEnv(n, env=kind, wrapper=wrapper, device=DEV, seed=11, max_episode_steps=limit, auto_reset=False)
+            for _ in range(2)]
+    for e in envs:
+        e.reset()
+        injected = _inject(e, kind, n)
+    assert episode_supported(fp.policy, envs[0])
+    alpha = torch.from_numpy(ALPHAS3[(np.arange(n) * 5) % 3]).to(DEV)
+    estf = torch.zeros(8, n, dtype=torch.float64, device=DEV)
+    f = _np(fp.episode(envs[0], max_steps=T, obs_mode=mode, alpha=alpha, trace_envs=n, est_state=estf))
+    u, states = _loop(fp, envs[1], mode, T, alpha)
+    length, status = _lengths(u["terminated"], u["truncated"])
+    assert np.array_equal(f["steps"], length) and np.array_equal(f["status"], status)
+    # what happened: the injected terminations (and the patterns, whole groups at their step), the time limit
+    # inside the run or envs still running
+    assert (status == N.PID_TERMINATED).sum() >= injected and length[3] == 1 and length[17] == 3
+    if n >= 130:
+        assert np.all(length[64:96] == 1) and np.all(status[64:96] == N.PID_TERMINATED) and length[96:128].min() > 1
+    if n >= 514:
+        assert np.all(length[128:192] == 2) and length[192:256].min() > 2 and length[0:64].max() > 2
+    if limit is not None:
+        assert ((status == N.PID_TRUNCATED) & (length == limit)).sum() > n // 3 and not (status == N.PID_RUNNING).any()
+    elif T == 512:  # the time limit ends the launch
+        assert ((status == N.PID_TRUNCATED) & (length == T)).sum() > n // 3
+    else:
+        assert ((status == N.PID_RUNNING) & (length == T)).sum() > n // 3
+    live = np.arange(T)[:, None] < length[None, :]
+    for k in ("actions", "obs", "state12", "vel_est"):
+        assert np.array_equal(_bits(f[k])[live], _bits(u[k])[live]), k
+        assert not f[k][~live].any()  # rows past an env's last step are not written
+    want = _metrics(u, length)
+    for k, _ in N.PID_METRIC_FIELDS[2:]:
+        assert np.array_equal(_bits(f[k]), _bits(want[k])), k
+    assert np.array_equal(_bits(f["vel_err_sq"]), _bits(want["vel_err_sq"]))
+    # the estimator block and the env state, each env at its last step
+    idx = np.arange(n)
+    assert np.array_equal(_bits(estf.cpu().numpy()), _bits(u["est"][length - 1, :, idx].T))
+    sf = envs[0].get_state()
+    for k in ("qpos", "qvel", "voltage", "target", "rate_int", "step_count", "episode"):
+        last = np.stack([states[length[i] - 1][k][i] for i in range(n)])
+        assert np.array_equal(_bits(sf[k]), _bits(last)), k
+    assert np.array_equal(sf["step_count"], length)
+    for e in envs:
+        e.close()
+
+
+def _fly(fp, n, mode, alpha=None, alpha_all=0.8, T=40, wrapper="RateControlWrapper", trace=True, seed=3):
+    env = QuadVecEnv(n, wrapper=wrapper, device=DEV, seed=seed, auto_reset=False)
+    env.reset()
+    st0 = env.get_state()
+    _, s12 = env.observe(state=True)
+    s0 = s12.cpu().numpy().copy()
+    r = _np(fp.episode(env, max_steps=T, obs_mode=mode, alpha=alpha, alpha_all=alpha_all, trace_envs=n if trace else 0))
+    r["s0"], r["final_qpos"], r["dt"], r["target"] = s0, env.get_state()["qpos"], env.dt, st0["target"]
+    r["lo"], r["hi"] = np.array(env.cfg.obs_low[:], np.float32), np.array(env.cfg.obs_high[:], np.float32)
+    env.close()
+    return r
+
+
+def test_vel_err_sq_matches_the_ref_on_the_kernels_own_trace(fp):
+    n, T = 96, 40
+    alpha = ALPHAS3[(np.arange(n) * 5) % 3]
+    r = _fly(fp, n, "env", torch.from_numpy(alpha).to(DEV), T=T)
+    for i in range(n):
+        L = int(r["steps"][i])
+        tot, vs = deploy_ref.vel_err_sq(r["state12"][:L, i], r["s0"][i, 0:3], alpha[i], r["dt"])
+        np.testing.assert_allclose(r["vel_err_sq"][i], tot, rtol=1e-12)
+        assert np.array_equal(r["vel_est"][:L, i], vs.astype(np.float32))
+    assert r["vel_err_sq"].min() > 0
+
+
+def test_alpha_null_equals_a_filled_array_and_pairs_permute(fp):
+    n = 130
+    a = _fly(fp, n, "deployed", None, alpha_all=0.5)
+    b = _fly(fp, n, "deployed", torch.full((n,), 0.5, dtype=torch.float64, device=DEV))
+    for k in a:
+        assert np.array_equal(_bits(np.asarray(a[k])), _bits(np.asarray(b[k]))), k
+    # (env, alpha) pairs: G copies of the same 8 start states with the alphas in two orders
+    G, E = 8, 8
+    alphas = np.linspace(0.0, 0.9, G)
+    perm = np.random.default_rng(2).permutation(G)
+    src = QuadVecEnv(E, wrapper="RateControlWrapper", device=DEV, seed=9, auto_reset=False)
+    src.reset()
+    st = src.get_state()
+    src.close()
+    out = []
+    for order in (np.arange(G), perm):
+        env = QuadVecEnv(G * E, wrapper="RateControlWrapper", device=DEV, seed=9, auto_reset=False)
+        env.set_state(**{k: np.tile(v, (G,) + (1,) * (v.ndim - 1)) for k, v in st.items()})
+        al = torch.from_numpy(np.repeat(alphas[order], E)).to(DEV)
+        out.append(_np(fp.episode(env, max_steps=60, obs_mode="deployed", alpha=al)))
+        env.close()
+    for k in out[0]:
+        x = out[0][k].reshape(G, E)[perm]
+        assert np.array_equal(_bits(x), _bits(out[1][k].reshape(G, E))), k
+    assert len({out[0]["total_reward"].reshape(G, E)[g].tobytes() for g in range(G)}) == G  # the alpha matters
+
+
+def test_deployed_obs_is_clipped_and_differs_in_the_velocity_columns_only(fp):
+    n, T = 130, 60
+    r = _fly(fp, n, "deployed", None, alpha_all=0.8, T=T, wrapper=None)
+    L = r["steps"]
+    live = np.arange(T)[:, None] < L[None, :]
+    obs = r["obs"][live]
+    assert np.abs(obs).max() <= 1.0
+    # the env's observation of the state the deployed one was built from: row t + 1 belongs to state12 row t
+    lo, hi = r["lo"], r["hi"]
+    both = live[1:] & live[:-1]
+    s = r["state12"][:-1][both]
+    tgt = np.broadcast_to(r["target"][None], (T - 1, n, 3))[both]
+    raw = s.copy()
+    raw[:, 0:3] = tgt - s[:, 0:3]
+    envobs = np.float32(2.0) * (raw - lo) / (hi - lo) - np.float32(1.0)
+    dep = r["obs"][1:][both]
+    inside = np.abs(envobs) <= 1.0
+    other = [0, 1, 2, 3, 4, 5, 9, 10, 11]
+    assert np.array_equal(dep[:, other][inside[:, other]], envobs[:, other][inside[:, other]])
+    assert np.all(np.abs(dep[:, other][~inside[:, other]]) == 1.0)
+    assert (dep[:, 6:9] != envobs[:, 6:9]).mean() > 0.9  # the estimate, not the true velocity
+    # and the velocity columns are the normalised, clipped estimate
+    v = r["vel_est"][:-1][both]
+    vn = np.clip(np.float32(2.0) * (v - lo[6:9]) / (hi[6:9] - lo[6:9]) - np.float32(1.0), -1, 1)
+    assert np.array_equal(dep[:, 6:9], vn)
+
+
+# ---------------------------------------------------------------------------------------------
+def test_evaluate_episodes_fused_equals_the_loop():
+    pol = _policy()
+    a = EV.evaluate_episodes(pol, 64, wrapper="RateControlWrapper", max_episode_steps=96, device=DEV, seed=4, fused=True)
+    b = EV.evaluate_episodes(pol, 64, wrapper="RateControlWrapper", max_episode_steps=96, device=DEV, seed=4, fused=False)
+    c = EV.evaluate_episodes(pol, 64, wrapper="RateControlWrapper", max_episode_steps=96, device=DEV, seed=4)
+    assert set(a) == set(b) == set(c)
+    for k in b:
+        assert np.array_equal(_bits(np.asarray(a[k])), _bits(np.asarray(b[k]))), k
+        assert np.array_equal(_bits(np.asarray(a[k])), _bits(np.asarray(c[k]))), k
+        assert np.asarray(a[k]).dtype == np.asarray(b[k]).dtype
+    assert a["terminated"].any() or (a["lengths"] == 96).all()
+    d = EV.evaluate_episodes(pol, 64, wrapper="RateControlWrapper", max_episode_steps=96, device=DEV, seed=4,
+                             obs_mode="deployed", velocity_alpha=0.5)
+    assert set(d) == set(a) | {"vel_rmse", "pos_errors"} and d["vel_rmse"] > 0 and d["pos_errors"].shape == (64,)
+    with pytest.raises(ValueError):
+        EV.evaluate_episodes(pol, 8, device=DEV, obs_mode="deployed", fused=False)
+    with pytest.raises(ValueError):
+        EV.evaluate_episodes(pol, 8, device=DEV, wrapper="RelPosActWrapper", fused=True)
+
+
+def test_policy_episodes_fused_equals_the_loop():
+    pol = _policy()
+    args = (pol, 64, "RateControlWrapper", "hover", 96, torch.device(DEV), 4)
+    (a, la), (b, lb) = EV._policy_episodes(*args, fused=True), EV._policy_episodes(*args, fused=False)
+    assert la == lb == 96 and set(a) == set(b) and a["digests"] == b["digests"] and len(set(a["digests"])) == 64
+    for k in b:
+        if k != "digests":
+            assert np.array_equal(_bits(np.asarray(a[k])), _bits(np.asarray(b[k]))), k
+    r = EV.compare_pair("pid", "model", model=pol, num_episodes=32, wrapper=None, max_episode_steps=64, device=DEV)
+    assert r["model"]["digests"] == r["pid"]["digests"] and "model" in r["table"]
+
+
+def test_velocity_estimator_evaluation():
+    pol = _policy()
+    alphas, E, T = (0.0, 0.5, 0.9), 32, 80
+    out = {cl: EV.evaluate_velocity_estimator(pol, alphas, E, max_steps=T, closed_loop=cl, wrapper="RateControlWrapper",
+                                              device=DEV, seed=6, trace_envs=3 * E) for cl in (False, True)}
+    for cl, r in out.items():
+        for k, v in r["start"].items():  # every alpha group starts from the same resets
+            g = np.asarray(v).reshape((3, E) + np.asarray(v).shape[1:])
+            assert np.array_equal(g[0], g[1]) and np.array_equal(g[0], g[2]), k
+        assert r["rmse"].shape == (3,) and np.all(r["rmse"] > 0) and len(r["table"].splitlines()) == 4
+        assert ("mean_reward" in r) == cl and ("survival" in r["table"]) == cl
+    m = out[False]["metrics"]
+    # open loop: the policy never sees the estimate, so every group flies the same episodes
+    tr = m["total_reward"].reshape(3, E)
+    assert np.array_equal(tr[0], tr[1]) and np.array_equal(tr[0], tr[2])
+    assert out[False]["rmse"][0] < out[False]["rmse"][1] < out[False]["rmse"][2]  # more smoothing, more lag
+    assert not np.array_equal(out[True]["mean_reward"][0], out[True]["mean_reward"][2])
+    # alpha = 0: the estimate is the plain finite difference of the traced positions
+    dt = 0.01
+    p0 = out[False]["start"]["qpos"][:E, 0:3].astype(np.float32)
+    for i in range(E):
+        L = int(m["steps"][i])
+        p = np.concatenate([p0[i:i + 1], m["state12"][:L, i, 0:3]]).astype(np.float64)
+        tot = 0.0
+        for k in range(L):
+            v = (p[k + 1] - p[k]) / ((k + 1) * dt - k * dt)
+            d = v - m["state12"][k, i, 6:9].astype(np.float64)
+            tot += (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+        assert m["vel_err_sq"][i] == tot, i
+    assert out[False]["rmse"][0] == np.sqrt(m["vel_err_sq"][:E].sum() / m["steps"][:E].sum())
+
+
+def test_cli_flags(tmp_path, capsys):
+    path = str(tmp_path / "policy.pt")
+    torch.save(_policy().state_dict(), path)
+    r = EV.main(["--model", path, "--test-velocity", "--num-episodes", "16", "--max-steps", "64"])
+    assert r["alphas"] == [0.0, 0.1, 0.2] and "vel RMSE" in capsys.readouterr().out
+    r = EV.main(["--model", path, "--test-velocity", "0.3", "0.8", "--deployed", "--num-episodes", "16", "--max-steps", "64"])
+    assert r["alphas"] == [0.3, 0.8] and "survival" in capsys.readouterr().out
+    r = EV.main(["--model", path, "--deployed", "--velocity-alpha", "0.6", "--num-episodes", "16"])
+    assert "vel_rmse" in r and "Velocity RMSE" in capsys.readouterr().out
+
+
+# ---------------------------------------------------------------------------------------------
+def test_argument_checks(fp):
+    L = N.lib()
+    n = 8
+    m = {k: torch.zeros(n, dtype=getattr(torch, dt), device=DEV) for k, dt in N.PID_METRIC_FIELDS}
+    s12 = torch.zeros(n, 12, device=DEV); t3 = torch.zeros(n, 3, device=DEV); obs = torch.zeros(n, 12, device=DEV)
+    st = torch.zeros(8, n, dtype=torch.float64, device=DEV)
+    act = torch.zeros(n, 4, device=DEV)
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+
+    def ep_rc(h, packed=fp.packed, max_steps=4, trace_envs=0, ta=None, drop=None, est_dt=0.01, max_dt=0.1, alpha_all=0.8,
+              obs_mode=0):
+        mm = {k: (None if k == drop else v.data_ptr()) for k, v in m.items()}
+        run = N.QuadPolicyRun(obs_mode=obs_mode, max_steps=max_steps, trace_envs=trace_envs,
+                              est=N.QuadVelEst(alpha=None, alpha_all=alpha_all, max_dt=max_dt, state=None), est_dt=est_dt,
+                              trace_actions=ta, trace_state12=None, trace_obs=None, trace_vel_est=None,
+                              metrics=N.QuadPidMetrics(**mm), vel_err_sq=None)
+        return L.quad_policy_episode(h, p(packed), C.byref(run), None)
+
+    def dep_rc(h, state=st, s=s12, t=t3, o=obs, rows=n, max_dt=0.1, alpha_all=0.8):
+        est = N.QuadVelEst(alpha=None, alpha_all=alpha_all, max_dt=max_dt, state=p(state))
+        return L.quad_deploy_obs(h, C.byref(est), p(s), p(t), 0.0, rows, p(o), None, None)
+
+    good = QuadVecEnv(n, device=DEV, auto_reset=False)
+    good.reset()
+    before = good.get_state()
+    unaligned = act.data_ptr() + 4
+    for rc in (ep_rc(good._h, max_steps=0), ep_rc(good._h, trace_envs=n + 1), ep_rc(good._h, trace_envs=-1),
+               ep_rc(good._h, drop="steps"), ep_rc(good._h, drop="yaw_rate_delta_sum"), ep_rc(good._h, est_dt=0.0),
+               ep_rc(good._h, est_dt=-0.01), ep_rc(good._h, est_dt=float("nan")), ep_rc(good._h, max_dt=0.0),
+               ep_rc(good._h, max_dt=-1.0), ep_rc(good._h, alpha_all=float("inf")), ep_rc(good._h, alpha_all=float("nan")),
+               ep_rc(good._h, obs_mode=2), ep_rc(good._h, packed=None), ep_rc(good._h, trace_envs=n, ta=unaligned),
+               ep_rc(None), L.quad_policy_episode(good._h, p(fp.packed), None, None),
+               dep_rc(good._h, state=None), dep_rc(good._h, s=None), dep_rc(good._h, t=None), dep_rc(good._h, o=None),
+               dep_rc(good._h, rows=0), dep_rc(good._h, max_dt=0.0), dep_rc(good._h, alpha_all=float("nan")), dep_rc(None)):
+        assert rc == N.QUAD_EINVAL
+        assert len(L.quad_last_error()) > 0
+    big = QuadVecEnv(1 << 16, device=DEV, auto_reset=False)
+    mb = {k: torch.zeros(1 << 16, dtype=getattr(torch, dt), device=DEV) for k, dt in N.PID_METRIC_FIELDS}
+    run = N.QuadPolicyRun(obs_mode=0, max_steps=2048, trace_envs=1 << 16,
+                          est=N.QuadVelEst(alpha=None, alpha_all=0.8, max_dt=0.1, state=None), est_dt=0.01,
+                          trace_actions=act.data_ptr(), metrics=N.QuadPidMetrics(**{k: v.data_ptr() for k, v in mb.items()}))
+    assert L.quad_policy_episode(big._h, p(fp.packed), C.byref(run), None) == N.QUAD_EINVAL and b"32-bit" in L.quad_last_error()
+    big.close()
+    torch.cuda.synchronize()
+    after = good.get_state()
+    assert all(np.array_equal(before[k], after[k]) for k in before)  # nothing was launched
+    assert ep_rc(good._h) == N.QUAD_OK and ep_rc(good._h, obs_mode=1) == N.QUAD_OK and dep_rc(good._h) == N.QUAD_OK
+    torch.cuda.synchronize()
+    good.close()
+    for kw in (dict(env="brax_hover"), dict(env="brax_jax_mjx"), dict(wrapper="RelPosActWrapper"), dict(wrapper="ctbr_relpos")):
+        e = QuadVecEnv(n, device=DEV, auto_reset=False, **kw)
+        assert ep_rc(e._h) == N.QUAD_EINVAL and len(L.quad_last_error()) > 0
+        assert not episode_supported(fp.policy, e)
+        e.close()
+    for kw in (dict(), dict(wrapper="RateControlWrapper"), dict(env="trajectory", wrapper="RateControlWrapper")):
+        e = QuadVecEnv(n, device=DEV, **kw)  # auto_reset = 1 is not consulted
+        e.reset()
+        assert ep_rc(e._h) == N.QUAD_OK and episode_supported(fp.policy, e)
+        torch.cuda.synchronize()
+        e.close()

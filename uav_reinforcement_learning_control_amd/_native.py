@@ -20,7 +20,7 @@ QUAD_ADV_GIVEN = 3        # ... : the sums are in QuadPPOBatch.adv_sums (quad_pp
 ADV_SUM_DOUBLES = 512     # QUAD_ADV_SUM_DOUBLES: one minibatch's block sums
 ENV_HOVER, ENV_TRAJ, ENV_BRAX_HOVER, ENV_BRAX_TRAJ = 0, 1, 2, 3
 WRAP_NONE, WRAP_CTBR, WRAP_RELPOS, WRAP_CTBR_RELPOS = 0, 1, 2, 3
-ABI_VERSION = 7
+ABI_VERSION = 8
 PID_YAW_FRAME, PID_WORLD_FRAME = 0, 1
 PID_RUNNING, PID_TERMINATED, PID_TRUNCATED, PID_INVALID = 0, 1, 2, 3
 
@@ -124,6 +124,23 @@ class QuadCtrlRun(C.Structure):
                 ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("metrics", QuadPidMetrics)]
 
 
+# the deployed observation path (policy_node.py's estimator and builder) and the policy's fused episode
+OBS_ENV, OBS_DEPLOYED = 0, 1
+OBS_MODES = {"env": OBS_ENV, "deployed": OBS_DEPLOYED, OBS_ENV: OBS_ENV, OBS_DEPLOYED: OBS_DEPLOYED}
+EST_NSTATE = 8
+
+
+class QuadVelEst(C.Structure):
+    _fields_ = [("alpha", C.c_void_p), ("alpha_all", C.c_double), ("max_dt", C.c_double), ("state", C.c_void_p)]
+
+
+class QuadPolicyRun(C.Structure):
+    _fields_ = [("obs_mode", C.c_int32), ("max_steps", C.c_int32), ("trace_envs", C.c_int32),
+                ("est", QuadVelEst), ("est_dt", C.c_double),
+                ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("trace_obs", C.c_void_p),
+                ("trace_vel_est", C.c_void_p), ("metrics", QuadPidMetrics), ("vel_err_sq", C.c_void_p)]
+
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -153,7 +170,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_ppo_grad_form", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_permutation", "quad_adam_workspace_bytes",
            "quad_clip_adam",
            "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
-           "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode")
+           "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode",
+           "quad_deploy_obs", "quad_policy_episode")
 
 
 class QuadRollout(C.Structure):
@@ -247,8 +265,11 @@ def _declare(L):
     L.quad_ctrl_default_params.argtypes = [C.POINTER(QuadCtrlParams)]
     L.quad_ctrl_act.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     L.quad_ctrl_episode.argtypes = [vp, C.POINTER(QuadCtrlRun), vp]
+    L.quad_deploy_obs.argtypes = [vp, C.POINTER(QuadVelEst), vp, vp, C.c_double, i32, vp, vp, vp]
+    L.quad_policy_episode.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), vp]
     for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
-              "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode"):
+              "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode", "quad_deploy_obs",
+              "quad_policy_episode"):
         getattr(L, n).restype = C.c_int
     for n in ("quad_clip_adam", "quad_ppo_grad", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_default_cfg", "quad_create", "quad_seed", "quad_reset", "quad_step", "quad_step_range", "quad_observe", "quad_terminated", "quad_step_random",
               "quad_random_actions", "quad_get_state", "quad_set_state", "quad_gae",

@@ -1,0 +1,36 @@
+// policy_episode.h -- host-side entries of the deployed-observation law and the fused policy episode
+// (policy_episode.hip), called by quad_deploy_obs and quad_policy_episode.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/quadenv.h"
+#include "env_tiles.h"
+
+namespace quadenv {
+
+struct EstArgs {  // QuadVelEst, flattened
+  const double* alpha;
+  double alpha_all, max_dt;
+  double* state;
+};
+
+struct EpisodeArgs {  // QuadPolicyRun, flattened
+  int32_t max_steps, trace_envs;
+  EstArgs est;
+  double est_dt;
+  float *trace_actions, *trace_state12, *trace_obs, *trace_vel_est;
+  QuadPidMetrics metrics;
+  double* vel_err_sq;
+};
+
+// k_deploy_obs over n rows (the observation bounds are the handle's constant block kc)
+hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const float* state12, const float* target3,
+                             double timestamp, int32_t n, float* obs, float* vel_est, hipStream_t s);
+
+// k_policy_episode<env_kind, ctbr, ., spec, obs_mode> over all envs of kp; the block shape is chosen here
+hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
+                                 int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s);
+
+}  // namespace quadenv

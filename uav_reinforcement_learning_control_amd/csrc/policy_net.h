@@ -449,6 +449,28 @@ __device__ __forceinline__ void stage_pieces(float* lds, const float* __restrict
   __syncthreads();
 }
 
+// X^T fragments of the wave's tile(s) from the per-thread observation rows (rollout.hip's env-to-lane mapping: with NT = 2 lane l's env is tile l >> 5's
+// env l & 31, with NT = 1 both lane halves carry env l & 31): lane half h
+// takes features 8h .. 8h + 7 (zero past feature 11) of its env in each tile.
+template <int NT>
+__device__ __forceinline__ void fragments(const float ob[12], float (&xb)[NT][8]) {
+  const bool h = (threadIdx.x & 32) != 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const float lo = ob[k], hi = k < 4 ? ob[8 + k] : 0.f;  // this env's features k and 8 + k
+    if constexpr (NT == 2) {  // lane l's env is tile (l >> 5)'s env l & 31
+      // the other lane half's value (v_permlane32_swap: first result = lanes 0-31's, second = 32-63's)
+      const float x = h ? lo : hi;
+      const auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+      const float got = __uint_as_float(h ? p[0] : p[1]);
+      xb[0][k] = h ? got : lo;
+      xb[NT - 1][k] = h ? hi : got;
+    } else {  // both lane halves carry env l & 31
+      xb[0][k] = h ? hi : lo;
+    }
+  }
+}
+
 // Box-Muller on Philox(seed; env, step, 0x200) -> 4 standard normals
 __device__ __forceinline__ void gauss4(uint64_t seed, uint64_t env, uint32_t step, float z[4]) {
   uint32_t c[4] = {uint32_t(env), uint32_t(env >> 32), step, 0x200u};

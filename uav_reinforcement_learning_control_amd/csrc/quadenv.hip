@@ -40,6 +40,7 @@
 #include "kconsts_default.h"
 #include "ctrl.h"
 #include "pid.h"
+#include "policy_episode.h"
 #include "rollout.h"
 
 using namespace quadenv;
@@ -1386,6 +1387,63 @@ int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream) {
   if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
   HIP_TRY(launch_ctrl_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
                               static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- the deployed observation path and the policy's fused episode (kernels: policy_episode.hip)
+static int check_est(const QuadVelEst* e, const char* who) {
+  const std::string w(who);
+  if (!e->alpha && !std::isfinite(e->alpha_all)) return fail(QUAD_EINVAL, w + ": alpha_all must be finite");
+  if (!(e->max_dt > 0.0)) return fail(QUAD_EINVAL, w + ": max_dt must be > 0");
+  return QUAD_OK;
+}
+
+int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
+  if (!h || !est) return fail(QUAD_EINVAL, "handle/est is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_deploy_obs: env_kind must be HOVER or TRAJ");
+  if (int rc = check_est(est, "quad_deploy_obs")) return rc;
+  if (!est->state) return fail(QUAD_EINVAL, "quad_deploy_obs: the estimator state block is required");
+  if (!state12 || !target3 || !obs) return fail(QUAD_EINVAL, "quad_deploy_obs: state12, target3 and obs are required");
+  if (n < 1) return fail(QUAD_EINVAL, "quad_deploy_obs: n must be >= 1");
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_deploy_obs(h->kdev, EstArgs{est->alpha, est->alpha_all, est->max_dt, est->state}, state12, target3,
+                            timestamp, n, obs, vel_est, static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream) {
+  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_policy_episode: env_kind must be HOVER or TRAJ");
+  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_policy_episode: the policy takes 12-D obs (no RELPOS)");
+  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED)
+    return fail(QUAD_EINVAL, "quad_policy_episode: unknown obs_mode");
+  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_policy_episode: max_steps must be >= 1");
+  const QuadPidMetrics& m = r->metrics;
+  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
+      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
+      !m.yaw_rate_delta_sum)
+    return fail(QUAD_EINVAL, "quad_policy_episode: every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_policy_episode: trace_envs must be in [0, N]");
+  if (int rc = check_est(&r->est, "quad_policy_episode")) return rc;
+  if (!(r->est_dt > 0.0)) return fail(QUAD_EINVAL, "quad_policy_episode: est_dt must be > 0");
+  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est;
+  if (any_trace && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
+      return fail(QUAD_EINVAL, "quad_policy_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
+         reinterpret_cast<uintptr_t>(r->trace_obs)) & 15u)
+      return fail(QUAD_EINVAL, "quad_policy_episode: the action, state12 and obs traces must be 16-byte aligned");
+  }
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return fail(QUAD_EINVAL, "quad_policy_episode: packed must be 16-byte aligned");
+  DeviceGuard g(h->device);
+  EpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0,
+                EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
+                r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
+  HIP_TRY(launch_policy_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode,
+                                packed, a, static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

@@ -260,6 +260,30 @@ class QuadVecEnv:
         from .. import controllers
         return controllers.ctrl_episode(self, params, set_of, law, max_steps, trace_envs, state)
 
+    # the deployed observation path (policy_node.py's velocity estimator and observation builder)
+    def deploy_obs(self, state12: torch.Tensor, target3: torch.Tensor, timestamp: float, est_state: torch.Tensor,
+                   alpha=None, alpha_all: float = 0.8, max_dt: float = 0.1, out: Optional[torch.Tensor] = None,
+                   vel_est: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One VelocityEstimator.update(position, timestamp) and one build_observation per row
+        (quad_deploy_obs): state12 [n,12], target3 [n,3], est_state float64 [8,n] (zero it at an episode
+        start; updated in place), alpha float64 [n] or None (alpha_all). Returns obs [n,12]; vel_est [n,3]
+        receives the estimate when given."""
+        n = int(state12.shape[0])
+        self._check(state12, (n, 12), torch.float32)
+        self._check(target3, (n, 3), torch.float32)
+        self._check(est_state, (N.EST_NSTATE, n), torch.float64)
+        out = torch.empty(n, 12, dtype=torch.float32, device=self.device) if out is None else out
+        self._check(out, (n, 12), torch.float32)
+        if vel_est is not None:
+            self._check(vel_est, (n, 3), torch.float32)
+        if alpha is not None:
+            self._check(alpha, (n,), torch.float64)
+        est = N.QuadVelEst(alpha=_ptr(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
+                           state=_ptr(est_state))
+        N.check(N.lib().quad_deploy_obs(self._h, C.byref(est), _ptr(state12), _ptr(target3), float(timestamp), n,
+                                        _ptr(out), _ptr(vel_est), self._stream()), "quad_deploy_obs")
+        return out
+
     # ------------------------------------------------------------------------------------
     _FIELDS = (("qpos", 11, np.float32), ("qvel", 10, np.float32), ("voltage", 1, np.float32),
                ("target", 3, np.float32), ("rate_int", 3, np.float32),

@@ -158,18 +158,64 @@ def evaluate_waypoints(model, trajectories: Sequence = ("eight",), spacings: Seq
     return out
 
 
+def _use_fused(fused: Optional[bool], policy, e, obs_mode: str) -> bool:
+    """None: the fused launch where quad_policy_episode flies this policy on this env, else the per-step loop."""
+    from .ppo.fused import episode_supported
+    if obs_mode not in ("env", "deployed"):
+        raise ValueError(f"obs_mode must be \"env\" or \"deployed\", got {obs_mode!r}")
+    ok = episode_supported(policy, e)
+    use = ok if fused is None else bool(fused)
+    if use and not ok:
+        raise ValueError("fused=True: quad_policy_episode flies 12-128-128-4 policies on hover / trajectory envs "
+                         "with 12-D observations")
+    if obs_mode == "deployed" and not use:
+        raise ValueError("obs_mode=\"deployed\" runs in the fused launch only")
+    return use
+
+
+def _fused_episodes(policy, e, obs_mode: str, velocity_alpha: Optional[float]) -> dict:
+    """One quad_policy_episode launch over e's envs; the metric arrays on the host."""
+    from .ppo.fused import FusedPolicy
+    fp = FusedPolicy(policy)
+    fp.pack()
+    m = fp.episode(e, obs_mode=obs_mode, alpha_all=0.8 if velocity_alpha is None else float(velocity_alpha))
+    torch.cuda.synchronize(e.device)
+    return {k: v.cpu().numpy() for k, v in m.items()}
+
+
+def vel_rmse(vel_err_sq, steps) -> float:
+    """evaluate.py:751-760's RMSE of the velocity estimate: sqrt(sum of |v_est - v_true|^2 / samples)."""
+    return float(np.sqrt(np.sum(np.asarray(vel_err_sq, np.float64)) / max(int(np.sum(steps)), 1)))
+
+
 @torch.no_grad()
 def evaluate_episodes(model, num_episodes: int = 1024, wrapper: Optional[str] = "auto", env: str = "hover",
-                      max_episode_steps: Optional[int] = None, device="cuda", seed: int = 0) -> dict:
+                      max_episode_steps: Optional[int] = None, device="cuda", seed: int = 0,
+                      fused: Optional[bool] = None, obs_mode: str = "env",
+                      velocity_alpha: Optional[float] = None) -> dict:
     """``num_episodes`` episodes at once from HoverEnv resets, deterministic policy, each run to
     termination or truncation (evaluate.py:296-437 without the viewer). Returns per-episode
-    rewards / lengths / terminated flags and their mean / std."""
+    rewards / lengths / terminated flags and their mean / std. `fused`: None flies them in one
+    quad_policy_episode launch where that is supported, else in the per-step loop (the same bits);
+    obs_mode="deployed" feeds the policy the ROS2 node's observation (velocity estimated with
+    `velocity_alpha`, default 0.8; clipped) and adds vel_rmse and pos_errors."""
     device = torch.device(device)
     policy, cfg_wrapper = load_policy(model, device)
     wrapper = cfg_wrapper if wrapper == "auto" else wrapper
     e = QuadVecEnv(num_episodes, env=env, wrapper=wrapper, device=device, seed=seed,
                    max_episode_steps=max_episode_steps, auto_reset=False)
     obs = e.reset().clone()
+    if _use_fused(fused, policy, e, obs_mode):
+        m = _fused_episodes(policy, e, obs_mode, velocity_alpha)
+        e.close()
+        r, l = m["total_reward"], m["steps"]
+        out = {"rewards": r, "lengths": l, "terminated": m["status"] == N.PID_TERMINATED,
+               "mean_reward": float(r.mean()), "std_reward": float(r.std()),
+               "mean_length": float(l.mean()), "std_length": float(l.std())}
+        if obs_mode == "deployed":
+            out["vel_rmse"] = vel_rmse(m["vel_err_sq"], l)
+            out["pos_errors"] = m["pos_err_sum"] / np.maximum(l, 1)
+        return out
     act = _Actor(policy, num_episodes, device)
     ret = torch.zeros(num_episodes, dtype=torch.float64, device=device)
     length = torch.zeros(num_episodes, dtype=torch.int32, device=device)
@@ -251,8 +297,11 @@ def _table(rows_in) -> str:
     return "\n".join(rows)
 
 
-def _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, device, seed) -> tuple:
-    """The policy's episodes with the PID metric's position error: (summary, the env's time limit)."""
+def _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, device, seed,
+                     fused: Optional[bool] = None, obs_mode: str = "env",
+                     velocity_alpha: Optional[float] = None) -> tuple:
+    """The policy's episodes with the PID metric's position error: (summary, the env's time limit). `fused`,
+    `obs_mode` and `velocity_alpha` as in evaluate_episodes."""
     policy, cfg_wrapper = load_policy(model, device)
     wrapper = cfg_wrapper if wrapper == "auto" else wrapper
     e = QuadVecEnv(num_episodes, env=env, wrapper=wrapper, device=device, seed=seed,
@@ -260,6 +309,16 @@ def _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, devic
     obs = e.reset().clone()
     reset_obs = obs.clone()
     digests = episode_digests(e)
+    if _use_fused(fused, policy, e, obs_mode):
+        m = _fused_episodes(policy, e, obs_mode, velocity_alpha)
+        l, te_np = m["steps"], m["status"] == N.PID_TERMINATED
+        pe = m["pos_err_sum"] / np.maximum(l, 1)
+        extra = {"vel_rmse": vel_rmse(m["vel_err_sq"], l)} if obs_mode == "deployed" else {}
+        pol = _summary(m["total_reward"], l, te_np, pos_errors=pe, mean_pos_error=float(pe.mean()),
+                       survival=float((~te_np).mean()), reset_obs=reset_obs.cpu().numpy(), digests=digests, **extra)
+        max_steps = e.max_episode_steps
+        e.close()
+        return pol, max_steps
     act = _Actor(policy, num_episodes, device)
     n = num_episodes
     ret = torch.zeros(n, dtype=torch.float64, device=device)
@@ -359,6 +418,72 @@ def compare_pair(a: str, b: str, model=None, params=None, num_episodes: int = 25
     return out
 
 
+@torch.no_grad()
+def evaluate_velocity_estimator(model, alphas: Sequence[float] = (0.0, 0.1, 0.2), num_episodes: int = 256,
+                                max_steps: int = 2000, closed_loop: bool = False, wrapper: Optional[str] = "auto",
+                                env: str = "hover", device="cuda", seed: int = 0, trace_envs: int = 0) -> dict:
+    """The reference's ``evaluate.py --test-velocity`` (:615-770), batched: every alpha of `alphas` flies the
+    same `num_episodes` resets (alpha-major: env a * num_episodes + e starts from reset e, so a wave shares
+    its alpha) for up to `max_steps` steps in one launch. closed_loop=False is the reference's test: the
+    policy sees the env's observation and the estimators run beside it. closed_loop=True feeds the policy
+    the deployed observation, which the reference never does. Returns {"alphas", "rmse" (per alpha:
+    sqrt(sum vel_err_sq / sum steps)), "steps", "start" (the copied start states), "metrics", "table"}, with
+    closed_loop=True also "mean_reward", "mean_length", "survival" and "mean_pos_error" per alpha."""
+    from .ppo.fused import FusedPolicy, episode_supported
+    device = torch.device(device)
+    alphas = [float(a) for a in alphas]
+    if not alphas or num_episodes < 1:
+        raise ValueError("at least one alpha and one episode are required")
+    policy, cfg_wrapper = load_policy(model, device)
+    wrapper = cfg_wrapper if wrapper == "auto" else wrapper
+    A, E = len(alphas), int(num_episodes)
+    src = QuadVecEnv(E, env=env, wrapper=wrapper, device=device, seed=seed, max_episode_steps=max_steps,
+                     auto_reset=False)
+    src.reset()
+    st = src.get_state()
+    src.close()
+    e = QuadVecEnv(A * E, env=env, wrapper=wrapper, device=device, seed=seed, max_episode_steps=max_steps,
+                   auto_reset=False)
+    if not episode_supported(policy, e):
+        e.close()
+        raise ValueError("evaluate_velocity_estimator needs a 12-128-128-4 policy on a 12-D observation env")
+    start = {k: np.tile(v, (A,) + (1,) * (v.ndim - 1)) for k, v in st.items()}
+    e.set_state(**start)
+    fp = FusedPolicy(policy)
+    fp.pack()
+    alpha = torch.tensor(alphas, dtype=torch.float64, device=device).repeat_interleave(E)
+    m = fp.episode(e, max_steps=max_steps, obs_mode="deployed" if closed_loop else "env", alpha=alpha,
+                   trace_envs=trace_envs)
+    torch.cuda.synchronize(device)
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    e.close()
+    return velocity_summary(alphas, E, m, closed_loop, start)
+
+
+def velocity_summary(alphas, episodes: int, m: dict, closed_loop: bool, start: Optional[dict] = None) -> dict:
+    """evaluate_velocity_estimator's figures from the alpha-major metric arrays of one launch."""
+    A, E = len(alphas), int(episodes)
+    steps = np.asarray(m["steps"]).reshape(A, E)
+    out = {"alphas": list(alphas), "steps": steps.sum(axis=1), "metrics": m, "start": start,
+           "rmse": np.array([vel_rmse(np.asarray(m["vel_err_sq"]).reshape(A, E)[a], steps[a]) for a in range(A)])}
+    rows = [f"{'alpha':>6} {'vel RMSE':>12} {'samples':>9}"]
+    if closed_loop:
+        st = np.asarray(m["status"]).reshape(A, E)
+        out["mean_reward"] = np.asarray(m["total_reward"]).reshape(A, E).mean(axis=1)
+        out["mean_length"] = steps.mean(axis=1)
+        out["survival"] = (st != N.PID_TERMINATED).mean(axis=1)
+        out["mean_pos_error"] = (np.asarray(m["pos_err_sum"]).reshape(A, E) / np.maximum(steps, 1)).mean(axis=1)
+        rows[0] += f" {'reward':>10} {'length':>8} {'survival':>9} {'pos error':>10}"
+    for a in range(A):
+        row = f"{alphas[a]:6.2f} {out['rmse'][a]:8.4f} m/s {int(out['steps'][a]):9d}"
+        if closed_loop:
+            row += (f" {out['mean_reward'][a]:10.2f} {out['mean_length'][a]:8.1f} {100 * out['survival'][a]:8.1f}% "
+                    f"{out['mean_pos_error'][a]:9.3f}m")
+        rows.append(row)
+    out["table"] = "\n".join(rows)
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--model", default=None, help="policy archive / state dict (not needed with --controller pid)")
@@ -378,7 +503,21 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int, default=5000)
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--num-episodes", type=int, default=1024)
+    ap.add_argument("--test-velocity", nargs="*", type=float, default=None, metavar="ALPHA",
+                    help="the velocity estimator's RMSE per low-pass alpha (default 0.0 0.1 0.2)")
+    ap.add_argument("--deployed", action="store_true",
+                    help="feed the policy the ROS2 node's observation (estimated velocity, clipped); with "
+                         "--test-velocity: close the loop through the estimator")
+    ap.add_argument("--velocity-alpha", type=float, default=None,
+                    help="the estimator's alpha for --deployed episodes (default 0.8)")
     a = ap.parse_args(argv)
+    if a.test_velocity is not None:
+        if a.model is None:
+            ap.error("--test-velocity needs --model")
+        r = evaluate_velocity_estimator(a.model, a.test_velocity or [0.0, 0.1, 0.2], a.num_episodes,
+                                        max_steps=min(a.max_steps, 2000), closed_loop=a.deployed, env=a.env)
+        print(r["table"])
+        return r
     if a.compare or a.controller in ("se3", "smc", "lqr"):
         from .controllers import CtrlParams
         params = CtrlParams.from_json(a.gains) if a.gains else CtrlParams()
@@ -406,10 +545,13 @@ def main(argv=None):
         r = compare_controllers(a.model, a.gains, a.num_episodes, env=a.env)
         print(r["table"])
         return r
-    if a.mode == "episodes":
-        r = evaluate_episodes(a.model, a.num_episodes)
+    if a.mode == "episodes" or a.deployed:
+        r = evaluate_episodes(a.model, a.num_episodes, obs_mode="deployed" if a.deployed else "env",
+                              velocity_alpha=a.velocity_alpha)
         print(f"Episodes: {a.num_episodes}\nMean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
               f"Mean length: {r['mean_length']:.1f} +/- {r['std_length']:.1f}")
+        if a.deployed:
+            print(f"Velocity RMSE: {r['vel_rmse']:.4f} m/s\nMean error: {r['pos_errors'].mean():.3f}m")
         return r
     r = evaluate_waypoints(a.model, a.trajectory, a.spacing, a.reach_radius, a.max_steps, a.replicas)
     status = {0: "running", 1: "lap", 2: "terminated", 3: "max steps"}

@@ -149,6 +149,59 @@ class FusedPolicy:
                           gamma=float(gamma))
         N.check(N.lib().quad_rollout(env._h, _p(self.packed), C.byref(r), self._stream()), "quad_rollout")
 
+    def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
+                max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
+        """quad_policy_episode: the deterministic policy's whole episodes from the envs' current state (call
+        env.reset() first) in one launch. Every env runs to its first terminated / truncated step or
+        `max_steps` (default: the env's max_episode_steps) and is then frozen, not reset. obs_mode "env": the
+        policy sees the env's observation and the deployed velocity estimator runs beside it; "deployed": the
+        policy sees what the reference's ROS2 node would feed it (estimated velocity, clipped). `alpha`: one
+        low-pass coefficient per env ([N] float64) or None for `alpha_all`. Returns device tensors: the
+        QuadPidMetrics fields and "vel_err_sq" ([N]); with trace_envs = M > 0 also "actions" [T, M, 4], "obs"
+        and "state12" [T, M, 12] and "vel_est" [T, M, 3] of the first M envs (rows past an env's last step
+        stay zero)."""
+        n, dev = env.num_envs, self.device
+        T = int(env.max_episode_steps if max_steps is None else max_steps)
+        M = int(trace_envs)
+        res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+        res["vel_err_sq"] = torch.zeros(n, dtype=torch.float64, device=dev)
+        if M > 0 and T > 0:
+            for k, w in (("actions", 4), ("obs", 12), ("state12", 12), ("vel_est", 3)):
+                res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
+        if alpha is not None:
+            alpha = torch.as_tensor(alpha, dtype=torch.float64, device=dev).contiguous()
+            _need(alpha, (n,), torch.float64, dev, "alpha")
+        if est_state is not None:
+            _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
+        tr = lambda k: res[k].data_ptr() if k in res else None
+        run = N.QuadPolicyRun(obs_mode=N.OBS_MODES[obs_mode], max_steps=T, trace_envs=M,
+                              est=N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
+                                               state=_p(est_state)),
+                              est_dt=float(env.dt), trace_actions=tr("actions"), trace_state12=tr("state12"),
+                              trace_obs=tr("obs"), trace_vel_est=tr("vel_est"),
+                              metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
+                              vel_err_sq=res["vel_err_sq"].data_ptr())
+        N.check(N.lib().quad_policy_episode(env._h, _p(self.packed), C.byref(run), self._stream()),
+                "quad_policy_episode")
+        return res
+
+
+def _net_supported(policy) -> bool:
+    try:
+        FusedPolicy._check_shapes(policy)
+    except (ValueError, AttributeError, IndexError, TypeError):
+        return False
+    return policy.log_std.device.type == "cuda"
+
+
+def episode_supported(policy, env) -> bool:
+    """quad_policy_episode flies a 12-128-128-4 actor on hover / trajectory envs (12-D obs), with or without
+    RateControlWrapper; the handle's auto-reset setting does not matter."""
+    cfg = getattr(env, "cfg", None)
+    return (cfg is not None and getattr(env, "_h", None) is not None
+            and cfg.env_kind in (N.ENV_HOVER, N.ENV_TRAJ) and cfg.wrapper in (N.WRAP_NONE, N.WRAP_CTBR)
+            and _net_supported(policy))
+
 
 def rollout_supported(env) -> bool:
     """quad_rollout drives hover / trajectory envs (12-D obs) with SB3 auto-reset."""
