@@ -427,6 +427,38 @@ typedef struct QuadPolicyRun {
 } QuadPolicyRun;
 int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream);
 
+/* ---- Waypoint laps in ONE launch: evaluate.py:440-612 evaluate_trajectory for the policy and
+ * for every law of the controller family. Call after quad_waypoints_begin (or an earlier run: s is in / out).
+ * Every env whose tracker status is 0 runs (law or actor -> env step -> tracker) until its tracker status
+ * leaves 0 or for max_steps iterations and is then frozen, as in quad_ctrl_episode; an env that enters with
+ * another status takes no step. A switch overwrites the env's target register, so the handle must be of the
+ * HOVER kind (the reference builds a HoverEnv); wrapper NONE for the laws, NONE or CTBR for the policy.
+ * reach_radius >= 0 (0: no waypoint is ever reached, the distance test is strict).
+ * The metrics' status is QUAD_PID_LAP where the tracker's is 1, TERMINATED / TRUNCATED where it is 2 / 3,
+ * RUNNING where it is still 0, and QUAD_PID_INVALID for an env whose QuadCtrlRun set_of entry is out of
+ * range: that env takes no step and its tracker row is left as it was. The metrics restart from zero in
+ * every call; the tracker's steps and total_reward carry on. The position error uses the target read before
+ * the step. Controller and estimator state carry across switches: nothing resets them.
+ * Traces: the run's own (QuadCtrlRun / QuadPolicyRun) plus trace_reward [max_steps][trace_envs] and
+ * trace_wp_idx [max_steps][trace_envs], the index of the waypoint the step flew toward; the run's
+ * max_steps * trace_envs bound applies.
+ * Contract: bit-identical, for every env up to its last step, to this loop on a second handle with
+ * auto_reset = 0: quad_observe and quad_target_info once; per step quad_ctrl_act (or quad_policy_act with
+ * deterministic = 1), quad_step, quad_waypoints_update, quad_target_info. In QUAD_OBS_ENV the policy acts on
+ * quad_step's observation, which is built with the target the step was flown with -- one step stale after a
+ * switch, as evaluate.py:537-555 has it. In QUAD_OBS_DEPLOYED it acts on quad_deploy_obs called after the
+ * tracker update with the env's new target: the node always reads the current setpoint. */
+#define QUAD_PID_LAP 4 /* joins QUAD_PID_RUNNING .. QUAD_PID_INVALID */
+typedef struct QuadWaypointRun {
+  QuadWaypoints w;
+  QuadWaypointState s;    /* in/out: as quad_waypoints_begin (or an earlier run) left it */
+  float*   trace_reward;  /* [max_steps][trace_envs] or NULL */
+  int32_t* trace_wp_idx;  /* the waypoint index the step flew toward, or NULL */
+} QuadWaypointRun;
+int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointRun* wr, void* stream);
+int quad_policy_waypoints(QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
+                          void* stream);
+
 /* PPO rollout support (row P of the scope table): generalized advantage estimation over a
  * time-major rollout, SB3 RolloutBuffer.compute_returns_and_advantage semantics.
  *  rewards, values, episode_starts: device [T,N] float32 (episode_starts 1.0 where the step

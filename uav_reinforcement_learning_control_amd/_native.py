@@ -23,6 +23,7 @@ WRAP_NONE, WRAP_CTBR, WRAP_RELPOS, WRAP_CTBR_RELPOS = 0, 1, 2, 3
 ABI_VERSION = 8
 PID_YAW_FRAME, PID_WORLD_FRAME = 0, 1
 PID_RUNNING, PID_TERMINATED, PID_TRUNCATED, PID_INVALID = 0, 1, 2, 3
+PID_LAP = 4  # quad_ctrl_waypoints / quad_policy_waypoints: the env completed its lap
 
 
 class QuadCfg(C.Structure):
@@ -76,6 +77,11 @@ class QuadWaypoints(C.Structure):
 
 class QuadWaypointState(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("wp_idx", "reached", "laps", "steps", "status", "total_reward")]
+
+
+class QuadWaypointRun(C.Structure):
+    _fields_ = [("w", QuadWaypoints), ("s", QuadWaypointState), ("trace_reward", C.c_void_p),
+                ("trace_wp_idx", C.c_void_p)]
 
 
 # QuadPidGains: the 21 numbers of pid_gains.json in CascadedPIDController.__init__'s order, then MASS
@@ -171,7 +177,7 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_clip_adam",
            "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
            "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode",
-           "quad_deploy_obs", "quad_policy_episode")
+           "quad_deploy_obs", "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints")
 
 
 class QuadRollout(C.Structure):
@@ -267,9 +273,11 @@ def _declare(L):
     L.quad_ctrl_episode.argtypes = [vp, C.POINTER(QuadCtrlRun), vp]
     L.quad_deploy_obs.argtypes = [vp, C.POINTER(QuadVelEst), vp, vp, C.c_double, i32, vp, vp, vp]
     L.quad_policy_episode.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), vp]
+    L.quad_ctrl_waypoints.argtypes = [vp, C.POINTER(QuadCtrlRun), C.POINTER(QuadWaypointRun), vp]
+    L.quad_policy_waypoints.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), C.POINTER(QuadWaypointRun), vp]
     for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
               "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode", "quad_deploy_obs",
-              "quad_policy_episode"):
+              "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints"):
         getattr(L, n).restype = C.c_int
     for n in ("quad_clip_adam", "quad_ppo_grad", "quad_ppo_hidden", "quad_ppo_adv_stats", "quad_ppo_adv_stats_epoch", "quad_default_cfg", "quad_create", "quad_seed", "quad_reset", "quad_step", "quad_step_range", "quad_observe", "quad_terminated", "quad_step_random",
               "quad_random_actions", "quad_get_state", "quad_set_state", "quad_gae",

@@ -15,6 +15,9 @@
   * ``ctrl_act`` / ``ctrl_episode``  ``pid_act`` / ``pid_episode`` for any law of ``LAWS``
                       (``quad_ctrl_act`` / ``quad_ctrl_episode``).
 
+  * ``ctrl_waypoints``  waypoint laps for any law in one launch (``quad_ctrl_waypoints``): the course of
+                      ``waypoints.WaypointCourse`` after its ``begin``.
+
 ``QuadVecEnv.pid_act`` / ``pid_episode`` / ``ctrl_act`` / ``ctrl_episode`` are these functions bound as methods.
 """
 from __future__ import annotations
@@ -33,7 +36,7 @@ MODES = {"yaw_frame": N.PID_YAW_FRAME, "pid_controller": N.PID_YAW_FRAME, N.PID_
          "world_frame": N.PID_WORLD_FRAME, "pid_controller_world_frame": N.PID_WORLD_FRAME,
          N.PID_WORLD_FRAME: N.PID_WORLD_FRAME}
 STATUS = {N.PID_RUNNING: "running", N.PID_TERMINATED: "terminated", N.PID_TRUNCATED: "truncated",
-          N.PID_INVALID: "invalid"}
+          N.PID_INVALID: "invalid", N.PID_LAP: "lap"}
 
 # field -> (pid_gains.json section, key), in QuadPidGains order
 _JSON = (("kp_xy", "position_xy", "kp"), ("kd_xy", "position_xy", "kd"), ("ki_xy", "position_xy", "ki"),
@@ -353,5 +356,36 @@ def ctrl_episode(env, params: ParamsLike = None, set_of=None, law="se3", max_ste
     return res
 
 
+def ctrl_waypoints(env, course, params: ParamsLike = None, set_of=None, law="pid_world", max_steps: int = 5000,
+                   trace_envs: int = 0, state: Optional[torch.Tensor] = None) -> dict:
+    """quad_ctrl_waypoints: every env of a hover `env` whose tracker status is 0 flies (law -> env step ->
+    tracker) until it completes its lap, terminates, truncates or `max_steps` pass, in one launch. `course`: a
+    WaypointCourse after course.begin(env) (or an earlier run: the tracker carries on). Returns ctrl_episode's
+    metric tensors (status PID_LAP where the lap was completed); with trace_envs = M > 0 also "actions",
+    "state12", "rewards" [T, M] and "flown_wp" [T, M] (the waypoint each step flew toward). The tracker arrays
+    are course.tracker."""
+    n, dev = env.num_envs, env.device
+    T, M = int(max_steps), int(trace_envs)
+    tab = param_table(params, dev)
+    so = _set_of(set_of, n, dev)
+    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+    if M > 0 and T > 0:
+        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
+        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
+        res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
+        res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
+    if state is not None:
+        env._check(state, (N.CTRL_NSTATE, n), torch.float64)
+    run = N.QuadCtrlRun(params=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
+                        law=LAWS[law], max_steps=T, trace_envs=M, state=None if state is None else state.data_ptr(),
+                        trace_actions=res["actions"].data_ptr() if "actions" in res else None,
+                        trace_state12=res["state12"].data_ptr() if "state12" in res else None,
+                        metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
+    wr = course.run(res.get("rewards"), res.get("flown_wp"))
+    N.check(N.lib().quad_ctrl_waypoints(env._h, C.byref(run), C.byref(wr), env._stream()), "quad_ctrl_waypoints")
+    return res
+
+
 __all__ = ["PIDGains", "gain_table", "pid_act", "pid_episode", "pid_score", "target_info", "gains_from_vector",
-           "MODES", "STATUS", "CtrlParams", "LAWS", "param_table", "params_from_vector", "ctrl_act", "ctrl_episode"]
+           "MODES", "STATUS", "CtrlParams", "LAWS", "param_table", "params_from_vector", "ctrl_act", "ctrl_episode",
+           "ctrl_waypoints"]

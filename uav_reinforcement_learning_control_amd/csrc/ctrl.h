@@ -19,4 +19,8 @@ hipError_t launch_ctrl_act(const PidPlant& plant, const QuadCtrlParams* params, 
 hipError_t launch_ctrl_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec,
                                const PidPlant& plant, const QuadCtrlRun& r, hipStream_t s);
 
+// k_ctrl_waypoints<law, spec> over all envs of kp (hover kind)
+hipError_t launch_ctrl_waypoints(const KConsts<float>* kc, const KParams& kp, bool spec, const PidPlant& plant,
+                                 const QuadCtrlRun& r, const QuadWaypointRun& wr, hipStream_t s);
+
 }  // namespace quadenv

@@ -6,6 +6,9 @@
 //                                   env in 64-thread blocks, env loaded once, (law -> env_step) up to
 //                                   max_steps times with the env, the eight controller states, the
 //                                   parameter set and the metric accumulators in registers, one store
+//   k_ctrl_waypoints<LAW, SPEC>     the same body with the waypoint tracker (quad_waypoints.h) after every
+//                                   step: hover kind, (law -> env_step -> tracker) until the tracker's
+//                                   status leaves 0 (quad_ctrl_waypoints)
 //
 // The law is a template argument, so each instantiation keeps only its own law's parameters and state
 // rows live: the SMC rows 6-7 of the state block are loaded and stored by the SMC instantiation alone.
@@ -18,6 +21,7 @@
 #include "kconsts_default.h"
 #include "quad_ctrl.h"
 #include "quad_physics.h"
+#include "quad_waypoints.h"
 
 using namespace quadenv;
 
@@ -82,9 +86,18 @@ __device__ __forceinline__ void store_metrics(const QuadPidMetrics& o, int i, co
   o.yaw_rate_delta_sum[i] = m.yr_delta;
 }
 
-template <int KIND, int LAW>
+// the metric status of a tracker status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
+__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
+  return tracker_status == 1 ? QUAD_PID_LAP
+                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
+                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
+}
+
+// WP: the waypoint tracker runs after every step and ends the env's run (wr: the kernel's QuadWaypointRun;
+// never read otherwise)
+template <int KIND, int LAW, bool WP>
 __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const KParams& p, const PidPlant& plant,
-                                                  const QuadCtrlRun& r) {
+                                                  const QuadCtrlRun& r, const QuadWaypointRun* wr) {
   const int i = blockIdx.x * EP_BLOCK + threadIdx.x;
   if (i >= p.n) return;
   PidAcc m;
@@ -94,6 +107,19 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
     return;
   }
   const QuadCtrlParams C = r.params[set];
+  WpTrack tk = {};
+  const double* wp = nullptr;
+  int cnt = 1;
+  if constexpr (WP) {
+    tk = load_track(wr->s, i);
+    if (tk.status != 0) {  // finished in an earlier run: no step, env and tracker as they are
+      store_metrics(r.metrics, i, m, metric_status_of(tk.status));
+      return;
+    }
+    const int ws = wr->w.set_of ? wr->w.set_of[i] : 0;
+    cnt = wr->w.counts[ws];
+    wp = wr->w.points + size_t(ws) * wr->w.max_points * 3;
+  }
   EnvRegs<float> e;
   load_env(p, i, e, false);
   const uint32_t ep = Tiles(p).ldu(F_EP, env_off(uint32_t(i)));
@@ -115,6 +141,15 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
     env_step<float, false>(K, e, a, sr);
 #pragma unroll
     for (int j = 0; j < 12; j++) s12[j] = sr.state12[j];
+    int flown = 0;
+    if constexpr (WP) {
+      flown = tk.wp_idx;
+      float nt[3];
+      if (wp_update(wp, cnt, wr->w.reach_radius, s12, sr.reward, sr.term, sr.trunc, tk, nt)) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) e.target[j] = nt[j];
+      }
+    }
     target_info_of<KIND>(K, p, i, e, ep, ti);
     pid_acc_step(m, s12, tgt, sr.reward);
     if (traced) {
@@ -126,8 +161,17 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
           sto(reinterpret_cast<float4*>(r.trace_state12), 48u * row + 16u * j,
               make_float4(s12[4 * j], s12[4 * j + 1], s12[4 * j + 2], s12[4 * j + 3]));
       }
+      if constexpr (WP) {
+        if (wr->trace_reward) sto(wr->trace_reward, 4u * row, sr.reward);
+        if (wr->trace_wp_idx) sto(wr->trace_wp_idx, 4u * row, int32_t(flown));
+      }
     }
-    if (sr.term || sr.trunc) {
+    if constexpr (WP) {
+      if (tk.status != 0) {
+        status = metric_status_of(tk.status);
+        break;
+      }
+    } else if (sr.term || sr.trunc) {
       status = sr.term ? QUAD_PID_TERMINATED : QUAD_PID_TRUNCATED;
       break;
     }
@@ -138,6 +182,7 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
     for (int j = 0; j < ROWS; j++) r.state[size_t(j) * size_t(p.n) + size_t(i)] = cs[j];
   }
   store_metrics(r.metrics, i, m, status);
+  if constexpr (WP) store_track(wr->s, i, tk);
 }
 
 template <int KIND, int LAW, bool SPEC>
@@ -146,9 +191,23 @@ __global__ __launch_bounds__(EP_BLOCK) void k_ctrl_episode(const KConsts<float>*
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, false>();
-    ctrl_episode_body<KIND, LAW>(K, p, plant, r);
+    ctrl_episode_body<KIND, LAW, false>(K, p, plant, r, nullptr);
   } else {
-    ctrl_episode_body<KIND, LAW>(*kc, p, plant, r);
+    ctrl_episode_body<KIND, LAW, false>(*kc, p, plant, r, nullptr);
+  }
+}
+
+// the WP form of k_ctrl_episode: hover kind only (a switch overwrites the target register), the tracker's
+// tables and rows in a kernel argument of its own so k_ctrl_episode's arguments stay as they are
+template <int LAW, bool SPEC>
+__global__ __launch_bounds__(EP_BLOCK) void k_ctrl_waypoints(const KConsts<float>* __restrict__ kc, KParams p,
+                                                             PidPlant plant, QuadCtrlRun r, QuadWaypointRun wr) {
+  p.kc = kc;
+  if constexpr (SPEC) {
+    constexpr KConsts<float> K = kdef_block<QUAD_ENV_HOVER, false>();
+    ctrl_episode_body<QUAD_ENV_HOVER, LAW, true>(K, p, plant, r, &wr);
+  } else {
+    ctrl_episode_body<QUAD_ENV_HOVER, LAW, true>(*kc, p, plant, r, &wr);
   }
 }
 
@@ -186,6 +245,18 @@ hipError_t launch_ctrl_episode(const KConsts<float>* kc, const KParams& kp, int 
     with_kind(env_kind == QUAD_ENV_TRAJ, spec, [&](auto kind, auto sp) {
       hipLaunchKernelGGL((k_ctrl_episode<decltype(kind)::value, decltype(lw)::value, decltype(sp)::value>), grid, blk,
                          0, s, kc, kp, plant, r);
+    });
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_ctrl_waypoints(const KConsts<float>* kc, const KParams& kp, bool spec, const PidPlant& plant,
+                                 const QuadCtrlRun& r, const QuadWaypointRun& wr, hipStream_t s) {
+  const dim3 grid((kp.n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
+  with_law(r.law, [&](auto lw) {
+    with_bool(spec, [&](auto sp) {
+      hipLaunchKernelGGL((k_ctrl_waypoints<decltype(lw)::value, decltype(sp)::value>), grid, blk, 0, s, kc, kp, plant,
+                         r, wr);
     });
   });
   return hipGetLastError();

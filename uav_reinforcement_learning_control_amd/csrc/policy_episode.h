@@ -33,4 +33,12 @@ hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const
 hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
                                  int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s);
 
+// the block shape of both fused policy launches for n envs: tiles per wave (1 / 2), envs per block (64 / 256)
+void episode_block_shape(int32_t n, int& nt, int& eb);
+
+// k_policy_waypoints<ctbr, ., spec, obs_mode> over all envs of kp (hover kind)
+hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
+                                   const float* packed, const EpisodeArgs& a, const QuadWaypointRun& wr,
+                                   hipStream_t s);
+
 }  // namespace quadenv

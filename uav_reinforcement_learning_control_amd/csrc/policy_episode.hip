@@ -22,8 +22,13 @@
 //   * A wave leaves the loop when none of its lanes runs, and the waves of a block leave at different
 //     steps, so after the staging barriers the loop holds no block-wide barrier.
 //
-// This file is compiled once per env kind (-DPE_KIND=0 hover / 1 trajectory): the two objects build in
-// parallel, each with its own instantiations.
+// k_policy_waypoints is the same body with the waypoint tracker (quad_waypoints.h) after every committed step
+// (WP): hover kind, the tracker's status ends an env's run, the deployed observation is rebuilt with the
+// target the tracker has just written (quad_policy_waypoints).
+//
+// This file is compiled once per env kind (-DPE_KIND=0 hover / 1 trajectory) and once more for the hover
+// kind's waypoint instantiations (-DPE_KIND=2): the three objects build in parallel, each with its own
+// instantiations.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -38,13 +43,16 @@
 #include "quad_deploy.h"
 #include "quad_physics.h"
 #include "quad_pid.h"
+#include "quad_waypoints.h"
 
 #ifndef PE_KIND
-#error "compile with -DPE_KIND=0 (hover) or 1 (trajectory)"
+#error "compile with -DPE_KIND=0 (hover), 1 (trajectory) or 2 (hover, waypoint laps)"
 #endif
+#define PE_WP (PE_KIND == 2)
 
 namespace quadenv {
 
+#if !PE_WP
 // one env kind's instantiations (this translation unit's)
 template <int KIND>
 hipError_t launch_episode_kind(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
@@ -54,6 +62,7 @@ template <>  // the trajectory kind's: the other object of this file
 hipError_t launch_episode_kind<QUAD_ENV_TRAJ>(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec,
                                               int obs_mode, int nt, int eb, const float* packed, const EpisodeArgs& a,
                                               hipStream_t s);
+#endif
 #endif
 
 namespace {
@@ -83,9 +92,18 @@ __device__ __forceinline__ void store_row12(float* base, uint32_t row, const flo
 // NT = 2: wave w of a block owns envs 64w .. 64w + 63 = its two MFMA tiles. NT = 1: wave w owns the 32
 // envs 32w .. 32w + 31; lanes l and l + 32 both carry env l & 31 (the same bits), the lower half stores.
 // EB: envs per block (256: k_rollout's shape; 64: one or two waves, for evaluation-sized batches).
-template <int KIND, bool CTBR, int NT, int MODE, int EB>
+// the metric status of a tracker status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
+__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
+  return tracker_status == 1 ? QUAD_PID_LAP
+                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
+                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
+}
+
+// WP: the waypoint tracker runs after every committed step and ends the env's run (wr: the kernel's
+// QuadWaypointRun; never read otherwise)
+template <int KIND, bool CTBR, int NT, int MODE, int EB, bool WP>
 __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KParams& p, const float* __restrict__ packed,
-                                             const EpisodeArgs& a) {
+                                             const EpisodeArgs& a, const QuadWaypointRun* wr) {
   constexpr int BLK = EB * 2 / NT;
   extern __shared__ float lds[];
   const int w = threadIdx.x >> 6;
@@ -115,15 +133,35 @@ __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KPar
   observe(K, e, ob, s12);  // what quad_observe reports
   target_info_of<KIND>(K, p, i, e, ep, ti);
   double vel[3];
-  vel_est_update(alpha, a.est.max_dt, s12, double(e.step) * a.est_dt, est, vel);
+  WpTrack tk = {};
+  const double* wp = nullptr;
+  int cnt = 1;
+  int32_t status = QUAD_PID_RUNNING;
+  bool run = true;
+  if constexpr (WP) {
+    tk = load_track(wr->s, i);
+    const int ws = wr->w.set_of ? wr->w.set_of[i] : 0;
+    cnt = wr->w.counts[ws];
+    wp = wr->w.points + size_t(ws) * wr->w.max_points * 3;
+    run = tk.status == 0;  // finished in an earlier run: no step, env, estimator and tracker as they are
+    status = metric_status_of(tk.status);
+    // a resumed run: the estimator already holds this instant's sample (a second one, dt = 0, would restart it)
+    const double ts = double(e.step) * a.est_dt;
+    if (run && !(est[7] != 0.0 && est[3] == ts)) {
+      vel_est_update(alpha, a.est.max_dt, s12, ts, est, vel);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 3; j++) vel[j] = est[4 + j];
+    }
+  } else {
+    vel_est_update(alpha, a.est.max_dt, s12, double(e.step) * a.est_dt, est, vel);
+  }
   if (MODE == QUAD_OBS_DEPLOYED) deploy_obs(K.obs_lo, K.obs_span, K.obs_rspan, s12, e.target, vel, ob);
 
   PidAcc m;
   double verr = 0.0;
   const uint32_t M = uint32_t(a.trace_envs);
   const bool traced = owner && uint32_t(i) < M;
-  int32_t status = QUAD_PID_RUNNING;
-  bool run = true;
   for (int t = 0; t < a.max_steps; t++) {
     if (!__any(run)) break;  // wave-uniform: the whole wave leaves together
     // ---- policy: the actor on the wave's tile(s), full wave (frozen lanes feed their columns too)
@@ -159,6 +197,15 @@ __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KPar
       e = en;
 #pragma unroll
       for (int j = 0; j < 12; j++) { s12[j] = r.state12[j]; ob[j] = r.obs[j]; }
+      int flown = 0;
+      if constexpr (WP) {  // the env's observation above keeps the target the step was flown with
+        flown = tk.wp_idx;
+        float nt[3];
+        if (wp_update(wp, cnt, wr->w.reach_radius, s12, r.reward, r.term, r.trunc, tk, nt)) {
+#pragma unroll
+          for (int j = 0; j < 3; j++) e.target[j] = nt[j];
+        }
+      }
       target_info_of<KIND>(K, p, i, e, ep, ti);
       pid_acc_step(m, s12, tgt, r.reward);
       vel_est_update(alpha, a.est.max_dt, s12, double(e.step) * a.est_dt, est, vel);
@@ -175,8 +222,17 @@ __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KPar
 #pragma unroll
           for (int j = 0; j < 3; j++) sto(a.trace_vel_est, 12u * row + 4u * j, float(vel[j]));
         }
+        if constexpr (WP) {
+          if (wr->trace_reward) sto(wr->trace_reward, 4u * row, r.reward);
+          if (wr->trace_wp_idx) sto(wr->trace_wp_idx, 4u * row, int32_t(flown));
+        }
       }
-      if (r.term || r.trunc) {
+      if constexpr (WP) {
+        if (tk.status != 0) {
+          status = metric_status_of(tk.status);
+          run = false;
+        }
+      } else if (r.term || r.trunc) {
         status = r.term ? QUAD_PID_TERMINATED : QUAD_PID_TRUNCATED;
         run = false;
       }
@@ -191,6 +247,7 @@ __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KPar
     }
     store_metrics(a.metrics, i, m, status);
     if (a.vel_err_sq) a.vel_err_sq[i] = verr;
+    if constexpr (WP) store_track(wr->s, i, tk);
   }
 }
 
@@ -201,12 +258,46 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_policy_episode(const KConsts<fl
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
-    episode_body<KIND, CTBR, NT, MODE, EB>(K, p, packed, a);
+    episode_body<KIND, CTBR, NT, MODE, EB, false>(K, p, packed, a, nullptr);
   } else {
-    episode_body<KIND, CTBR, NT, MODE, EB>(*kc, p, packed, a);
+    episode_body<KIND, CTBR, NT, MODE, EB, false>(*kc, p, packed, a, nullptr);
   }
 }
 
+#if PE_WP
+// the WP form of k_policy_episode: hover kind only (a switch overwrites the target register), the tracker's
+// tables and rows in a kernel argument of its own so k_policy_episode's arguments stay as they are
+template <bool CTBR, int NT, bool SPEC, int MODE, int EB>
+__global__ __launch_bounds__(EB * 2 / NT) void k_policy_waypoints(const KConsts<float>* __restrict__ kc, KParams p,
+                                                                  const float* __restrict__ packed, EpisodeArgs a,
+                                                                  QuadWaypointRun wr) {
+  p.kc = kc;
+  if constexpr (SPEC) {
+    constexpr KConsts<float> K = kdef_block<QUAD_ENV_HOVER, CTBR>();
+    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(K, p, packed, a, &wr);
+  } else {
+    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(*kc, p, packed, a, &wr);
+  }
+}
+
+template <bool CTBR, int NT, bool SPEC, int MODE, int EB>
+hipError_t launch_wp(const KConsts<float>* kc, const KParams& kp, const float* packed, const EpisodeArgs& a,
+                     const QuadWaypointRun& wr, hipStream_t s) {
+  static bool opted[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  const int bytes = LDS_F * int(sizeof(float));
+  if (!opted[dev]) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_waypoints<CTBR, NT, SPEC, MODE, EB>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    opted[dev] = true;
+  }
+  hipLaunchKernelGGL((k_policy_waypoints<CTBR, NT, SPEC, MODE, EB>), dim3((kp.n + EB - 1) / EB), dim3(EB * 2 / NT),
+                     bytes, s, kc, kp, packed, a, wr);
+  return hipGetLastError();
+}
+#else
 template <int KIND, bool CTBR, int NT, bool SPEC, int MODE, int EB>
 hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* packed, const EpisodeArgs& a,
                   hipStream_t s) {
@@ -225,6 +316,7 @@ hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* pack
                      dim3(EB * 2 / NT), bytes, s, kc, kp, packed, a);
   return hipGetLastError();
 }
+#endif
 
 #if PE_KIND == 0
 constexpr int DEPLOY_BLOCK = 256;
@@ -260,6 +352,26 @@ __global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float
 
 }  // namespace
 
+#if PE_WP
+// quad_policy_waypoints' launch: launch_policy_episode's block-shape rule (below, in the hover object)
+hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
+                                   const float* packed, const EpisodeArgs& a, const QuadWaypointRun& wr,
+                                   hipStream_t s) {
+  int nt, eb;
+  episode_block_shape(kp.n, nt, eb);
+  return with_bool(ctbr, [&](auto cb) {
+    return with_bool(spec, [&](auto sp) {
+      return with_bool(obs_mode == QUAD_OBS_DEPLOYED, [&](auto dm) {
+        constexpr bool CB = decltype(cb)::value, SP = decltype(sp)::value;
+        constexpr int MD = decltype(dm)::value ? QUAD_OBS_DEPLOYED : QUAD_OBS_ENV;
+        if (nt == 1) return launch_wp<CB, 1, SP, MD, 64>(kc, kp, packed, a, wr, s);
+        return eb == 64 ? launch_wp<CB, 2, SP, MD, 64>(kc, kp, packed, a, wr, s)
+                        : launch_wp<CB, 2, SP, MD, 256>(kc, kp, packed, a, wr, s);
+      });
+    });
+  });
+}
+#else
 template <>
 hipError_t launch_episode_kind<PE_KIND>(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
                                         int nt, int eb, const float* packed, const EpisodeArgs& a, hipStream_t s) {
@@ -278,6 +390,7 @@ hipError_t launch_episode_kind<PE_KIND>(const KConsts<float>* kc, const KParams&
     });
   });
 }
+#endif
 
 #if PE_KIND == 0
 hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const float* state12, const float* target3,
@@ -293,13 +406,17 @@ hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const
 // computes the same bits. QUADENV_ROLLOUT_NT = 1 / 2 and QUADENV_EPISODE_BLOCK = 64 / 256 pin them (A/B, tests);
 // NT = 1 always takes 64-env blocks (launch_episode_kind).
 constexpr int EPISODE_WIDE_N = 16384;
+void episode_block_shape(int32_t n, int& nt, int& eb) {
+  const bool wide = n > EPISODE_WIDE_N;
+  const char* v = std::getenv("QUADENV_ROLLOUT_NT");
+  nt = v && std::atoi(v) == 1 ? 1 : (v && std::atoi(v) == 2 ? 2 : (wide ? 2 : 1));
+  const char* b = std::getenv("QUADENV_EPISODE_BLOCK");
+  eb = b && std::atoi(b) == 64 ? 64 : (b && std::atoi(b) == 256 ? 256 : (wide ? 256 : 64));
+}
 hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
                                  int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s) {
-  const bool wide = kp.n > EPISODE_WIDE_N;
-  const char* v = std::getenv("QUADENV_ROLLOUT_NT");
-  const int nt = v && std::atoi(v) == 1 ? 1 : (v && std::atoi(v) == 2 ? 2 : (wide ? 2 : 1));
-  const char* b = std::getenv("QUADENV_EPISODE_BLOCK");
-  const int eb = b && std::atoi(b) == 64 ? 64 : (b && std::atoi(b) == 256 ? 256 : (wide ? 256 : 64));
+  int nt, eb;
+  episode_block_shape(kp.n, nt, eb);
   return env_kind == QUAD_ENV_TRAJ
              ? launch_episode_kind<QUAD_ENV_TRAJ>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s)
              : launch_episode_kind<QUAD_ENV_HOVER>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s);

@@ -41,6 +41,7 @@
 #include "ctrl.h"
 #include "pid.h"
 #include "policy_episode.h"
+#include "quad_waypoints.h"
 #include "rollout.h"
 
 using namespace quadenv;
@@ -846,15 +847,17 @@ __global__ __launch_bounds__(BLOCK) void k_waypoints_begin(KParams p, QuadWaypoi
   const int set = w.set_of ? w.set_of[i] : 0;
   const int cnt = w.counts[set];
   const double* wp = w.points + size_t(set) * w.max_points * 3;
-  const int nxt = 1 % cnt;
+  WpTrack tr;
+  float pos0[3], tgt[3];
+  wp_begin(wp, cnt, tr, pos0, tgt);
   const Tiles S(p);
   const uint32_t vo = env_off(uint32_t(i));
 #pragma unroll
   for (int j = 0; j < 3; j++) {
-    S.st(F_QPOS + j, vo, float(wp[j]));
+    S.st(F_QPOS + j, vo, pos0[j]);
     S.st(F_QVEL + j, vo, 0.f);
     S.st(F_QVEL + 3 + j, vo, 0.f);
-    S.st(F_TGT + j, vo, float(wp[3 * nxt + j]));  // waypoints[i].astype(np.float32)
+    S.st(F_TGT + j, vo, tgt[j]);  // waypoints[i].astype(np.float32)
     S.st(F_RINT + j, vo, 0.f);
   }
   S.st(F_QPOS + 3, vo, 1.f);
@@ -862,12 +865,7 @@ __global__ __launch_bounds__(BLOCK) void k_waypoints_begin(KParams p, QuadWaypoi
   S.st(F_QPOS + 5, vo, 0.f);
   S.st(F_QPOS + 6, vo, 0.f);
   S.stu(F_STEP, vo, 0u);
-  t.wp_idx[i] = nxt;
-  t.reached[i] = 0;
-  t.laps[i] = 0;
-  t.steps[i] = 0;
-  t.status[i] = 0;
-  t.total_reward[i] = 0.0;
+  store_track(t, i, tr);
   EnvRegs<float> e;
   load_env(p, i, e, false);
   float obs[12], s12[12];
@@ -893,33 +891,16 @@ __global__ __launch_bounds__(BLOCK) void k_waypoints_update(KParams p, QuadWaypo
   const int set = w.set_of ? w.set_of[i] : 0;
   const int cnt = w.counts[set];
   const double* wp = w.points + size_t(set) * w.max_points * 3;
-  t.total_reward[i] += double(rew[i]);
-  t.steps[i] += 1;
-  int k = t.wp_idx[i];
   // dist_to_wp = float(np.linalg.norm(drone_pos - current_target)): float32 pos minus the
-  // float64 waypoint, norm in float64
-  double d2 = 0.0;
+  // float64 waypoint, norm in float64 (wp_update, quad_waypoints.h)
+  WpTrack tr = load_track(t, i);
+  const float pos[3] = {s12[size_t(i) * 12], s12[size_t(i) * 12 + 1], s12[size_t(i) * 12 + 2]};
+  float tgt[3];
+  if (wp_update(wp, cnt, w.reach_radius, pos, rew[i], term[i] != 0, trunc[i] != 0, tr, tgt)) {
 #pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const double d = double(s12[size_t(i) * 12 + j]) - wp[3 * k + j];
-    d2 += d * d;
+    for (int j = 0; j < 3; j++) Tiles(p).st(F_TGT + j, env_off(uint32_t(i)), tgt[j]);
   }
-  int status = 0;
-  if (sqrt(d2) < double(w.reach_radius)) {
-    t.reached[i] += 1;
-    k = (k + 1) % cnt;
-    t.wp_idx[i] = k;
-    if (k == 0) {
-      t.laps[i] += 1;
-      status = 1;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 3; j++) Tiles(p).st(F_TGT + j, env_off(uint32_t(i)), float(wp[3 * k + j]));
-    }
-  }
-  if (status == 0 && term[i]) status = 2;
-  else if (status == 0 && trunc[i]) status = 3;
-  t.status[i] = status;
+  store_track(t, i, tr);
 }
 
 // quad_get_state / quad_set_state: the dense [fields][N] pieces of QuadStateSoA <-> the tiles
@@ -1444,6 +1425,79 @@ int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun*
                 r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
   HIP_TRY(launch_policy_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode,
                                 packed, a, static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- waypoint laps in one launch (kernels: k_ctrl_waypoints, k_policy_waypoints)
+static bool metrics_complete(const QuadPidMetrics& m) {
+  return m.steps && m.status && m.total_reward && m.pos_err_sum && m.pos_err_sq && m.pos_err_max &&
+         m.yaw_rate_abs_sum && m.yaw_rate_sum && m.yaw_rate_sq && m.yaw_rate_abs_max && m.yaw_rate_sign_changes &&
+         m.yaw_rate_delta_sum;
+}
+
+// what both lap calls ask of the handle and of the tracker; the wrapper is the caller's to check
+static int check_waypoint_run(const QuadHandle* h, const char* who, const QuadWaypointRun* wr) {
+  const std::string w(who);
+  if (h->cfg.env_kind != QUAD_ENV_HOVER)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER (a switch overwrites the target register)");
+  if (!wr->w.points || !wr->w.counts || wr->w.max_points < 1) return fail(QUAD_EINVAL, w + ": waypoint table is empty");
+  if (!(wr->w.reach_radius >= 0.f)) return fail(QUAD_EINVAL, w + ": reach_radius must be >= 0");
+  const QuadWaypointState& s = wr->s;
+  if (!s.wp_idx || !s.reached || !s.laps || !s.steps || !s.status || !s.total_reward)
+    return fail(QUAD_EINVAL, w + ": waypoint tracker arrays are required");
+  return QUAD_OK;
+}
+
+int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointRun* wr, void* stream) {
+  if (!h || !r || !wr) return fail(QUAD_EINVAL, "handle/run/waypoints is NULL");
+  if (int rc = check_waypoint_run(h, "quad_ctrl_waypoints", wr)) return rc;
+  if (int rc = check_ctrl(h, "quad_ctrl_waypoints", r->params, r->n_sets, r->law)) return rc;
+  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: max_steps must be >= 1");
+  if (!metrics_complete(r->metrics)) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: trace_envs must be in [0, N]");
+  const bool any_trace = r->trace_actions || r->trace_state12 || wr->trace_reward || wr->trace_wp_idx;
+  if (any_trace && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
+      return fail(QUAD_EINVAL, "quad_ctrl_waypoints: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
+      return fail(QUAD_EINVAL, "quad_ctrl_waypoints: traces must be 16-byte aligned");
+  }
+  DeviceGuard g(h->device);
+  QuadCtrlRun run = *r;
+  if (!any_trace) run.trace_envs = 0;
+  HIP_TRY(launch_ctrl_waypoints(h->kdev, h->kp, h->spec, make_pid_plant(h->cfg), run, *wr,
+                                static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_policy_waypoints(QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
+                          void* stream) {
+  if (!h || !packed || !r || !wr) return fail(QUAD_EINVAL, "handle/packed/run/waypoints is NULL");
+  if (int rc = check_waypoint_run(h, "quad_policy_waypoints", wr)) return rc;
+  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_policy_waypoints: the policy takes 12-D obs (no RELPOS)");
+  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED)
+    return fail(QUAD_EINVAL, "quad_policy_waypoints: unknown obs_mode");
+  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_policy_waypoints: max_steps must be >= 1");
+  if (!metrics_complete(r->metrics)) return fail(QUAD_EINVAL, "quad_policy_waypoints: every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_policy_waypoints: trace_envs must be in [0, N]");
+  if (int rc = check_est(&r->est, "quad_policy_waypoints")) return rc;
+  if (!(r->est_dt > 0.0)) return fail(QUAD_EINVAL, "quad_policy_waypoints: est_dt must be > 0");
+  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || wr->trace_reward ||
+                         wr->trace_wp_idx;
+  if (any_trace && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
+      return fail(QUAD_EINVAL, "quad_policy_waypoints: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
+         reinterpret_cast<uintptr_t>(r->trace_obs)) & 15u)
+      return fail(QUAD_EINVAL, "quad_policy_waypoints: the action, state12 and obs traces must be 16-byte aligned");
+  }
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return fail(QUAD_EINVAL, "quad_policy_waypoints: packed must be 16-byte aligned");
+  DeviceGuard g(h->device);
+  EpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0,
+                EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
+                r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
+  HIP_TRY(launch_policy_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode, packed, a, *wr,
+                                  static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

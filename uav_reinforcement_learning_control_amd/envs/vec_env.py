@@ -260,6 +260,11 @@ class QuadVecEnv:
         from .. import controllers
         return controllers.ctrl_episode(self, params, set_of, law, max_steps, trace_envs, state)
 
+    def ctrl_waypoints(self, course, params=None, set_of=None, law="pid_world", max_steps: int = 5000,
+                       trace_envs: int = 0, state=None) -> dict:
+        from .. import controllers
+        return controllers.ctrl_waypoints(self, course, params, set_of, law, max_steps, trace_envs, state)
+
     # the deployed observation path (policy_node.py's velocity estimator and observation builder)
     def deploy_obs(self, state12: torch.Tensor, target3: torch.Tensor, timestamp: float, est_state: torch.Tensor,
                    alpha=None, alpha_all: float = 0.8, max_dt: float = 0.1, out: Optional[torch.Tensor] = None,

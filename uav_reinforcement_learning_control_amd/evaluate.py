@@ -8,8 +8,12 @@ waypoint lap (:440-612). Here N evaluations run at once on the GPU:
     termination or truncation; per-episode return and length (the reference's summary).
   * ``evaluate_waypoints`` -- N waypoint laps in parallel (one waypoint set per env, e.g. the
     eight / circle / square generators at several spacings); the bookkeeping -- reward sum, step
-    count, waypoint switching within ``reach_radius``, lap completion, target update -- is the
-    ``quad_waypoints_update`` kernel after each step.
+    count, waypoint switching within ``reach_radius``, lap completion, target update -- runs inside
+    the fused ``quad_policy_waypoints`` launch (12-D observations, hover env), else it is the
+    ``quad_waypoints_update`` kernel after each step of the loop. ``evaluate_ctrl_waypoints`` flies the
+    same courses with a classical law (``quad_ctrl_waypoints``), ``compare_pair(..., trajectories=...)``
+    any two fliers on identical courses (``--trajectory ... --controller lqr``, ``--trajectory ...
+    --compare pid model``, ``--trajectory ... --deployed``).
 
   * ``evaluate_pid_episodes`` -- the same N episodes flown by the cascaded PID baseline
     (``controllers.py``; one fused launch), and ``compare_controllers`` -- a policy and the PID on the
@@ -100,38 +104,73 @@ def _waypoint_sets(trajectories, spacings) -> list:
     return sets
 
 
+def _lap_extras(out: dict, sets, n: int, m: Optional[dict]) -> dict:
+    out["name"] = np.array([sets[i % len(sets)][0] for i in range(n)])
+    out["n_waypoints"] = np.array([len(sets[i % len(sets)][1]) for i in range(n)])
+    if m is not None:
+        out["metrics"] = m
+        out["pos_errors"] = m["pos_err_sum"] / np.maximum(m["steps"], 1)
+    return out
+
+
+def _lap_record(out: dict, m: dict) -> None:
+    """record=True from the fused traces: rows up to the longest flight; rows past an env's last step are zero."""
+    T = max(int(out["steps"].max()), 1)
+    out["positions"] = m.pop("state12")[:T, :, :3].copy()
+    out["actions"] = m.pop("actions")[:T]
+    out["rewards"] = m.pop("rewards")[:T]
+    out["flown_wp"] = m.pop("flown_wp")[:T]
+
+
 @torch.no_grad()
 def evaluate_waypoints(model, trajectories: Sequence = ("eight",), spacings: Sequence[float] = (0.5,),
                        reach_radius: float = 0.25, max_steps: int = 5000, replicas: int = 1,
                        wrapper: Optional[str] = "auto", env: str = "hover", device="cuda",
-                       seed: int = 0, record: bool = False) -> dict:
+                       seed: int = 0, record: bool = False, fused: Optional[bool] = None, obs_mode: str = "env",
+                       velocity_alpha: Optional[float] = None) -> dict:
     """One lap per (waypoint set x replica) env, all at once. Returns per-env numpy arrays
     (name, steps, reached, laps, status, total_reward; with record=True also positions /
-    actions / rewards [T, N, ...]) -- status 1 = lap completed, 2 = terminated, 3 = max steps."""
+    actions / rewards [T, N, ...]) -- status 1 = lap completed, 2 = terminated, 3 = max steps.
+    `fused`: None flies the laps in one quad_policy_waypoints launch where that is supported (a 12-128-128-4
+    policy on a hover env with 12-D observations), else in the per-step loop; both give the same bits for
+    every env up to its last step (the loop goes on stepping a finished env, the launch freezes it and leaves
+    its later record rows zero). The launch adds "metrics" (the QuadPidMetrics arrays and vel_err_sq) and
+    "pos_errors"; obs_mode="deployed" (fused only) feeds the policy the ROS2 node's observation, velocity
+    estimated with `velocity_alpha` (default 0.8)."""
+    from .ppo.fused import FusedPolicy, waypoints_supported
+    from .waypoints import WaypointCourse
     device = torch.device(device)
     policy, cfg_wrapper = load_policy(model, device)
     wrapper = cfg_wrapper if wrapper == "auto" else wrapper
     sets = _waypoint_sets(trajectories, spacings)
     n = len(sets) * replicas
-    maxp = max(len(p) for _, p in sets)
-    pts = np.zeros((len(sets), maxp, 3), np.float64)
-    for k, (_, p) in enumerate(sets):
-        pts[k, :len(p)] = p
-    points = torch.from_numpy(pts).to(device)
-    counts = torch.tensor([len(p) for _, p in sets], dtype=torch.int32, device=device)
-    set_of = (torch.arange(n, device=device, dtype=torch.int32) % len(sets)).contiguous()
-    w = N.QuadWaypoints(points=points.data_ptr(), counts=counts.data_ptr(), set_of=set_of.data_ptr(),
-                        max_points=maxp, reach_radius=float(reach_radius))
-    trk = {k: torch.zeros(n, dtype=torch.int32, device=device) for k in ("wp_idx", "reached", "laps", "steps", "status")}
-    trk["total_reward"] = torch.zeros(n, dtype=torch.float64, device=device)
-    st = N.QuadWaypointState(**{k: v.data_ptr() for k, v in trk.items()})
+    course = WaypointCourse([p for _, p in sets], n, reach_radius, device)
     e = QuadVecEnv(n, env=env, wrapper=wrapper, device=device, seed=seed,
                    max_episode_steps=max_steps, auto_reset=False)
     e.reset()
-    obs = torch.zeros(n, e.obs_dim, device=device)
-    L = N.lib()
-    N.check(L.quad_waypoints_begin(e._h, C.byref(w), C.byref(st), C.c_void_p(obs.data_ptr()), e._stream()),
-            "quad_waypoints_begin")
+    obs = course.begin(e)
+    if obs_mode not in ("env", "deployed"):
+        raise ValueError(f"obs_mode must be \"env\" or \"deployed\", got {obs_mode!r}")
+    ok = waypoints_supported(policy, e)
+    use = ok if fused is None else bool(fused)
+    if use and not ok:
+        raise ValueError("fused=True: quad_policy_waypoints flies 12-128-128-4 policies on hover envs with 12-D "
+                         "observations")
+    if obs_mode == "deployed" and not use:
+        raise ValueError("obs_mode=\"deployed\" runs in the fused launch only")
+    if use:
+        fp = FusedPolicy(policy)
+        fp.pack()
+        m = fp.waypoints(e, course, max_steps=max_steps, obs_mode=obs_mode, trace_envs=n if record else 0,
+                         alpha_all=0.8 if velocity_alpha is None else float(velocity_alpha))
+        torch.cuda.synchronize(device)
+        m = {k: v.cpu().numpy() for k, v in m.items()}
+        out = course.result()
+        if record:
+            _lap_record(out, m)
+            m.pop("obs"), m.pop("vel_est")
+        e.close()
+        return _lap_extras(out, sets, n, m)
     act = _Actor(policy, n, device)
     rec = {"positions": [], "actions": [], "rewards": []} if record else None
     for t in range(max_steps):
@@ -141,21 +180,67 @@ def evaluate_waypoints(model, trajectories: Sequence = ("eight",), spacings: Seq
             rec["positions"].append(info["state"][:, :3].clone())
             rec["actions"].append(a.clone())
             rec["rewards"].append(rew.clone())
-        N.check(L.quad_waypoints_update(e._h, C.byref(w), C.byref(st), C.c_void_p(info["state"].data_ptr()),
-                                        C.c_void_p(rew.data_ptr()), C.c_void_p(te.data_ptr()),
-                                        C.c_void_p(tr.data_ptr()), e._stream()), "quad_waypoints_update")
-        if (t + 1) % 128 == 0 and bool((trk["status"] != 0).all()):
+        course.update(e, info["state"], rew, te, tr)
+        if (t + 1) % 128 == 0 and bool((course.tracker["status"] != 0).all()):
             break
     torch.cuda.synchronize(device)
-    out = {k: v.cpu().numpy() for k, v in trk.items()}
-    out["name"] = np.array([sets[i % len(sets)][0] for i in range(n)])
-    out["n_waypoints"] = np.array([len(sets[i % len(sets)][1]) for i in range(n)])
+    out = _lap_extras(course.result(), sets, n, None)
     if rec is not None:
         out["positions"] = torch.stack(rec["positions"]).cpu().numpy()
         out["actions"] = torch.stack(rec["actions"]).cpu().numpy()
         out["rewards"] = torch.stack(rec["rewards"]).cpu().numpy()
     e.close()
     return out
+
+
+def _lap_law(law: str) -> str:
+    """A lap is trajectory following: "pid" is the world-frame PID, the reference's trajectory follower."""
+    return "pid_world" if law == "pid" else law
+
+
+@torch.no_grad()
+def evaluate_ctrl_waypoints(law: str, params=None, trajectories: Sequence = ("eight",),
+                            spacings: Sequence[float] = (0.5,), reach_radius: float = 0.25, max_steps: int = 5000,
+                            replicas: int = 1, device="cuda", seed: int = 0, record: bool = False) -> dict:
+    """evaluate_waypoints flown by a law of the controller family ("pid": the world-frame PID; "pid_yaw",
+    "se3", "smc", "lqr") in one quad_ctrl_waypoints launch, on the same courses (same sets, same env order).
+    `params`: a CtrlParams / PIDGains, a pid_gains.json-shaped path, or None. Returns evaluate_waypoints'
+    keys (name, n_waypoints, wp_idx, reached, laps, steps, status, total_reward), "metrics" (the
+    QuadPidMetrics arrays) and "pos_errors" (per-env mean position error against the target each step was
+    flown with); with record=True also positions / actions / rewards / flown_wp [T, N, ...]."""
+    from .controllers import CtrlParams, ctrl_waypoints
+    from .waypoints import WaypointCourse
+    device = torch.device(device)
+    if isinstance(params, str):
+        params = CtrlParams.from_json(params)
+    sets = _waypoint_sets(trajectories, spacings)
+    n = len(sets) * replicas
+    course = WaypointCourse([p for _, p in sets], n, reach_radius, device)
+    e = QuadVecEnv(n, env="hover", wrapper=None, device=device, seed=seed, max_episode_steps=max_steps,
+                   auto_reset=False)
+    e.reset()
+    course.begin(e)
+    m = ctrl_waypoints(e, course, params, law=_lap_law(law), max_steps=max_steps, trace_envs=n if record else 0)
+    torch.cuda.synchronize(device)
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    out = course.result()
+    if record:
+        _lap_record(out, m)
+    e.close()
+    return _lap_extras(out, sets, n, m)
+
+
+def lap_table(rows_in) -> str:
+    """One line per flier: status counts, mean steps, waypoints reached and mean position error."""
+    rows = [f"{'controller':>14} {'laps':>6} {'term.':>6} {'max steps':>9} {'running':>8} {'steps':>9} "
+            f"{'reached':>8} {'pos error':>10}"]
+    for name, r in rows_in:
+        st = np.asarray(r["status"])
+        pe = f"{float(np.mean(r['pos_errors'])):9.3f}m" if "pos_errors" in r else f"{'-':>10}"
+        rows.append(f"{name:>14} {int((st == 1).sum()):6d} {int((st == 2).sum()):6d} {int((st == 3).sum()):9d} "
+                    f"{int((st == 0).sum()):8d} {float(np.mean(r['steps'])):9.1f} {float(np.mean(r['reached'])):8.2f} "
+                    f"{pe}")
+    return "\n".join(rows)
 
 
 def _use_fused(fused: Optional[bool], policy, e, obs_mode: str) -> bool:
@@ -391,13 +476,33 @@ def episode_digests(e: QuadVecEnv) -> list:
 @torch.no_grad()
 def compare_pair(a: str, b: str, model=None, params=None, num_episodes: int = 256, env: str = "hover",
                  wrapper: Optional[str] = "auto", max_episode_steps: Optional[int] = None, device="cuda",
-                 seed: int = 0, survive_steps: int = 512) -> dict:
+                 seed: int = 0, survive_steps: int = 512, trajectories: Optional[Sequence] = None,
+                 spacings: Sequence[float] = (0.5,), reach_radius: float = 0.25, max_steps: int = 5000,
+                 replicas: int = 1, obs_mode: str = "env", velocity_alpha: Optional[float] = None) -> dict:
     """The reference's compare_controllers.py, batched: controllers `a` and `b` (any of CONTROLLERS, or
     "model" for the policy `model`) on the same Philox episodes. {a: ..., b: ..., "table"}; each entry has
     evaluate_pid_episodes' keys plus "digests" and "survival_rate" (episodes of at least `survive_steps`
-    steps, compare_controllers.py's measure); the table prints its four metrics."""
+    steps, compare_controllers.py's measure); the table prints its four metrics. With `trajectories` both
+    sides fly waypoint laps on the same courses instead (evaluate_waypoints / evaluate_ctrl_waypoints with
+    `spacings`, `reach_radius`, `max_steps`, `replicas`; hover env): each entry has their keys, the table is
+    lap_table's."""
     device = torch.device(device)
     out = {}
+    if trajectories is not None:
+        for name in (a, b):
+            if name == "model":
+                if model is None:
+                    raise ValueError("comparing against \"model\" needs a policy")
+                out[name] = evaluate_waypoints(model, trajectories, spacings, reach_radius, max_steps, replicas,
+                                               wrapper=wrapper, device=device, seed=seed, obs_mode=obs_mode,
+                                               velocity_alpha=velocity_alpha)
+            elif name in CONTROLLERS:
+                out[name] = evaluate_ctrl_waypoints(name, params, trajectories, spacings, reach_radius, max_steps,
+                                                    replicas, device=device, seed=seed)
+            else:
+                raise ValueError(f"unknown controller {name!r}: one of {CONTROLLERS + ('model',)}")
+        out["table"] = lap_table([(name, out[name]) for name in dict.fromkeys((a, b))])
+        return out
     for name in (a, b):
         if name == "model":
             if model is None:
@@ -497,7 +602,9 @@ def main(argv=None):
     ap.add_argument("--gains", default=None, help="pid_gains.json-shaped file (default: the reference's gains)")
     ap.add_argument("--env", default="hover", choices=["hover", "trajectory"])
     ap.add_argument("--mode", choices=["episodes", "trajectory"], default="trajectory")
-    ap.add_argument("--trajectory", nargs="+", default=["eight"], choices=["eight", "circle", "square"])
+    ap.add_argument("--trajectory", nargs="+", default=None, choices=["eight", "circle", "square"],
+                    help="waypoint laps (default eight); given with --controller pid|se3|smc|lqr, --compare or "
+                         "--deployed, those fly the laps instead of hover episodes")
     ap.add_argument("--spacing", nargs="+", type=float, default=[0.5])
     ap.add_argument("--reach-radius", type=float, default=0.25)
     ap.add_argument("--max-steps", type=int, default=5000)
@@ -511,6 +618,8 @@ def main(argv=None):
     ap.add_argument("--velocity-alpha", type=float, default=None,
                     help="the estimator's alpha for --deployed episodes (default 0.8)")
     a = ap.parse_args(argv)
+    laps = a.trajectory is not None  # asked for by name: the classical laws, --compare and --deployed fly laps too
+    a.trajectory = a.trajectory or ["eight"]
     if a.test_velocity is not None:
         if a.model is None:
             ap.error("--test-velocity needs --model")
@@ -525,13 +634,28 @@ def main(argv=None):
         if a.compare:
             if "model" in a.compare and a.model is None:
                 ap.error("--compare with model needs --model")
-            r = compare_pair(a.compare[0], a.compare[1], a.model, params, a.num_episodes, env=a.env)
+            if laps:
+                r = compare_pair(a.compare[0], a.compare[1], a.model, params, trajectories=a.trajectory,
+                                 spacings=a.spacing, reach_radius=a.reach_radius, max_steps=a.max_steps,
+                                 replicas=a.replicas, obs_mode="deployed" if a.deployed else "env",
+                                 velocity_alpha=a.velocity_alpha)
+            else:
+                r = compare_pair(a.compare[0], a.compare[1], a.model, params, a.num_episodes, env=a.env)
             print(r["table"])
+            return r
+        if laps:
+            r = evaluate_ctrl_waypoints(a.controller, params, a.trajectory, a.spacing, a.reach_radius, a.max_steps,
+                                        a.replicas)
+            _print_laps(a.controller, r)
             return r
         r = evaluate_ctrl_episodes(a.controller, params, a.num_episodes, env=a.env)
         print(f"Episodes: {a.num_episodes}\nSurvival: {100 * r['survival']:.0f}%\n"
               f"Mean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
               f"Mean length: {r['mean_length']:.1f} +/- {r['std_length']:.1f}\nMean error: {r['mean_pos_error']:.3f}m")
+        return r
+    if a.controller == "pid" and laps:
+        r = evaluate_ctrl_waypoints("pid", a.gains, a.trajectory, a.spacing, a.reach_radius, a.max_steps, a.replicas)
+        _print_laps("pid", r)
         return r
     if a.controller == "pid":
         r = evaluate_pid_episodes(a.gains, a.num_episodes, env=a.env)
@@ -545,7 +669,7 @@ def main(argv=None):
         r = compare_controllers(a.model, a.gains, a.num_episodes, env=a.env)
         print(r["table"])
         return r
-    if a.mode == "episodes" or a.deployed:
+    if a.mode == "episodes" or (a.deployed and not laps):
         r = evaluate_episodes(a.model, a.num_episodes, obs_mode="deployed" if a.deployed else "env",
                               velocity_alpha=a.velocity_alpha)
         print(f"Episodes: {a.num_episodes}\nMean reward: {r['mean_reward']:.2f} +/- {r['std_reward']:.2f}\n"
@@ -553,13 +677,22 @@ def main(argv=None):
         if a.deployed:
             print(f"Velocity RMSE: {r['vel_rmse']:.4f} m/s\nMean error: {r['pos_errors'].mean():.3f}m")
         return r
-    r = evaluate_waypoints(a.model, a.trajectory, a.spacing, a.reach_radius, a.max_steps, a.replicas)
-    status = {0: "running", 1: "lap", 2: "terminated", 3: "max steps"}
+    r = evaluate_waypoints(a.model, a.trajectory, a.spacing, a.reach_radius, a.max_steps, a.replicas,
+                           obs_mode="deployed" if a.deployed else "env", velocity_alpha=a.velocity_alpha)
+    _print_laps("policy (deployed)" if a.deployed else "policy", r)
+    return r
+
+
+def _print_laps(name: str, r: dict) -> None:
+    """evaluate.py's per-course line, with the mean position error where the fused launch measured it, and the
+    summary line of lap_table."""
+    from .waypoints import STATUS
     for i in range(len(r["name"])):
+        pe = f"  pos error {r['pos_errors'][i]:.3f}m" if "pos_errors" in r else ""
         print(f"{r['name'][i]:>12}: steps {r['steps'][i]:5d}  waypoints {r['reached'][i]:3d}/"
               f"{r['n_waypoints'][i]:3d}  laps {r['laps'][i]}  reward {r['total_reward'][i]:9.2f}  "
-              f"{status[int(r['status'][i])]}")
-    return r
+              f"{STATUS[int(r['status'][i])]}{pe}")
+    print(lap_table([(name, r)]))
 
 
 if __name__ == "__main__":

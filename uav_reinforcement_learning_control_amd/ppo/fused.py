@@ -185,6 +185,43 @@ class FusedPolicy:
                 "quad_policy_episode")
         return res
 
+    def waypoints(self, env, course, *, max_steps: int = 5000, obs_mode="env", alpha=None, alpha_all: float = 0.8,
+                  max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
+        """quad_policy_waypoints: the deterministic policy's waypoint laps on a hover `env` in one launch.
+        `course`: a WaypointCourse after course.begin(env) (or an earlier run: the tracker carries on). Every env
+        whose tracker status is 0 flies until it completes its lap, terminates, truncates or `max_steps` pass.
+        obs_mode "env": the policy sees the step's own observation (one step stale after a switch, as the
+        reference's loop has it); "deployed": the ROS2 node's observation, rebuilt with the new target. Returns
+        episode()'s tensors (status PID_LAP where the lap was completed) and, with trace_envs = M > 0, also
+        "rewards" [T, M] and "flown_wp" [T, M] (the waypoint each step flew toward). The tracker arrays are
+        course.tracker."""
+        n, dev = env.num_envs, self.device
+        T, M = int(max_steps), int(trace_envs)
+        res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+        res["vel_err_sq"] = torch.zeros(n, dtype=torch.float64, device=dev)
+        if M > 0 and T > 0:
+            for k, w in (("actions", 4), ("obs", 12), ("state12", 12), ("vel_est", 3)):
+                res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
+            res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
+            res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
+        if alpha is not None:
+            alpha = torch.as_tensor(alpha, dtype=torch.float64, device=dev).contiguous()
+            _need(alpha, (n,), torch.float64, dev, "alpha")
+        if est_state is not None:
+            _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
+        tr = lambda k: res[k].data_ptr() if k in res else None
+        run = N.QuadPolicyRun(obs_mode=N.OBS_MODES[obs_mode], max_steps=T, trace_envs=M,
+                              est=N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
+                                               state=_p(est_state)),
+                              est_dt=float(env.dt), trace_actions=tr("actions"), trace_state12=tr("state12"),
+                              trace_obs=tr("obs"), trace_vel_est=tr("vel_est"),
+                              metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
+                              vel_err_sq=res["vel_err_sq"].data_ptr())
+        wr = course.run(res.get("rewards"), res.get("flown_wp"))
+        N.check(N.lib().quad_policy_waypoints(env._h, _p(self.packed), C.byref(run), C.byref(wr), self._stream()),
+                "quad_policy_waypoints")
+        return res
+
 
 def _net_supported(policy) -> bool:
     try:
@@ -201,6 +238,11 @@ def episode_supported(policy, env) -> bool:
     return (cfg is not None and getattr(env, "_h", None) is not None
             and cfg.env_kind in (N.ENV_HOVER, N.ENV_TRAJ) and cfg.wrapper in (N.WRAP_NONE, N.WRAP_CTBR)
             and _net_supported(policy))
+
+
+def waypoints_supported(policy, env) -> bool:
+    """quad_policy_waypoints: episode_supported on a hover env (a switch overwrites the target register)."""
+    return episode_supported(policy, env) and env.cfg.env_kind == N.ENV_HOVER
 
 
 def rollout_supported(env) -> bool:
