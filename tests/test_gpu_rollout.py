@@ -51,7 +51,7 @@ def _bufs(T, n):
                 stats=torch.zeros(N.POLICY_STAT_SLOTS, 3, dtype=torch.float64, device="cuda"))
 
 
-def _two_launch(fp, env, b, T, seed, gamma):
+def _two_launch(fp, env, b, T, seed, gamma, deterministic=False):
     cur = torch.zeros(4, dtype=torch.int32, device="cuda")
     act_env = torch.zeros(env.num_envs, 4, device="cuda")
     epi = fp.make_epilogue(env.reward, env.terminated, env.truncated, env.terminal_obs, b["rewards"],
@@ -59,16 +59,17 @@ def _two_launch(fp, env, b, T, seed, gamma):
     for _ in range(T):
         fp.act(b["last_obs"], act_env, actions=b["actions"], log_prob=b["log_prob"], value=b["value"],
                obs_copy=b["obs_copy"], last_start=b["last_start"], episode_starts=b["episode_starts"],
-               cursor=cur, rows=T, seed=seed, env_id_base=env.env_id_base, epilogue=epi)
+               cursor=cur, rows=T, seed=seed, env_id_base=env.env_id_base, deterministic=deterministic,
+               epilogue=epi)
         env.step(act_env, obs=b["last_obs"], info="raw")
     fp.post(epi, cur)
     torch.cuda.synchronize()
 
 
-def _one_launch(fp, env, b, T, seed, gamma, chunks):
+def _one_launch(fp, env, b, T, seed, gamma, chunks, deterministic=False):
     t = 0
     for k in chunks:
-        fp.rollout(env, t0=t, steps=k, seed=seed, gamma=gamma, **b)
+        fp.rollout(env, t0=t, steps=k, seed=seed, gamma=gamma, deterministic=deterministic, **b)
         t += k
     assert t == T
     torch.cuda.synchronize()
@@ -117,6 +118,48 @@ def test_one_launch_rollout_is_bit_identical(kind, wrapper, max_steps, n, chunks
             truncs += int(np.sum((done[t] == 1) & (length == max_steps)))
             length[done[t] == 1] = 0
         assert truncs > 0
+
+
+@pytest.mark.parametrize("nt", ["2", "1"])
+def test_deterministic_rollout_is_bit_identical_and_unnoised(nt, monkeypatch):
+    """QuadRollout.deterministic: one launch against two launches with deterministic = 1 on both sides,
+    every buffer and the env state bit for bit; the actions rows are the un-noised mean (the torch fp32
+    mean of the stored observations, test_gpu_policy's 2e-5 bar; the noise's std is 0.08 .. 0.22), so
+    log_prob is the constant -sum(log_std) - 4 * 0.5 log(2 pi) to f32 rounding."""
+    monkeypatch.setenv("QUADENV_ROLLOUT_NT", nt)
+    from uav_reinforcement_learning_control_amd.ppo.fused import FusedPolicy
+    kind, wrapper, max_steps, n, chunks = "trajectory", "RateControlWrapper", 11, 777, (5, 5, 10)
+    T, seed, gamma = sum(chunks), 0x1234_5678_9ABC, 0.97
+    pol = _policy()
+    fp = FusedPolicy(pol)
+    fp.pack()
+    ea, eb = _env(n, kind, wrapper, max_steps, base=3 * n), _env(n, kind, wrapper, max_steps, base=3 * n)
+    A, B = _bufs(T, n), _bufs(T, n)
+    A["last_obs"].copy_(ea.reset())
+    B["last_obs"].copy_(eb.reset())
+    _two_launch(fp, ea, A, T, seed, gamma, deterministic=True)
+    _one_launch(fp, eb, B, T, seed, gamma, chunks, deterministic=True)
+    for k in ("obs_copy", "actions", "log_prob", "value", "episode_starts", "rewards", "last_obs",
+              "last_start", "ep_ret", "ep_len"):
+        a, b = A[k].cpu().numpy(), B[k].cpu().numpy()
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), \
+            f"{k}: {np.sum(a.view(np.uint32) != b.view(np.uint32))} words differ"
+    sa, sb = ea.get_state(), eb.get_state()
+    for k, v in sa.items():
+        assert np.array_equal(np.asarray(v).view(np.uint32), np.asarray(sb[k]).view(np.uint32)), k
+    np.testing.assert_allclose(B["stats"].sum(0).cpu().numpy(), A["stats"].sum(0).cpu().numpy(), rtol=1e-6)
+    assert B["last_start"].sum().item() + B["episode_starts"][1:].sum().item() > 0   # episodes ended
+    # no noise: the stored actions are the policy's mean of the stored observations
+    with torch.no_grad():
+        mean, _ = pol.forward_heads(B["obs_copy"].reshape(T * n, 12))
+    a, m = B["actions"].reshape(T * n, 4).double(), mean.double()
+    assert ((a - m).abs() / (1 + m.abs())).max().item() <= 2e-5
+    # z = 0 exactly, so every log_prob is the same number: four terms -log_std[k] - 0.5 log(2 pi), each
+    # rounded twice and summed in f32 (partial sums below 8: at most 8 half-ulps of 4.77e-7)
+    lp = B["log_prob"].cpu().numpy()
+    const = -float(pol.log_std.detach().double().sum()) - 4 * 0.5 * math.log(2 * math.pi)
+    assert np.unique(lp).size == 1
+    assert abs(float(lp.flat[0]) - const) <= 8 * 0.5 * 4.77e-7
 
 
 def test_rollout_rejects_bad_arguments():
