@@ -668,6 +668,94 @@ int quad_ppo_adv_stats_epoch(const float* advantages, const int64_t* perm, int32
 int quad_ppo_hidden(const QuadPolicyParams* params, const QuadPPOBatch* b, const QuadPolicyGrads* grads,
                     float* hidden, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- PPO populations in lock-step launches (added within ABI v8, whose number an
+ * existing layout test pins: a v8 library built before these entry points lacks the quad_pop_* exports, and the
+ * Python binding says so when it loads one): P independent small learners that share
+ * every shape -- env kind, wrapper and constants, envs per member N, rollout rows T, minibatch size B -- and
+ * differ in their pointers, seeds and scalar hyperparameters. Each call below does, in ONE launch per kernel
+ * family, what P single calls do (the member is one more grid dimension; its block reads the member's
+ * argument struct from a device table and runs the single kernel's body), so member m's outputs are
+ * bit-identical to the single calls on member m's arguments.
+ *   quad_pop_pack            quad_policy_pack(params -> packed)
+ *   quad_pop_rollout         quad_rollout(env, packed, rollout with the given t0 / steps)
+ *   quad_pop_value           quad_policy_act(deterministic, rows = 1): V(rollout.last_obs) -> last_values
+ *   quad_pop_gae             quad_gae(rollout buffers, last_values, rollout.last_start, rollout.gamma, gae_lambda)
+ *   quad_pop_permutation     quad_permutation(T N, seeds[m]) -> perm
+ *   quad_pop_adv_stats_epoch quad_ppo_adv_stats_epoch(advantages, perm, B, T N / B) -> adv_sums
+ *   quad_pop_ppo_grad        quad_ppo_grad (bf16x3 form) on minibatch `slot` of the epoch: index = perm + slot B,
+ *                            adv_sums row `slot` (QUAD_ADV_GIVEN), stats -> mb_stats + 4 slot
+ *   quad_pop_clip_adam       quad_clip_adam(adam)
+ * The tables are built once by quad_pop_create (which validates every member and copies the tables to the
+ * device; it synchronizes) and reused: a launch call makes no allocation, no host-to-device copy and no host
+ * synchronization, so every launch call is stream-ordered and graph-capturable. A launch covers a SUBSET of
+ * the members: quad_pop_subset registers a list of distinct member indices once (one small upload) and
+ * returns its id; id 0 is every member. Members outside the subset are not touched. The member's buffers
+ * are referenced, not copied: keep them alive and in place for the lifetime of the population. A table entry
+ * also holds the env handle's parameters as they are at creation (its seed among them): do not quad_seed a
+ * member's handle afterwards. */
+typedef struct QuadPopMember {
+  QuadHandle* env;          /* the member's own env handle (quad_rollout's requirements) */
+  QuadPolicyParams params;
+  QuadPolicyGrads grads;
+  QuadAdam adam;            /* with the member's lr, betas, eps, max_grad_norm */
+  float* packed;            /* [quad_policy_packed_floats()] (16-byte aligned) */
+  QuadRollout rollout;      /* the member's buffers, rows = T, seed, gamma; t0 and steps are given per launch */
+  float* last_values;       /* [N] V(last_obs), written by quad_pop_value */
+  float* scratch_actions;   /* [N,4] the deterministic actions quad_pop_value also writes */
+  float* advantages;        /* [T,N] */
+  float* returns;           /* [T,N] */
+  int64_t* perm;            /* [T N] the epoch permutation */
+  double* adv_sums;         /* [T N / B][QUAD_ADV_SUM_DOUBLES] */
+  float* mb_stats;          /* [T N / B][4]: pg_loss, vf_loss, entropy, clip_fraction per minibatch slot */
+  void* workspace;          /* quad_pop_workspace_bytes(adam, B) bytes, 16-byte aligned */
+  int64_t workspace_bytes;
+  float gae_lambda, clip_range, ent_coef, vf_coef;
+} QuadPopMember;
+typedef struct QuadPop QuadPop;
+/* Device workspace (bytes) one member needs: gradient partials, the W2 image, the gradient-norm partials.
+ * 0 on invalid arguments. */
+int64_t quad_pop_workspace_bytes(const QuadAdam* adam, int32_t batch);
+/* QUAD_EINVAL (nothing allocated, *out = NULL) for: P < 1 or P > 65,535; a NULL required pointer; a misaligned buffer;
+ * members whose shapes (env kind, wrapper, constants, N, rows, Adam tensor sizes) differ; an env kind or
+ * wrapper quad_rollout rejects; batch < 1 or > 8192 (the separate-block gradient form's limit); T N not a
+ * multiple of batch; a workspace that is too small; hyperparameters quad_ppo_grad / quad_clip_adam reject;
+ * QUADENV_LEARNER=f32 (only the bf16x3 gradient has a population form). */
+int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int32_t normalize_advantage,
+                    QuadPop** out);
+void quad_pop_destroy(QuadPop* pop);
+/* Register the subset `members[0..count)` (distinct indices in [0, P)); *subset_id receives its id.
+ * QUAD_EINVAL for an empty list, an index out of range or a duplicate. */
+int quad_pop_subset(QuadPop* pop, const int32_t* members, int32_t count, int32_t* subset_id);
+int quad_pop_pack(QuadPop* pop, int32_t subset, void* stream);
+int quad_pop_rollout(QuadPop* pop, int32_t subset, int32_t t0, int32_t steps, void* stream);
+int quad_pop_value(QuadPop* pop, int32_t subset, void* stream);
+int quad_pop_gae(QuadPop* pop, int32_t subset, void* stream);
+/* seeds: device uint64 [P], indexed by MEMBER (entries of members outside the subset are not read) */
+int quad_pop_permutation(QuadPop* pop, int32_t subset, const uint64_t* seeds, void* stream);
+int quad_pop_adv_stats_epoch(QuadPop* pop, int32_t subset, void* stream);
+int quad_pop_ppo_grad(QuadPop* pop, int32_t subset, int32_t slot, void* stream);
+int quad_pop_clip_adam(QuadPop* pop, int32_t subset, void* stream);
+
+/* Evaluation episodes of a population in ONE launch: quad_policy_episode (env-observation mode) for every
+ * member of the subset on an evaluation handle of the member's own and the member's packed image
+ * (quad_pop_pack first, after an update). quad_pop_attach_eval validates evals[0..P) -- one per member, each
+ * what quad_policy_episode takes; env = NULL for a member that is not evaluated -- builds the table and uploads
+ * it once; calling it again replaces the table. The table holds each handle's parameters (its seed among them)
+ * as they are when attached and refers to the handle's state: quad_pop_detach_eval before an evaluation handle
+ * is destroyed or re-seeded (quad_pop_episode then returns QUAD_EINVAL until the next attach). quad_pop_episode
+ * also rejects a subset with a member that has no handle attached.
+ * QUAD_EINVAL for anything quad_policy_episode rejects, obs_mode != QUAD_OBS_ENV, and evaluation handles whose
+ * env kind, wrapper, constants or env count differ, or run.max_steps that differ. Every env of every member
+ * flies from its current state (reset the handles first) to its first terminated / truncated step or
+ * max_steps and is frozen; each member's metrics arrays are written as quad_policy_episode writes them. */
+typedef struct QuadPopEval {
+  QuadHandle* env;          /* the member's evaluation handle (any auto_reset setting) */
+  QuadPolicyRun run;        /* obs_mode QUAD_OBS_ENV; the member's own metrics / trace / estimator arrays */
+} QuadPopEval;
+int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals);
+int quad_pop_detach_eval(QuadPop* pop);
+int quad_pop_episode(QuadPop* pop, int32_t subset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

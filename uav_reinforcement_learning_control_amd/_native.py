@@ -209,6 +209,30 @@ class QuadAdam(C.Structure):
                 ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
+POP_MAX_BATCH = 8192  # quad_pop_create: the separate-block gradient form's minibatch limit
+
+
+class QuadPopMember(C.Structure):
+    """One member of a lock-step PPO population (quad_pop_create; include/quadenv.h)."""
+    _fields_ = [("env", C.c_void_p), ("params", QuadPolicyParams), ("grads", QuadPolicyGrads), ("adam", QuadAdam),
+                ("packed", C.c_void_p), ("rollout", QuadRollout), ("last_values", C.c_void_p),
+                ("scratch_actions", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("perm", C.c_void_p), ("adv_sums", C.c_void_p), ("mb_stats", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("gae_lambda", C.c_float), ("clip_range", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float)]
+
+
+class QuadPopEval(C.Structure):
+    _fields_ = [("env", C.c_void_p), ("run", QuadPolicyRun)]
+
+
+POP_EXPORTS = ("quad_pop_workspace_bytes", "quad_pop_create", "quad_pop_destroy", "quad_pop_subset", "quad_pop_pack",
+               "quad_pop_rollout", "quad_pop_value", "quad_pop_gae", "quad_pop_permutation",
+               "quad_pop_adv_stats_epoch", "quad_pop_ppo_grad", "quad_pop_clip_adam", "quad_pop_attach_eval",
+               "quad_pop_detach_eval", "quad_pop_episode")
+EXPORTS = EXPORTS + POP_EXPORTS
+
+
 class QuadError(RuntimeError):
     pass
 
@@ -275,6 +299,25 @@ def _declare(L):
     L.quad_policy_episode.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), vp]
     L.quad_ctrl_waypoints.argtypes = [vp, C.POINTER(QuadCtrlRun), C.POINTER(QuadWaypointRun), vp]
     L.quad_policy_waypoints.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), C.POINTER(QuadWaypointRun), vp]
+    if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
+        raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
+    L.quad_pop_detach_eval.argtypes = [vp]
+    L.quad_pop_workspace_bytes.argtypes = [C.POINTER(QuadAdam), i32]
+    L.quad_pop_workspace_bytes.restype = C.c_int64
+    L.quad_pop_create.argtypes = [C.POINTER(QuadPopMember), i32, i32, i32, C.POINTER(vp)]
+    L.quad_pop_destroy.argtypes = [vp]
+    L.quad_pop_destroy.restype = None
+    L.quad_pop_subset.argtypes = [vp, C.POINTER(i32), i32, C.POINTER(i32)]
+    L.quad_pop_rollout.argtypes = [vp, i32, i32, i32, vp]
+    L.quad_pop_permutation.argtypes = [vp, i32, vp, vp]
+    L.quad_pop_ppo_grad.argtypes = [vp, i32, i32, vp]
+    L.quad_pop_attach_eval.argtypes = [vp, C.POINTER(QuadPopEval)]
+    for n in ("quad_pop_pack", "quad_pop_value", "quad_pop_gae", "quad_pop_adv_stats_epoch", "quad_pop_clip_adam",
+              "quad_pop_episode"):
+        getattr(L, n).argtypes = [vp, i32, vp]
+    for n in POP_EXPORTS[1:]:
+        if n != "quad_pop_destroy":
+            getattr(L, n).restype = C.c_int
     for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
               "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode", "quad_deploy_obs",
               "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints"):

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 
+#include "../../include/quadenv.h"
 #include "policy_net.h"
 
 namespace quadenv {
@@ -42,6 +43,24 @@ struct GArgs {
   float clip, inv_batch, vf_coef;
   float* dump;  // diagnostics only (k_ppo_grad*_dump): [2 nets][batch][256] hidden pre-activations
   const void* wimg;  // bf16x3 form: the W2 fragments of every wave as bf16 pieces (k_x3_prep, WIMG_BYTES)
+};
+
+// k_ppo_reduce's arguments
+struct RArgs {
+  QuadPolicyGrads gr;
+  const float* part;
+  const float* log_std;
+  float* stats;
+  int32_t nb, nbc;
+  float inv_batch, ent_coef;
+};
+
+// k_grad_sumsq's and k_adam's arguments (quad_clip_adam)
+struct AdamArgs {
+  QuadAdam a;
+  int32_t offs[QUAD_ADAM_MAX_TENSORS + 1];  // prefix sums of numel
+  float* part;                              // [nblocks] sums of squares
+  int32_t nblocks;
 };
 
 struct Layout {

@@ -36,6 +36,7 @@
 #include "../../include/quadenv.h"
 #include "learner.h"
 #include "policy_net.h"
+#include "population.h"
 
 namespace quadenv {
 
@@ -374,14 +375,18 @@ __global__ __launch_bounds__(256) void k_adv_stats_epoch(const float* __restrict
 }
 static_assert(QUAD_ADV_SUM_DOUBLES == 2 * ADV_BLOCKS, "ABI constant");
 
-struct RArgs {
-  QuadPolicyGrads gr;
-  const float* part;
-  const float* log_std;
-  float* stats;
-  int32_t nb, nbc;
-  float inv_batch, ent_coef;
-};
+// the population form (population.h): block (b, m, k) is block b of minibatch m of member active[k]'s epoch
+__global__ __launch_bounds__(256) void k_pop_adv_stats_epoch(const GArgs* __restrict__ tab,
+                                                             const int32_t* __restrict__ active) {
+  __shared__ double red[2][256];
+  const GArgs& g = tab[active[blockIdx.z]];
+  const size_t m = blockIdx.y;
+  const float* __restrict__ adv = g.adv;
+  const int64_t* __restrict__ perm = g.idx;
+  double* __restrict__ sums = const_cast<double*>(g.adv_part);
+  const int batch = g.batch;
+  adv_stats_block(adv, perm + m * size_t(batch), batch, sums + m * QUAD_ADV_SUM_DOUBLES, blockIdx.x, red);
+}
 
 // (net, parameter) sums of the nb block partials, in float64 (the partials of a bias or head
 // gradient are sums over disjoint row sets that largely cancel): 64 parameters per block, each
@@ -389,7 +394,7 @@ struct RArgs {
 // quarters then added in order. One thread per parameter left 147 blocks to stream the 38 MB
 // partial image of the bf16x3 form (13.3 us)
 constexpr int RQ = 4;
-__global__ __launch_bounds__(256) void k_ppo_reduce(RArgs a) {
+__device__ __forceinline__ void ppo_reduce_body(const RArgs& a) {
   __shared__ double qs[RQ][64];
   const int pl = threadIdx.x & 63, qt = threadIdx.x >> 6;
   const int q = blockIdx.x * 64 + pl;
@@ -439,6 +444,17 @@ __global__ __launch_bounds__(256) void k_ppo_reduce(RArgs a) {
   }
 }
 
+__global__ __launch_bounds__(256) void k_ppo_reduce(RArgs a) { ppo_reduce_body(a); }
+
+// the population form (population.h): block (b, k) is block b of member active[k]'s reduction; the member's
+// statistics row of minibatch `slot` is stats + 4 slot
+__global__ __launch_bounds__(256) void k_pop_ppo_reduce(const RArgs* __restrict__ tab, const int32_t* __restrict__ active,
+                                                        int32_t slot) {
+  RArgs a = tab[active[blockIdx.y]];
+  if (a.stats) a.stats += 4 * size_t(slot);
+  ppo_reduce_body(a);
+}
+
 // ---- the epoch permutation of PPO.train (SB3: indices = np.random.permutation(buffer_size)).
 // A keyed bijection of [0, 2^(2k)) -- a 4-round balanced Feistel network whose round function is a
 // 32-bit integer hash of (half, key, round) -- walked until it lands in [0, n) (cycle walking:
@@ -465,7 +481,7 @@ __host__ __device__ __forceinline__ uint64_t perm_feistel(uint64_t x, int half_b
   return (uint64_t(L) << half_bits) | R;
 }
 
-__global__ __launch_bounds__(256) void k_permutation(int64_t n, int half_bits, uint64_t seed, int64_t* __restrict__ out) {
+__device__ __forceinline__ void permutation_body(int64_t n, int half_bits, uint64_t seed, int64_t* __restrict__ out) {
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256) {
     uint64_t x = uint64_t(i);
     do { x = perm_feistel(x, half_bits, seed); } while (x >= uint64_t(n));
@@ -473,17 +489,22 @@ __global__ __launch_bounds__(256) void k_permutation(int64_t n, int half_bits, u
   }
 }
 
+__global__ __launch_bounds__(256) void k_permutation(int64_t n, int half_bits, uint64_t seed, int64_t* __restrict__ out) {
+  permutation_body(n, half_bits, seed, out);
+}
+
+// the population form (population.h): block (b, k) is block b of member m = active[k]'s permutation, keyed
+// by seeds[m], into the member's epoch permutation (its GArgs entry's idx)
+__global__ __launch_bounds__(256) void k_pop_permutation(const GArgs* __restrict__ tab, const int32_t* __restrict__ active,
+                                                         const uint64_t* __restrict__ seeds, int64_t n, int half_bits) {
+  const int m = active[blockIdx.y];
+  permutation_body(n, half_bits, seeds[m], const_cast<int64_t*>(tab[m].idx));
+}
+
 int lfail(int code, const char* m) { return set_error(code, m); }
 
 // ---- fused clip_grad_norm_ + Adam (quad_clip_adam)
 constexpr int ADAM_BLOCK = 256;
-
-struct AdamArgs {
-  QuadAdam a;
-  int32_t offs[QUAD_ADAM_MAX_TENSORS + 1];  // prefix sums of numel
-  float* part;                              // [nblocks] sums of squares
-  int32_t nblocks;
-};
 
 __device__ __forceinline__ int tensor_of(const AdamArgs& g, int i) {
   int t = 0;
@@ -493,7 +514,7 @@ __device__ __forceinline__ int tensor_of(const AdamArgs& g, int i) {
 }
 
 // per-block sums of squared gradients (fixed-order tree); block 0 advances the step counters
-__global__ __launch_bounds__(ADAM_BLOCK) void k_grad_sumsq(AdamArgs g) {
+__device__ __forceinline__ void grad_sumsq_body(const AdamArgs& g) {
   __shared__ float red[ADAM_BLOCK];
   const int i = blockIdx.x * ADAM_BLOCK + threadIdx.x;
   float v = 0.f;
@@ -512,8 +533,10 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_grad_sumsq(AdamArgs g) {
   if (blockIdx.x == 0 && int(threadIdx.x) < g.a.count) g.a.step[threadIdx.x][0] += 1.f;
 }
 
+__global__ __launch_bounds__(ADAM_BLOCK) void k_grad_sumsq(AdamArgs g) { grad_sumsq_body(g); }
+
 // every block reduces the partials in the same order (same norm everywhere), then clips + updates
-__global__ __launch_bounds__(ADAM_BLOCK) void k_adam(AdamArgs g) {
+__device__ __forceinline__ void adam_body(const AdamArgs& g) {
   __shared__ float red[ADAM_BLOCK];
   float v = 0.f;
   for (int b = threadIdx.x; b < g.nblocks; b += ADAM_BLOCK) v += g.part[b];
@@ -541,6 +564,19 @@ __global__ __launch_bounds__(ADAM_BLOCK) void k_adam(AdamArgs g) {
   const double bc1 = 1.0 - pow(b1, step), bc2 = 1.0 - pow(b2, step);
   const double denom = sqrt(double(vv)) / sqrt(bc2) + g.a.eps;
   g.a.params[t][j] = float(double(g.a.params[t][j]) - (g.a.lr / bc1) * double(m) / denom);
+}
+
+__global__ __launch_bounds__(ADAM_BLOCK) void k_adam(AdamArgs g) { adam_body(g); }
+
+// the population forms (population.h): block (b, k) is block b of member active[k]'s launch. The entry is
+// read in place (its pointer arrays are indexed per thread, as the single form indexes its kernel argument)
+__global__ __launch_bounds__(ADAM_BLOCK) void k_pop_grad_sumsq(const AdamArgs* __restrict__ tab,
+                                                               const int32_t* __restrict__ active) {
+  grad_sumsq_body(tab[active[blockIdx.y]]);
+}
+__global__ __launch_bounds__(ADAM_BLOCK) void k_pop_adam(const AdamArgs* __restrict__ tab,
+                                                         const int32_t* __restrict__ active) {
+  adam_body(tab[active[blockIdx.y]]);
 }
 
 int adam_layout(const QuadAdam* a, AdamArgs& g) {
@@ -728,3 +764,100 @@ int quad_clip_adam(const QuadAdam* a, void* workspace, int64_t workspace_bytes, 
 }
 
 }  // extern "C"
+
+// ---- the population launches of this file's kernels (population.h)
+namespace quadenv {
+namespace pop {
+
+namespace {
+// a member's workspace: [gradient partials][W2 image][gradient-norm partials]
+int64_t adam_ws_offset(int32_t batch) {
+  const Layout l = layout_both(batch);
+  return l.part_bytes + l.wimg_bytes;
+}
+}  // namespace
+
+int64_t learner_workspace_bytes(const QuadAdam* adam, int32_t batch) {
+  AdamArgs g{};
+  if (batch < 1 || adam_layout(adam, g) != QUAD_OK) return 0;
+  return adam_ws_offset(batch) + ((int64_t(g.nblocks) * int64_t(sizeof(float)) + 15) & ~int64_t(15));
+}
+
+int fill_learner(const QuadPopMember& m, int i, int32_t batch, int32_t normalize, GArgs* gt, RArgs* rt, AdamArgs* at) {
+  const QuadPolicyParams& p = m.params;
+  const QuadPolicyGrads& gr = m.grads;
+  if (!p.pi_w0 || !p.pi_b0 || !p.pi_w1 || !p.pi_b1 || !p.act_w || !p.act_b || !p.vf_w0 || !p.vf_b0 || !p.vf_w1 ||
+      !p.vf_b1 || !p.val_w || !p.val_b || !p.log_std)
+    return lfail(QUAD_EINVAL, "quad_pop_create: a policy parameter pointer is NULL");
+  if (!gr.pi_w0 || !gr.pi_b0 || !gr.pi_w1 || !gr.pi_b1 || !gr.act_w || !gr.act_b || !gr.vf_w0 || !gr.vf_b0 ||
+      !gr.vf_w1 || !gr.vf_b1 || !gr.val_w || !gr.val_b || !gr.log_std)
+    return lfail(QUAD_EINVAL, "quad_pop_create: a gradient pointer is NULL");
+  const QuadRollout& r = m.rollout;
+  if (!r.obs_copy || !r.actions || !r.log_prob || !m.advantages || !m.returns || !m.perm || !m.mb_stats ||
+      !m.workspace || (normalize && !m.adv_sums))
+    return lfail(QUAD_EINVAL, "quad_pop_create: a learner buffer is NULL");
+  if ((reinterpret_cast<uintptr_t>(r.obs_copy) | reinterpret_cast<uintptr_t>(r.actions) |
+       reinterpret_cast<uintptr_t>(m.workspace)) & 15u)
+    return lfail(QUAD_EINVAL, "quad_pop_create: obs_copy, actions and workspace must be 16-byte aligned");
+  if (!(m.clip_range > 0.f)) return lfail(QUAD_EINVAL, "quad_pop_create: clip_range must be > 0");
+  AdamArgs a{};
+  if (int rc = adam_layout(&m.adam, a)) return rc;
+  const QuadAdam& ad = m.adam;
+  if (!(ad.eps > 0.0) || !(ad.lr >= 0.0) || !(ad.beta1 >= 0.0 && ad.beta1 < 1.0) || !(ad.beta2 >= 0.0 && ad.beta2 < 1.0))
+    return lfail(QUAD_EINVAL, "quad_pop_create: need lr >= 0, eps > 0, 0 <= betas < 1");
+  if (m.workspace_bytes < learner_workspace_bytes(&m.adam, batch))
+    return lfail(QUAD_EINVAL, "quad_pop_create: workspace too small");
+  const Layout l = layout_both(batch);
+  char* ws = static_cast<char*>(m.workspace);
+  const bool norm = normalize && batch > 1;
+  GArgs g{};
+  g.actor = NetW{p.pi_w0, p.pi_b0, p.pi_w1, p.pi_b1, p.act_w, p.act_b};
+  g.critic = NetW{p.vf_w0, p.vf_b0, p.vf_w1, p.vf_b1, p.val_w, p.val_b};
+  g.log_std = p.log_std;
+  g.obs = r.obs_copy; g.act = r.actions; g.logp_old = r.log_prob; g.adv = m.advantages; g.ret = m.returns;
+  g.idx = m.perm;
+  g.adv_part = norm ? m.adv_sums : nullptr;
+  g.part = reinterpret_cast<float*>(ws);
+  g.batch = batch; g.nb = l.nb; g.per_block = l.per_block; g.nbc = l.nbc; g.per_block_c = l.per_block_c;
+  g.clip = m.clip_range; g.inv_batch = 1.0f / float(batch); g.vf_coef = m.vf_coef;
+  g.dump = nullptr;
+  g.wimg = ws + l.part_bytes;
+  gt[i] = g;
+  RArgs ra{};
+  ra.gr = gr; ra.part = g.part; ra.log_std = p.log_std; ra.stats = m.mb_stats; ra.nb = l.nb; ra.nbc = l.nbc;
+  ra.inv_batch = 1.0f / float(batch); ra.ent_coef = m.ent_coef;
+  rt[i] = ra;
+  a.part = reinterpret_cast<float*>(ws + adam_ws_offset(batch));
+  at[i] = a;
+  return QUAD_OK;
+}
+
+int launch_pop_permutation(const GArgs* tab, const int32_t* active, int count, int64_t n, const uint64_t* seeds,
+                           hipStream_t s) {
+  int bits = 2;
+  while ((int64_t(1) << bits) < n) bits += 2;
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_pop_permutation, dim3(unsigned(blocks < 8192 ? blocks : 8192), count), dim3(256), 0, s, tab,
+                     active, seeds, n, bits / 2);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : lfail(QUAD_EHIP, "k_pop_permutation launch failed");
+}
+
+int launch_pop_adv_stats_epoch(const GArgs* tab, const int32_t* active, int count, int n_minibatches, hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_adv_stats_epoch, dim3(ADV_BLOCKS, n_minibatches, count), dim3(256), 0, s, tab, active);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : lfail(QUAD_EHIP, "k_pop_adv_stats_epoch launch failed");
+}
+
+int launch_pop_reduce(const RArgs* rtab, const int32_t* active, int count, int slot, hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_ppo_reduce, dim3((2 * PSTRIDE + 63) / 64, count), dim3(256), 0, s, rtab, active, slot);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : lfail(QUAD_EHIP, "k_pop_ppo_reduce launch failed");
+}
+
+int launch_pop_clip_adam(const AdamArgs* t, const int32_t* active, int count, int nblocks, hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_grad_sumsq, dim3(nblocks, count), dim3(ADAM_BLOCK), 0, s, t, active);
+  if (hipGetLastError() != hipSuccess) return lfail(QUAD_EHIP, "k_pop_grad_sumsq launch failed");
+  hipLaunchKernelGGL(k_pop_adam, dim3(nblocks, count), dim3(ADAM_BLOCK), 0, s, t, active);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : lfail(QUAD_EHIP, "k_pop_adam launch failed");
+}
+
+}  // namespace pop
+}  // namespace quadenv

@@ -35,6 +35,7 @@
 #include "../../include/quadenv.h"
 #include "learner.h"
 #include "learner_x3_common.h"
+#include "population.h"
 
 namespace quadenv {
 
@@ -628,6 +629,28 @@ __global__ __launch_bounds__(LB, 1) void k_ppo_grad_x3_sep(GArgs g) {
     body<1>(g, lds_x3s, blockIdx.x - g.nb);
 }
 
+// The population forms (population.h): block (b, k) is block b of member active[k]'s launch. k_pop_x3_prep is
+// k_x3_prep's W2 split alone (a population's advantage statistics come from k_pop_adv_stats_epoch);
+// k_pop_ppo_grad_x3_sep reads the member's GArgs once at entry into scalars (uniform address, before any
+// store) and moves its index slice and advantage sums to minibatch `slot` of the epoch.
+__global__ __launch_bounds__(256) void k_pop_x3_prep(const GArgs* __restrict__ tab, const int32_t* __restrict__ active) {
+  const GArgs& g = tab[active[blockIdx.y]];
+  split_w2_unit(g.actor.w1, g.critic.w1, const_cast<bf16x8*>(static_cast<const bf16x8*>(g.wimg)),
+                4 * blockIdx.x + (threadIdx.x >> 6));
+}
+
+__global__ __launch_bounds__(LB, 1) void k_pop_ppo_grad_x3_sep(const GArgs* __restrict__ tab,
+                                                               const int32_t* __restrict__ active, int32_t slot) {
+  extern __shared__ __attribute__((aligned(16))) char lds_x3p[];
+  GArgs g = tab[active[blockIdx.y]];
+  g.idx += size_t(slot) * size_t(g.batch);
+  if (g.adv_part) g.adv_part += size_t(slot) * QUAD_ADV_SUM_DOUBLES;
+  if (int(blockIdx.x) < g.nb)
+    body<ACT>(g, lds_x3p, blockIdx.x);
+  else
+    body<1>(g, lds_x3p, blockIdx.x - g.nb);
+}
+
 // diagnostics: the same body with the hidden pre-activations recorded (quad_ppo_hidden)
 __global__ __launch_bounds__(LB, 1) void k_ppo_grad_x3_dump(GArgs g) {
   extern __shared__ __attribute__((aligned(16))) char lds_x3d[];
@@ -691,6 +714,23 @@ int launch_ppo_grad_x3(const GArgs& g, hipStream_t s, double* adv_stats, const f
   else
     hipLaunchKernelGGL(k_ppo_grad_x3, dim3(g.nb), dim3(LB), B_TOTAL, s, g);
   if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_ppo_grad_x3 launch failed");
+  return QUAD_OK;
+}
+
+int launch_pop_grad_x3(const GArgs* tab, const int32_t* active, int count, int slot, int nb, hipStream_t s) {
+  static bool opted[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(QUAD_EHIP, "hipGetDevice failed");
+  if (!opted[dev]) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_ppo_grad_x3_sep),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, B_TOTAL) != hipSuccess)
+      return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    opted[dev] = true;
+  }
+  hipLaunchKernelGGL(k_pop_x3_prep, dim3(SPLIT_BLOCKS, count), dim3(256), 0, s, tab, active);
+  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_x3_prep launch failed");
+  hipLaunchKernelGGL(k_pop_ppo_grad_x3_sep, dim3(2 * nb, count), dim3(LB), B_TOTAL, s, tab, active, slot);
+  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_ppo_grad_x3_sep launch failed");
   return QUAD_OK;
 }
 

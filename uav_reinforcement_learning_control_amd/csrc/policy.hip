@@ -23,6 +23,7 @@
 #include "../../include/quadenv.h"
 #include "quad_physics.h"
 #include "policy_net.h"
+#include "population.h"
 
 using namespace quadenv;
 
@@ -75,8 +76,8 @@ __device__ float pack_one(const NetPtrs& p, int nout, int idx) {
   return t < nout ? p.b2[t] : 0.f;
 }
 
-__global__ void k_policy_pack(NetPtrs actor, NetPtrs critic, const float* __restrict__ log_std,
-                              float* __restrict__ out) {
+__device__ __forceinline__ void policy_pack_body(const NetPtrs& actor, const NetPtrs& critic,
+                                                 const float* __restrict__ log_std, float* __restrict__ out) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= PACKED_F + 2 * 32 * 64 + 2 * 4 * 64) return;
   if (idx >= PACKED_F + 2 * 32 * 64) {  // one (net, layer-1 block n, lane) unit of the W1 pieces
@@ -108,6 +109,20 @@ __global__ void k_policy_pack(NetPtrs actor, NetPtrs critic, const float* __rest
   else if (idx < LDS_F) v = pack_one(critic, 1, idx - ACTOR_F);
   else v = log_std[idx - LDS_F];
   out[idx] = v;
+}
+
+__global__ void k_policy_pack(NetPtrs actor, NetPtrs critic, const float* __restrict__ log_std,
+                              float* __restrict__ out) {
+  policy_pack_body(actor, critic, log_std, out);
+}
+
+// the population form (population.h): block (b, k) packs block b of member active[k]'s image
+__global__ void k_pop_policy_pack(const quadenv::pop::PackEntry* __restrict__ tab, const int32_t* __restrict__ active) {
+  const quadenv::pop::PackEntry e = tab[active[blockIdx.y]];
+  const QuadPolicyParams& p = e.p;
+  const NetPtrs actor{p.pi_w0, p.pi_b0, p.pi_w1, p.pi_b1, p.act_w, p.act_b};
+  const NetPtrs critic{p.vf_w0, p.vf_b0, p.vf_w1, p.vf_b1, p.val_w, p.val_b};
+  policy_pack_body(actor, critic, p.log_std, e.packed);
 }
 
 // the input fragment of one env: features 8 (lane>>5) .. + 7 (zero past feature 11)
@@ -236,7 +251,7 @@ struct ActArgs {
 // NT_ACT tiles per wave iteration (sharing weight fragments), BLK threads per block (one block per
 // CU; BLK = 512 puts two waves on each SIMD, which caps a wave at 256 registers)
 template <int NT_ACT, int BLK>
-__global__ __launch_bounds__(BLK) void k_policy_act(const float* __restrict__ packed, ActArgs a, EpiArgs e) {
+__device__ __forceinline__ void policy_act_body(const float* __restrict__ packed, const ActArgs& a, const EpiArgs& e) {
   extern __shared__ float lds[];
   constexpr int WAVES = BLK / 64;
   stage_lds<BLK>(lds, packed);
@@ -317,6 +332,23 @@ __global__ __launch_bounds__(BLK) void k_policy_act(const float* __restrict__ pa
   }
 }
 
+template <int NT_ACT, int BLK>
+__global__ __launch_bounds__(BLK) void k_policy_act(const float* __restrict__ packed, ActArgs a, EpiArgs e) {
+  policy_act_body<NT_ACT, BLK>(packed, a, e);
+}
+
+// the population form of the bootstrap value (population.h): block (b, k) is block b of member active[k]'s
+// deterministic quad_policy_act with rows = 1 and only the value row requested (FusedPolicy.value)
+template <int NT_ACT, int BLK>
+__global__ __launch_bounds__(BLK) void k_pop_policy_value(const quadenv::pop::ValueEntry* __restrict__ tab,
+                                                          const int32_t* __restrict__ active, int32_t n) {
+  const quadenv::pop::ValueEntry v = tab[active[blockIdx.y]];
+  const ActArgs a{v.obs, v.act_env, nullptr, nullptr, v.value, nullptr, nullptr, nullptr, nullptr, 1, 1, 0, 0, n, 0};
+  const EpiArgs e{};
+  const float* __restrict__ packed = v.packed;
+  policy_act_body<NT_ACT, BLK>(packed, a, e);
+}
+
 __global__ __launch_bounds__(PBLOCK) void k_rollout_post(const float* __restrict__ packed, EpiArgs e,
                                                          uint32_t* cursor, int32_t n) {
   extern __shared__ float lds[];
@@ -349,6 +381,8 @@ int lds_opt_in() {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_act<2, 256>),
                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
 
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_policy_value<2, 256>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rollout_post),
                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
     return pfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
@@ -383,6 +417,19 @@ int check_epi(const QuadRolloutPost* p) {
 }
 
 }  // namespace
+
+int quadenv::pop::launch_pop_pack(const PackEntry* tab, const int32_t* active, int count, hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_policy_pack, dim3((PACKED_F + 2 * 32 * 64 + 2 * 4 * 64 + 255) / 256, count), dim3(256), 0,
+                     s, tab, active);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : pfail(QUAD_EHIP, "k_pop_policy_pack launch failed");
+}
+
+int quadenv::pop::launch_pop_value(const ValueEntry* tab, const int32_t* active, int count, int n, hipStream_t s) {
+  if (int rc = lds_opt_in()) return rc;
+  hipLaunchKernelGGL((k_pop_policy_value<2, 256>), dim3(grid_for(n, 2, 4), count), dim3(256), LDS_F * sizeof(float),
+                     s, tab, active, n);
+  return hipGetLastError() == hipSuccess ? QUAD_OK : pfail(QUAD_EHIP, "k_pop_policy_value launch failed");
+}
 
 extern "C" {
 

@@ -33,6 +33,16 @@ hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const
 hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
                                  int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s);
 
+// The population form (population.h, quad_pop_episode): k_policy_episode's arguments per member, env-observation
+// mode; block (b, k) is block b of member active[k]'s episodes. kc: the constant block every member shares.
+struct PopEpisodeEntry {
+  KParams kp;
+  const float* packed;
+  EpisodeArgs a;
+};
+hipError_t launch_pop_policy_episode(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active,
+                                     int count, int n, int env_kind, bool ctbr, bool spec, hipStream_t s);
+
 // the block shape of both fused policy launches for n envs: tiles per wave (1 / 2), envs per block (64 / 256)
 void episode_block_shape(int32_t n, int& nt, int& eb);
 

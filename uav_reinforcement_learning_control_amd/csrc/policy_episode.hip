@@ -40,6 +40,7 @@
 #include "kconsts_default.h"
 #include "policy_episode.h"
 #include "policy_net.h"
+#include "population.h"
 #include "quad_deploy.h"
 #include "quad_physics.h"
 #include "quad_pid.h"
@@ -57,7 +58,14 @@ namespace quadenv {
 template <int KIND>
 hipError_t launch_episode_kind(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
                                int nt, int eb, const float* packed, const EpisodeArgs& a, hipStream_t s);
+template <int KIND>
+hipError_t launch_pop_episode_kind(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active,
+                                   int count, int n, bool ctbr, bool spec, int nt, int eb, hipStream_t s);
 #if PE_KIND == 0
+template <>
+hipError_t launch_pop_episode_kind<QUAD_ENV_TRAJ>(const KConsts<float>* kc, const PopEpisodeEntry* tab,
+                                                  const int32_t* active, int count, int n, bool ctbr, bool spec,
+                                                  int nt, int eb, hipStream_t s);
 template <>  // the trajectory kind's: the other object of this file
 hipError_t launch_episode_kind<QUAD_ENV_TRAJ>(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec,
                                               int obs_mode, int nt, int eb, const float* packed, const EpisodeArgs& a,
@@ -264,6 +272,46 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_policy_episode(const KConsts<fl
   }
 }
 
+#if !PE_WP
+// The population form (quad_pop_episode); the member's entry is read through pop::const_entry (population.h).
+template <int KIND, bool CTBR, int NT, bool SPEC, int EB>
+__global__ __launch_bounds__(EB * 2 / NT) void k_pop_policy_episode(const KConsts<float>* __restrict__ kc,
+                                                                    const PopEpisodeEntry* __restrict__ tab,
+                                                                    const int32_t* __restrict__ active) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (pop::const_entry, population.h)
+  const auto& en = pop::const_entry(tab, active[blockIdx.y]);
+  KParams p = en.kp;
+  p.kc = kc;
+  const EpisodeArgs a = en.a;
+  const float* __restrict__ packed = en.packed;
+  if constexpr (SPEC) {
+    constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
+    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(K, p, packed, a, nullptr);
+  } else {
+    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(*kc, p, packed, a, nullptr);
+  }
+#endif
+}
+
+template <int KIND, bool CTBR, int NT, bool SPEC, int EB>
+hipError_t launch_pop(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count, int n,
+                      hipStream_t s) {
+  static bool opted[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  const int bytes = LDS_F * int(sizeof(float));
+  if (!opted[dev]) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_policy_episode<KIND, CTBR, NT, SPEC, EB>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    opted[dev] = true;
+  }
+  hipLaunchKernelGGL((k_pop_policy_episode<KIND, CTBR, NT, SPEC, EB>), dim3((n + EB - 1) / EB, count),
+                     dim3(EB * 2 / NT), bytes, s, kc, tab, active);
+  return hipGetLastError();
+}
+#endif
+
 #if PE_WP
 // the WP form of k_policy_episode: hover kind only (a switch overwrites the target register), the tracker's
 // tables and rows in a kernel argument of its own so k_policy_episode's arguments stay as they are
@@ -392,6 +440,22 @@ hipError_t launch_episode_kind<PE_KIND>(const KConsts<float>* kc, const KParams&
 }
 #endif
 
+#if !PE_WP
+template <>
+hipError_t launch_pop_episode_kind<PE_KIND>(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active,
+                                            int count, int n, bool ctbr, bool spec, int nt, int eb, hipStream_t s) {
+  return with_bool(ctbr, [&](auto cb) {
+    return with_bool(spec, [&](auto sp) {
+      constexpr int KD = PE_KIND;
+      constexpr bool CB = decltype(cb)::value, SP = decltype(sp)::value;
+      if (nt == 1) return launch_pop<KD, CB, 1, SP, 64>(kc, tab, active, count, n, s);  // (launch_episode_kind's rule)
+      return eb == 64 ? launch_pop<KD, CB, 2, SP, 64>(kc, tab, active, count, n, s)
+                      : launch_pop<KD, CB, 2, SP, 256>(kc, tab, active, count, n, s);
+    });
+  });
+}
+#endif
+
 #if PE_KIND == 0
 hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const float* state12, const float* target3,
                              double timestamp, int32_t n, float* obs, float* vel_est, hipStream_t s) {
@@ -420,6 +484,14 @@ hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, in
   return env_kind == QUAD_ENV_TRAJ
              ? launch_episode_kind<QUAD_ENV_TRAJ>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s)
              : launch_episode_kind<QUAD_ENV_HOVER>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s);
+}
+hipError_t launch_pop_policy_episode(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active,
+                                     int count, int n, int env_kind, bool ctbr, bool spec, hipStream_t s) {
+  int nt, eb;
+  episode_block_shape(n, nt, eb);
+  return env_kind == QUAD_ENV_TRAJ
+             ? launch_pop_episode_kind<QUAD_ENV_TRAJ>(kc, tab, active, count, n, ctbr, spec, nt, eb, s)
+             : launch_pop_episode_kind<QUAD_ENV_HOVER>(kc, tab, active, count, n, ctbr, spec, nt, eb, s);
 }
 #endif
 

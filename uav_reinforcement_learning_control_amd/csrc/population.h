@@ -1,0 +1,103 @@
+// population.h -- PPO populations in lock-step launches (quad_pop_*, include/quadenv.h): the device
+// table entries of each kernel family and the host launchers the translation units export. A population
+// kernel is the single kernel's body behind one more grid dimension: block (.., k) runs member active[k],
+// whose argument struct it reads from the family's device table (population.hip builds the tables once).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/quadenv.h"
+#include "env_tiles.h"
+#include "learner.h"
+#include "policy_episode.h"
+#include "rollout.h"
+
+namespace quadenv {
+namespace pop {
+
+// what the population needs of an env handle (QuadHandle is quadenv.hip's)
+struct EnvView {
+  const KConsts<float>* kdev;   // the handle's constant block on the device
+  const KConsts<float>* khost;  // and its host copy (members must agree on it, bit for bit)
+  KParams kp;
+  int32_t env_kind, wrapper, auto_reset, device, n;
+  bool spec;
+};
+void env_view(const QuadHandle* h, EnvView* v);  // quadenv.hip
+// quad_policy_episode's argument checks (QUAD_EINVAL + message) and its flattened arguments; quadenv.hip
+int episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out);
+
+// A table entry seen through the constant address space (device code only). A population table is written by
+// the host before any launch and never while one runs, so its entries are invariant for a kernel, exactly as
+// its kernel arguments are; the constant address space tells the compiler so, and it may then re-issue an
+// entry's scalar loads where it would otherwise hold the values in registers or spill them. Read as plain
+// global loads into locals, the one-tile forms of k_pop_rollout spilled 4-28 bytes per lane more than k_rollout
+// (DESIGN 18). The register-tight kernels (rollout, policy episode) read their entry this way; the host pass
+// has no copy from an address-space-qualified struct, so their bodies are device-only.
+#if defined(__HIP_DEVICE_COMPILE__)
+template <class Entry>
+__device__ __forceinline__ const __attribute__((address_space(4))) Entry& const_entry(const Entry* tab, int32_t m) {
+  typedef const __attribute__((address_space(4))) Entry* CEntry;
+  return *(CEntry)(uintptr_t)(tab + m);
+}
+#endif
+
+// ---- rollout (rollout.hip): k_rollout's arguments, per member; t0 / steps come with the launch
+struct RollEntry {
+  KParams kp;  // kc unused: the launch passes the shared constant block as its noalias argument
+  const float* packed;
+  RollArgs a;
+};
+hipError_t launch_pop_rollout(const KConsts<float>* kc, const RollEntry* tab, const int32_t* active, int count, int n,
+                              int env_kind, bool ctbr, bool spec, uint32_t t0, int32_t steps, hipStream_t s);
+
+// ---- GAE (quadenv.hip): k_gae's arguments
+struct GaeEntry {
+  const float *rew, *val, *starts, *last_val, *dones;
+  float *adv, *ret;
+  float gamma, lam;
+};
+hipError_t launch_pop_gae(const GaeEntry* tab, const int32_t* active, int count, int T, int n, hipStream_t s);
+
+// ---- policy image and bootstrap value (policy.hip)
+struct PackEntry {
+  QuadPolicyParams p;
+  float* packed;
+};
+struct ValueEntry {  // quad_policy_act(deterministic, rows = 1, value = out): FusedPolicy.value
+  const float* packed;
+  const float* obs;
+  float* act_env;
+  float* value;
+};
+int launch_pop_pack(const PackEntry* tab, const int32_t* active, int count, hipStream_t s);
+int launch_pop_value(const ValueEntry* tab, const int32_t* active, int count, int n, hipStream_t s);
+
+// ---- learner (learner.hip, learner_x3.hip). The GArgs entry of a member holds the epoch's bases: idx = the
+// permutation, adv_part = the [n_minibatches][QUAD_ADV_SUM_DOUBLES] sums (NULL without normalization); the
+// gradient launch of minibatch `slot` advances both. RArgs.stats likewise is the [n_minibatches][4] base.
+struct LearnerTables {  // device
+  lrn::GArgs* g = nullptr;
+  lrn::RArgs* r = nullptr;
+  lrn::AdamArgs* a = nullptr;
+};
+// validate member `m`'s learner arguments and fill entry `i` of the host images (QUAD_EINVAL + message)
+int fill_learner(const QuadPopMember& m, int i, int32_t batch, int32_t normalize, lrn::GArgs* g, lrn::RArgs* r,
+                 lrn::AdamArgs* a);
+int64_t learner_workspace_bytes(const QuadAdam* adam, int32_t batch);
+int launch_pop_permutation(const lrn::GArgs* tab, const int32_t* active, int count, int64_t n, const uint64_t* seeds,
+                           hipStream_t s);
+int launch_pop_adv_stats_epoch(const lrn::GArgs* tab, const int32_t* active, int count, int n_minibatches,
+                               hipStream_t s);
+int launch_pop_reduce(const lrn::RArgs* rtab, const int32_t* active, int count, int slot, hipStream_t s);
+int launch_pop_clip_adam(const lrn::AdamArgs* atab, const int32_t* active, int count, int nblocks, hipStream_t s);
+
+}  // namespace pop
+
+namespace lrn {
+// k_x3_prep's W2 split + k_ppo_grad_x3_sep for every active member (learner_x3.hip); nb = layout_both(batch).nb
+int launch_pop_grad_x3(const GArgs* tab, const int32_t* active, int count, int slot, int nb, hipStream_t s);
+}  // namespace lrn
+
+}  // namespace quadenv

@@ -41,6 +41,7 @@
 #include "ctrl.h"
 #include "pid.h"
 #include "policy_episode.h"
+#include "population.h"
 #include "quad_waypoints.h"
 #include "rollout.h"
 
@@ -939,12 +940,10 @@ __global__ __launch_bounds__(BLOCK) void k_random_actions(int32_t n, uint64_t se
 }
 
 // SB3 RolloutBuffer.compute_returns_and_advantage, time-major [T, N]
-__global__ __launch_bounds__(BLOCK) void k_gae(const float* __restrict__ rew, const float* __restrict__ val,
-                                               const float* __restrict__ starts,
-                                               const float* __restrict__ last_val,
-                                               const float* __restrict__ dones, int32_t T, int32_t n,
-                                               float gamma, float lam, float* __restrict__ adv,
-                                               float* __restrict__ ret) {
+__device__ __forceinline__ void gae_body(const float* __restrict__ rew, const float* __restrict__ val,
+                                         const float* __restrict__ starts, const float* __restrict__ last_val,
+                                         const float* __restrict__ dones, int32_t T, int32_t n, float gamma,
+                                         float lam, float* __restrict__ adv, float* __restrict__ ret) {
   const int i = blockIdx.x * BLOCK + threadIdx.x;
   if (i >= n) return;
   float last = 0.f;
@@ -960,6 +959,22 @@ __global__ __launch_bounds__(BLOCK) void k_gae(const float* __restrict__ rew, co
     next_v = v;
     next_nt = 1.0f - starts[o];
   }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_gae(const float* __restrict__ rew, const float* __restrict__ val,
+                                               const float* __restrict__ starts,
+                                               const float* __restrict__ last_val,
+                                               const float* __restrict__ dones, int32_t T, int32_t n,
+                                               float gamma, float lam, float* __restrict__ adv,
+                                               float* __restrict__ ret) {
+  gae_body(rew, val, starts, last_val, dones, T, n, gamma, lam, adv, ret);
+}
+
+// the population form (population.h): block (b, k) is block b of member active[k]'s scan
+__global__ __launch_bounds__(BLOCK) void k_pop_gae(const pop::GaeEntry* __restrict__ tab,
+                                                   const int32_t* __restrict__ active, int32_t T, int32_t n) {
+  const pop::GaeEntry e = tab[active[blockIdx.y]];
+  gae_body(e.rew, e.val, e.starts, e.last_val, e.dones, T, n, e.gamma, e.lam, e.adv, e.ret);
 }
 
 }  // namespace
@@ -980,6 +995,17 @@ struct QuadHandle {
   int hd = -1;                       // k_step_hd for the 64-env nt launches: -1 = by size (hd_form), 0 / 1
   int nt = -1;                       // k_step_h's state cache policy: -1 = by size (nt_state), 0 / 1
 };
+
+// ---- what the population launches (population.hip) need from this file
+void quadenv::pop::env_view(const QuadHandle* h, EnvView* v) {
+  *v = EnvView{h->kdev, &h->kh, h->kp, h->cfg.env_kind, h->cfg.wrapper, h->cfg.auto_reset, h->device, h->n, h->spec};
+}
+
+hipError_t quadenv::pop::launch_pop_gae(const GaeEntry* tab, const int32_t* active, int count, int T, int n,
+                                        hipStream_t s) {
+  hipLaunchKernelGGL(k_pop_gae, dim3((n + BLOCK - 1) / BLOCK, count), dim3(BLOCK), 0, s, tab, active, T, n);
+  return hipGetLastError();
+}
 
 namespace {
 
@@ -1394,7 +1420,10 @@ int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, 
   return QUAD_OK;
 }
 
-int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream) {
+}  // extern "C"
+
+// quad_policy_episode's argument checks and its flattened arguments (also quad_pop_attach_eval's, population.hip)
+int quadenv::pop::episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out) {
   if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
     return fail(QUAD_EINVAL, "quad_policy_episode: env_kind must be HOVER or TRAJ");
@@ -1419,10 +1448,18 @@ int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun*
       return fail(QUAD_EINVAL, "quad_policy_episode: the action, state12 and obs traces must be 16-byte aligned");
   }
   if (reinterpret_cast<uintptr_t>(packed) & 15u) return fail(QUAD_EINVAL, "quad_policy_episode: packed must be 16-byte aligned");
+  *out = EpisodeArgs{r->max_steps, any_trace ? r->trace_envs : 0,
+                     EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
+                     r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
+  return QUAD_OK;
+}
+
+extern "C" {
+
+int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream) {
+  EpisodeArgs a{};
+  if (int rc = quadenv::pop::episode_args(h, packed, r, &a)) return rc;
   DeviceGuard g(h->device);
-  EpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0,
-                EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
-                r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
   HIP_TRY(launch_policy_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode,
                                 packed, a, static_cast<hipStream_t>(stream)));
   return QUAD_OK;

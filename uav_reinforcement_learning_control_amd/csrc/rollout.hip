@@ -31,6 +31,7 @@
 #include "env_tiles.h"
 #include "kconsts_default.h"
 #include "policy_net.h"
+#include "population.h"
 #include "quad_physics.h"
 #include "rollout.h"
 
@@ -284,12 +285,73 @@ hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* pack
   return hipGetLastError();
 }
 
+// The population form (population.h): block (b, k) is block b of member active[k]'s rollout. The member's
+// entry is read once at entry into scalars (uniform address, no store before it), t0 / steps come with the
+// launch, and the constant block -- the same for every member -- stays the noalias kernel argument.
+template <int KIND, bool CTBR, int NT, bool SPEC>
+__global__ __launch_bounds__(512 / NT) void k_pop_rollout(const KConsts<float>* __restrict__ kc,
+                                                          const pop::RollEntry* __restrict__ tab,
+                                                          const int32_t* __restrict__ active, uint32_t t0,
+                                                          int32_t steps) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (pop::const_entry, population.h)
+  const auto& en = pop::const_entry(tab, active[blockIdx.y]);
+  KParams p = en.kp;
+  p.kc = kc;
+  RollArgs a = en.a;
+  a.t0 = t0;
+  a.steps = steps;
+  const float* __restrict__ packed = en.packed;
+  if constexpr (SPEC) {
+    constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
+    rollout_body<KIND, CTBR, NT>(K, p, packed, a);
+  } else {
+    rollout_body<KIND, CTBR, NT>(*kc, p, packed, a);
+  }
+#endif
+}
+
+template <int KIND, bool CTBR, int NT, bool SPEC>
+hipError_t launch_pop(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active, int count, int n,
+                      uint32_t t0, int32_t steps, hipStream_t s) {
+  static bool opted[64] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  const int bytes = LDS_F * int(sizeof(float));
+  if (!opted[dev]) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_rollout<KIND, CTBR, NT, SPEC>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return e;
+    opted[dev] = true;
+  }
+  hipLaunchKernelGGL((k_pop_rollout<KIND, CTBR, NT, SPEC>), dim3((n + RBLOCK - 1) / RBLOCK, count), dim3(512 / NT),
+                     bytes, s, kc, tab, active, t0, steps);
+  return hipGetLastError();
+}
+
+int rollout_nt() {
+  const char* v = std::getenv("QUADENV_ROLLOUT_NT");  // A/B override: 1 or 2 tiles per wave
+  return v && std::atoi(v) == 1 ? 1 : (v && std::atoi(v) == 2 ? 2 : ROLLOUT_NT_DEFAULT);
+}
+
 }  // namespace
+
+hipError_t pop::launch_pop_rollout(const KConsts<float>* kc, const RollEntry* tab, const int32_t* active, int count,
+                                   int n, int env_kind, bool ctbr, bool spec, uint32_t t0, int32_t steps,
+                                   hipStream_t s) {
+  const int nt = rollout_nt();
+  return with_kind(env_kind == QUAD_ENV_TRAJ, ctbr, [&](auto kind, auto cb) {
+    return with_bool(nt == 1, [&](auto one) {
+      return with_bool(spec, [&](auto sp) {
+        return launch_pop<decltype(kind)::value, decltype(cb)::value, decltype(one)::value ? 1 : 2,
+                          decltype(sp)::value>(kc, tab, active, count, n, t0, steps, s);
+      });
+    });
+  });
+}
 
 hipError_t launch_rollout(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
                           const float* packed, const RollArgs& a, hipStream_t s) {
-  const char* v = std::getenv("QUADENV_ROLLOUT_NT");  // A/B override: 1 or 2 tiles per wave
-  const int nt = v && std::atoi(v) == 1 ? 1 : (v && std::atoi(v) == 2 ? 2 : ROLLOUT_NT_DEFAULT);
+  const int nt = rollout_nt();
   return with_kind(env_kind == QUAD_ENV_TRAJ, ctbr, [&](auto kind, auto cb) {
     return with_bool(nt == 1, [&](auto one) {
       return with_bool(spec, [&](auto sp) {
