@@ -532,6 +532,34 @@ typedef struct QuadPolicyAct {
 } QuadPolicyAct;
 int quad_policy_act(const float* packed, const QuadPolicyAct* a, int32_t n, void* stream);
 
+/* ---- A deterministic actor of any supported architecture on MFMA: mean = W3 act(W2 act(W1 x +
+ * b1) + b2) + b3 with 12-D observations and 4 outputs, h1 a multiple of 32 in [32, 512], h2 in {64, 128, 256},
+ * act ReLU or tanh -- the reference's optimize.py family and SB3's MlpPolicy default. Forward path only (no
+ * critic, no sampling, no log-probs): evaluation episodes, waypoint laps, the deployed observation path.
+ * The arithmetic is quad_policy_act's (three-piece bf16 splits, six piece products, f32 accumulation).
+ * Parameter pointers are device fp32 in torch's nn.Linear layout ([out, in] row-major): w0 [h1,12] b0 [h1]
+ * w1 [h2,h1] b1 [h2] w2 [4,h2] b2 [4]. An arch outside the family is QUAD_EINVAL (quad_actor_packed_floats: < 0).
+ * The added entry points did not change the ABI version. */
+enum { QUAD_ACTFN_RELU = 0, QUAD_ACTFN_TANH = 1 };
+typedef struct QuadActorArch { int32_t h1, h2, activation; } QuadActorArch;
+typedef struct QuadActorParams { const float *w0, *b0, *w1, *b1, *w2, *b2; } QuadActorParams;
+/* Size (floats) of the packed image quad_actor_pack writes for this arch. */
+int64_t quad_actor_packed_floats(const QuadActorArch* arch);
+/* Repack the parameters into the fragment order the actor kernels read (stream-ordered). `packed`: device,
+ * 16-byte aligned, quad_actor_packed_floats(arch) floats. */
+int quad_actor_pack(const QuadActorArch* arch, const QuadActorParams* p, float* packed, void* stream);
+/* mean [n,4] (or NULL) and actions_env [n,4] = clip(mean, -1, 1) (16-byte aligned; a NaN mean gives -1) of
+ * obs [n,12]. A row's result does not depend on n or on the other rows. */
+int quad_actor_act(const QuadActorArch* arch, const float* packed, const float* obs, float* mean,
+                   float* actions_env, int32_t n, void* stream);
+/* quad_policy_episode / quad_policy_waypoints with this actor: the same semantics, argument checks, status
+ * codes and trace rules, and the same contract -- bit-identical, for every env up to its last step, to their
+ * loops on a second handle with quad_actor_act in quad_policy_act's place. `packed`: quad_actor_pack's image. */
+int quad_actor_episode(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                       void* stream);
+int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                         const QuadWaypointRun* wr, void* stream);
+
 /* Finish the pending step (end of a rollout): the epilogue for row (t-1) % rows if the cursor
  * marks one pending, then clears the mark. A no-op otherwise. */
 int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* cursor, int32_t n,

@@ -147,6 +147,20 @@ class QuadPolicyRun(C.Structure):
                 ("trace_vel_est", C.c_void_p), ("metrics", QuadPidMetrics), ("vel_err_sq", C.c_void_p)]
 
 
+# the general actor (quad_actor_*): 12 -> h1 -> h2 -> 4, h1 a multiple of 32 up to 512, h2 in ACTOR_H2
+ACTFN_RELU, ACTFN_TANH = 0, 1
+ACTFNS = {"relu": ACTFN_RELU, "tanh": ACTFN_TANH}
+ACTOR_MAX_H1, ACTOR_H2 = 512, (64, 128, 256)
+
+
+class QuadActorArch(C.Structure):
+    _fields_ = [("h1", C.c_int32), ("h2", C.c_int32), ("activation", C.c_int32)]
+
+
+class QuadActorParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
+
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -177,7 +191,9 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_clip_adam",
            "quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
            "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode",
-           "quad_deploy_obs", "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints")
+           "quad_deploy_obs", "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints",
+           "quad_actor_packed_floats", "quad_actor_pack", "quad_actor_act", "quad_actor_episode",
+           "quad_actor_waypoints")
 
 
 class QuadRollout(C.Structure):
@@ -299,6 +315,17 @@ def _declare(L):
     L.quad_policy_episode.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), vp]
     L.quad_ctrl_waypoints.argtypes = [vp, C.POINTER(QuadCtrlRun), C.POINTER(QuadWaypointRun), vp]
     L.quad_policy_waypoints.argtypes = [vp, vp, C.POINTER(QuadPolicyRun), C.POINTER(QuadWaypointRun), vp]
+    if not hasattr(L, "quad_actor_act"):  # the version number did not change with the quad_actor_* additions
+        raise QuadError(f"{LIB_PATH} was built before the general actor's entry points (quad_actor_*); rebuild it")
+    arch = C.POINTER(QuadActorArch)
+    L.quad_actor_packed_floats.argtypes = [arch]
+    L.quad_actor_packed_floats.restype = C.c_int64
+    L.quad_actor_pack.argtypes = [arch, C.POINTER(QuadActorParams), vp, vp]
+    L.quad_actor_act.argtypes = [arch, vp, vp, vp, vp, i32, vp]
+    L.quad_actor_episode.argtypes = [vp, arch, vp, C.POINTER(QuadPolicyRun), vp]
+    L.quad_actor_waypoints.argtypes = [vp, arch, vp, C.POINTER(QuadPolicyRun), C.POINTER(QuadWaypointRun), vp]
+    for n in ("quad_actor_pack", "quad_actor_act", "quad_actor_episode", "quad_actor_waypoints"):
+        getattr(L, n).restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
     L.quad_pop_detach_eval.argtypes = [vp]

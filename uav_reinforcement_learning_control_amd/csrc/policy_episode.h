@@ -51,4 +51,17 @@ hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, 
                                    const float* packed, const EpisodeArgs& a, const QuadWaypointRun& wr,
                                    hipStream_t s);
 
+// ---- the general actor's forms (actor_arch.hip; quad_actor_episode / quad_actor_waypoints): the same closed loop
+// with actor_arch.h's forward, in 64-env blocks of two one-tile waves, the constant block read from memory
+struct ActorNet {  // a checked QuadActorArch: H1 / 32, H2 / 32 (2, 4 or 8), tanh (1) or ReLU (0)
+  int nb1, mb, tanh_act;
+};
+// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
+int actor_net_of(const QuadActorArch* a, ActorNet* out);
+hipError_t launch_actor_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, int obs_mode,
+                                const ActorNet& net, const float* packed, const EpisodeArgs& a, hipStream_t s);
+hipError_t launch_actor_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, int obs_mode,
+                                  const ActorNet& net, const float* packed, const EpisodeArgs& a,
+                                  const QuadWaypointRun& wr, hipStream_t s);
+
 }  // namespace quadenv

@@ -15,6 +15,9 @@
 // state, estimator, metric accumulators and observation stay in registers for the whole episode; the
 // packed actor is staged into LDS once. One store at the end.
 //
+// The loop itself (episode_body) lives in policy_episode_body.h with the forward as a template parameter, so the
+// general actor's kernels (actor_arch.hip) compile the same body; Net128Forward below is this file's forward.
+//
 // Two rules hold this kernel together:
 //   * A frozen env's lane keeps feeding its column of the wave's MFMA tile(s): every MFMA and
 //     permlane32_swap (fragments, net_forward) runs with the full wave outside any per-lane branch; only
@@ -39,6 +42,7 @@
 #include "env_tiles.h"
 #include "kconsts_default.h"
 #include "policy_episode.h"
+#include "policy_episode_body.h"
 #include "policy_net.h"
 #include "population.h"
 #include "quad_deploy.h"
@@ -75,104 +79,24 @@ hipError_t launch_episode_kind<QUAD_ENV_TRAJ>(const KConsts<float>* kc, const KP
 
 namespace {
 
-// k_pid_episode's store (pid.hip), for the same QuadPidMetrics layout
-__device__ __forceinline__ void store_metrics(const QuadPidMetrics& o, int i, const PidAcc& m, int32_t status) {
-  o.steps[i] = m.steps;
-  o.status[i] = status;
-  o.total_reward[i] = m.total_reward;
-  o.pos_err_sum[i] = m.pe_sum;
-  o.pos_err_sq[i] = m.pe_sq;
-  o.pos_err_max[i] = m.pe_max;
-  o.yaw_rate_abs_sum[i] = m.yr_abs_sum;
-  o.yaw_rate_sum[i] = m.yr_sum;
-  o.yaw_rate_sq[i] = m.yr_sq;
-  o.yaw_rate_abs_max[i] = m.yr_abs_max;
-  o.yaw_rate_sign_changes[i] = m.sign_changes;
-  o.yaw_rate_delta_sum[i] = m.yr_delta;
-}
-
-__device__ __forceinline__ void store_row12(float* base, uint32_t row, const float v[12]) {
-#pragma unroll
-  for (int j = 0; j < 3; j++)
-    sto(reinterpret_cast<float4*>(base), 48u * row + 16u * j, make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]));
-}
-
-// NT = 2: wave w of a block owns envs 64w .. 64w + 63 = its two MFMA tiles. NT = 1: wave w owns the 32
-// envs 32w .. 32w + 31; lanes l and l + 32 both carry env l & 31 (the same bits), the lower half stores.
-// EB: envs per block (256: k_rollout's shape; 64: one or two waves, for evaluation-sized batches).
-// the metric status of a tracker status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
-__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
-  return tracker_status == 1 ? QUAD_PID_LAP
-                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
-                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
-}
-
-// WP: the waypoint tracker runs after every committed step and ends the env's run (wr: the kernel's
-// QuadWaypointRun; never read otherwise)
-template <int KIND, bool CTBR, int NT, int MODE, int EB, bool WP>
-__device__ __forceinline__ void episode_body(const KConsts<float>& K, const KParams& p, const float* __restrict__ packed,
-                                             const EpisodeArgs& a, const QuadWaypointRun* wr) {
-  constexpr int BLK = EB * 2 / NT;
-  extern __shared__ float lds[];
-  const int w = threadIdx.x >> 6;
-  const bool h = (threadIdx.x & 32) != 0;
-  const int i_raw = blockIdx.x * EB + (NT == 2 ? int(threadIdx.x) : w * 32 + int(threadIdx.x & 31));
-  const bool ok = i_raw < p.n;
-  const bool owner = ok && (NT == 2 || !h);  // the lane that stores this env's outputs
-  // lanes past the last env shadow it (in-range loads, MFMA columns of their own) and store nothing
-  const int i = ok ? i_raw : p.n - 1;
-  const size_t n = size_t(p.n);
-
-  // ---- setup, once: env, actor image, first observation, first estimator sample
-  EnvRegs<float> e;
-  load_env(p, i, e, CTBR);
-  const uint32_t ep = Tiles(p).ldu(F_EP, env_off(uint32_t(i)));
-  const double alpha = a.est.alpha ? a.est.alpha[i] : a.est.alpha_all;
-  double est[EST_NSTATE];
-#pragma unroll
-  for (int j = 0; j < EST_NSTATE; j++) est[j] = a.est.state ? a.est.state[size_t(j) * n + size_t(i)] : 0.0;
-  stage_lds<BLK>(lds, packed);
-  stage_pieces<BLK>(lds, packed);  // the actor's W2 pieces; the critic's image rides along and is never evaluated
-  const float* log_std = packed + LDS_F;
+// the 12-128-128-4 ReLU actor of policy_net.h as episode_body's forward (policy_episode_body.h): the packed image
+// in LDS with the actor's W2 pieces, net_forward<ACT, NT>'s bits, k_policy_act's deterministic sample
+template <int NT>
+struct Net128Forward {
+  const float* __restrict__ packed;
   float sd[ACT];
+  template <int BLK>
+  __device__ __forceinline__ void stage() {
+    extern __shared__ float lds[];
+    stage_lds<BLK>(lds, packed);
+    stage_pieces<BLK>(lds, packed);  // the actor's W2 pieces; the critic's image rides along and is never evaluated
+    const float* log_std = packed + LDS_F;
 #pragma unroll
-  for (int k = 0; k < ACT; k++) sd[k] = expf(log_std[k]);
-  float ob[12], s12[12], ti[9];
-  observe(K, e, ob, s12);  // what quad_observe reports
-  target_info_of<KIND>(K, p, i, e, ep, ti);
-  double vel[3];
-  WpTrack tk = {};
-  const double* wp = nullptr;
-  int cnt = 1;
-  int32_t status = QUAD_PID_RUNNING;
-  bool run = true;
-  if constexpr (WP) {
-    tk = load_track(wr->s, i);
-    const int ws = wr->w.set_of ? wr->w.set_of[i] : 0;
-    cnt = wr->w.counts[ws];
-    wp = wr->w.points + size_t(ws) * wr->w.max_points * 3;
-    run = tk.status == 0;  // finished in an earlier run: no step, env, estimator and tracker as they are
-    status = metric_status_of(tk.status);
-    // a resumed run: the estimator already holds this instant's sample (a second one, dt = 0, would restart it)
-    const double ts = double(e.step) * a.est_dt;
-    if (run && !(est[7] != 0.0 && est[3] == ts)) {
-      vel_est_update(alpha, a.est.max_dt, s12, ts, est, vel);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 3; j++) vel[j] = est[4 + j];
-    }
-  } else {
-    vel_est_update(alpha, a.est.max_dt, s12, double(e.step) * a.est_dt, est, vel);
+    for (int k = 0; k < ACT; k++) sd[k] = expf(log_std[k]);
   }
-  if (MODE == QUAD_OBS_DEPLOYED) deploy_obs(K.obs_lo, K.obs_span, K.obs_rspan, s12, e.target, vel, ob);
-
-  PidAcc m;
-  double verr = 0.0;
-  const uint32_t M = uint32_t(a.trace_envs);
-  const bool traced = owner && uint32_t(i) < M;
-  for (int t = 0; t < a.max_steps; t++) {
-    if (!__any(run)) break;  // wave-uniform: the whole wave leaves together
-    // ---- policy: the actor on the wave's tile(s), full wave (frozen lanes feed their columns too)
+  __device__ __forceinline__ void operator()(const float (&ob)[12], float (&act)[ACT]) const {
+    extern __shared__ float lds[];
+    const bool h = (threadIdx.x & 32) != 0;
     float xb[NT][8], mean[NT][ACT];
     fragments<NT>(ob, xb);
     {
@@ -184,91 +108,26 @@ __device__ __forceinline__ void episode_body(const KConsts<float>& K, const KPar
       pipe_start<NT, true>(lds, o, xp, st);  // net_forward<ACT, NT> with the W2 pieces from LDS: the same bits
       net_core<ACT, NT, false, 0, true>(lds, o, o, xp, st, mean);
     }
-    float ac[ACT];
 #pragma unroll
     for (int k = 0; k < ACT; k++) {
       const float mk = (NT == 2 && h) ? mean[NT - 1][k] : mean[0][k];
-      const float act = mk + sd[k] * 0.f;  // k_policy_act's sample with deterministic = 1 (z = 0)
-      ac[k] = fminf(fmaxf(act, -1.f), 1.f);
-    }
-    // ---- env step on a copy; a frozen env keeps its state
-    EnvRegs<float> en = e;
-    StepRes r;
-    env_step<float, CTBR>(K, en, ac, r);
-    if (run) {
-      if (traced) {
-        const uint32_t row = uint32_t(t) * M + uint32_t(i);  // < 2^32 / 48: checked by quad_policy_episode
-        if (a.trace_actions) sto(reinterpret_cast<float4*>(a.trace_actions), 16u * row, make_float4(ac[0], ac[1], ac[2], ac[3]));
-        if (a.trace_obs) store_row12(a.trace_obs, row, ob);
-      }
-      const float tgt[3] = {ti[0], ti[1], ti[2]};  // the target read before the step
-      e = en;
-#pragma unroll
-      for (int j = 0; j < 12; j++) { s12[j] = r.state12[j]; ob[j] = r.obs[j]; }
-      int flown = 0;
-      if constexpr (WP) {  // the env's observation above keeps the target the step was flown with
-        flown = tk.wp_idx;
-        float nt[3];
-        if (wp_update(wp, cnt, wr->w.reach_radius, s12, r.reward, r.term, r.trunc, tk, nt)) {
-#pragma unroll
-          for (int j = 0; j < 3; j++) e.target[j] = nt[j];
-        }
-      }
-      target_info_of<KIND>(K, p, i, e, ep, ti);
-      pid_acc_step(m, s12, tgt, r.reward);
-      vel_est_update(alpha, a.est.max_dt, s12, double(e.step) * a.est_dt, est, vel);
-      {  // |v_est - v_true|^2 of the post-step sample, summed over the axes in order, float64
-#pragma clang fp contract(off)
-        const double d0 = vel[0] - double(s12[6]), d1 = vel[1] - double(s12[7]), d2 = vel[2] - double(s12[8]);
-        verr += (d0 * d0 + d1 * d1) + d2 * d2;
-      }
-      if (MODE == QUAD_OBS_DEPLOYED) deploy_obs(K.obs_lo, K.obs_span, K.obs_rspan, s12, e.target, vel, ob);
-      if (traced) {
-        const uint32_t row = uint32_t(t) * M + uint32_t(i);
-        if (a.trace_state12) store_row12(a.trace_state12, row, s12);
-        if (a.trace_vel_est) {
-#pragma unroll
-          for (int j = 0; j < 3; j++) sto(a.trace_vel_est, 12u * row + 4u * j, float(vel[j]));
-        }
-        if constexpr (WP) {
-          if (wr->trace_reward) sto(wr->trace_reward, 4u * row, r.reward);
-          if (wr->trace_wp_idx) sto(wr->trace_wp_idx, 4u * row, int32_t(flown));
-        }
-      }
-      if constexpr (WP) {
-        if (tk.status != 0) {
-          status = metric_status_of(tk.status);
-          run = false;
-        }
-      } else if (r.term || r.trunc) {
-        status = r.term ? QUAD_PID_TERMINATED : QUAD_PID_TRUNCATED;
-        run = false;
-      }
+      act[k] = mk + sd[k] * 0.f;  // k_policy_act's sample with deterministic = 1 (z = 0)
     }
   }
+};
 
-  if (owner) {
-    store_env(p, i, e, CTBR);
-    if (a.est.state) {
-#pragma unroll
-      for (int j = 0; j < EST_NSTATE; j++) a.est.state[size_t(j) * n + size_t(i)] = est[j];
-    }
-    store_metrics(a.metrics, i, m, status);
-    if (a.vel_err_sq) a.vel_err_sq[i] = verr;
-    if constexpr (WP) store_track(wr->s, i, tk);
-  }
-}
 
 // SPEC: the handle's constant block is the reference default (kconsts_default.h): immediates
 template <int KIND, bool CTBR, int NT, bool SPEC, int MODE, int EB>
 __global__ __launch_bounds__(EB * 2 / NT) void k_policy_episode(const KConsts<float>* __restrict__ kc, KParams p,
                                                                 const float* __restrict__ packed, EpisodeArgs a) {
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
+  Net128Forward<NT> fw{packed};
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
-    episode_body<KIND, CTBR, NT, MODE, EB, false>(K, p, packed, a, nullptr);
+    episode_body<KIND, CTBR, NT, MODE, EB, false>(K, p, fw, a, nullptr);
   } else {
-    episode_body<KIND, CTBR, NT, MODE, EB, false>(*kc, p, packed, a, nullptr);
+    episode_body<KIND, CTBR, NT, MODE, EB, false>(*kc, p, fw, a, nullptr);
   }
 }
 
@@ -284,11 +143,12 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_pop_policy_episode(const KConst
   p.kc = kc;
   const EpisodeArgs a = en.a;
   const float* __restrict__ packed = en.packed;
+  Net128Forward<NT> fw{packed};
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, CTBR>();
-    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(K, p, packed, a, nullptr);
+    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(K, p, fw, a, nullptr);
   } else {
-    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(*kc, p, packed, a, nullptr);
+    episode_body<KIND, CTBR, NT, QUAD_OBS_ENV, EB, false>(*kc, p, fw, a, nullptr);
   }
 #endif
 }
@@ -320,11 +180,12 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_policy_waypoints(const KConsts<
                                                                   const float* __restrict__ packed, EpisodeArgs a,
                                                                   QuadWaypointRun wr) {
   p.kc = kc;
+  Net128Forward<NT> fw{packed};
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<QUAD_ENV_HOVER, CTBR>();
-    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(K, p, packed, a, &wr);
+    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(K, p, fw, a, &wr);
   } else {
-    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(*kc, p, packed, a, &wr);
+    episode_body<QUAD_ENV_HOVER, CTBR, NT, MODE, EB, true>(*kc, p, fw, a, &wr);
   }
 }
 

@@ -26,7 +26,9 @@ struct EnvView {
 };
 void env_view(const QuadHandle* h, EnvView* v);  // quadenv.hip
 // quad_policy_episode's argument checks (QUAD_EINVAL + message) and its flattened arguments; quadenv.hip
-int episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out);
+// (who: the entry point the messages name)
+int episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out,
+                 const char* who = "quad_policy_episode");
 
 // A table entry seen through the constant address space (device code only). A population table is written by
 // the host before any launch and never while one runs, so its entries are invariant for a kernel, exactly as

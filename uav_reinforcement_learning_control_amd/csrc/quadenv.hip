@@ -1422,36 +1422,45 @@ int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, 
 
 }  // extern "C"
 
-// quad_policy_episode's argument checks and its flattened arguments (also quad_pop_attach_eval's, population.hip)
-int quadenv::pop::episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out) {
-  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_policy_episode: env_kind must be HOVER or TRAJ");
-  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_policy_episode: the policy takes 12-D obs (no RELPOS)");
-  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED)
-    return fail(QUAD_EINVAL, "quad_policy_episode: unknown obs_mode");
-  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_policy_episode: max_steps must be >= 1");
+// What quad_policy_episode / quad_policy_waypoints and their quad_actor_* forms ask of the wrapper, the run and
+// the image, after the entry point's own handle checks, and the flattened arguments. who: the entry point the
+// messages name (the message is built only on failure); lap_traces: the lap call's own traces are requested.
+static int policy_run_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, bool lap_traces,
+                           EpisodeArgs* out, const char* who) {
+  const auto bad = [who](const char* m) { return fail(QUAD_EINVAL, std::string(who) + ": " + m); };
+  if (wrap_relpos(h->cfg.wrapper)) return bad("the policy takes 12-D obs (no RELPOS)");
+  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED) return bad("unknown obs_mode");
+  if (r->max_steps < 1) return bad("max_steps must be >= 1");
   const QuadPidMetrics& m = r->metrics;
   if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
       !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
       !m.yaw_rate_delta_sum)
-    return fail(QUAD_EINVAL, "quad_policy_episode: every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_policy_episode: trace_envs must be in [0, N]");
-  if (int rc = check_est(&r->est, "quad_policy_episode")) return rc;
-  if (!(r->est_dt > 0.0)) return fail(QUAD_EINVAL, "quad_policy_episode: est_dt must be > 0");
-  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est;
+    return bad("every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return bad("trace_envs must be in [0, N]");
+  if (int rc = check_est(&r->est, who)) return rc;
+  if (!(r->est_dt > 0.0)) return bad("est_dt must be > 0");
+  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || lap_traces;
   if (any_trace && r->trace_envs > 0) {
     if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return fail(QUAD_EINVAL, "quad_policy_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
     if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
          reinterpret_cast<uintptr_t>(r->trace_obs)) & 15u)
-      return fail(QUAD_EINVAL, "quad_policy_episode: the action, state12 and obs traces must be 16-byte aligned");
+      return bad("the action, state12 and obs traces must be 16-byte aligned");
   }
-  if (reinterpret_cast<uintptr_t>(packed) & 15u) return fail(QUAD_EINVAL, "quad_policy_episode: packed must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
   *out = EpisodeArgs{r->max_steps, any_trace ? r->trace_envs : 0,
                      EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
                      r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
   return QUAD_OK;
+}
+
+// quad_policy_episode's argument checks and its flattened arguments (also quad_pop_attach_eval's, population.hip)
+int quadenv::pop::episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out,
+                               const char* who) {
+  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, std::string(who) + ": env_kind must be HOVER or TRAJ");
+  return policy_run_args(h, packed, r, false, out, who);
 }
 
 extern "C" {
@@ -1507,34 +1516,46 @@ int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointR
   return QUAD_OK;
 }
 
+// quad_policy_waypoints' argument checks and its flattened arguments (who: the entry point the messages name)
+static int waypoints_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
+                          EpisodeArgs* out, const char* who) {
+  if (!h || !packed || !r || !wr) return fail(QUAD_EINVAL, "handle/packed/run/waypoints is NULL");
+  if (int rc = check_waypoint_run(h, who, wr)) return rc;
+  return policy_run_args(h, packed, r, wr->trace_reward || wr->trace_wp_idx, out, who);
+}
+
 int quad_policy_waypoints(QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
                           void* stream) {
-  if (!h || !packed || !r || !wr) return fail(QUAD_EINVAL, "handle/packed/run/waypoints is NULL");
-  if (int rc = check_waypoint_run(h, "quad_policy_waypoints", wr)) return rc;
-  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_policy_waypoints: the policy takes 12-D obs (no RELPOS)");
-  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED)
-    return fail(QUAD_EINVAL, "quad_policy_waypoints: unknown obs_mode");
-  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_policy_waypoints: max_steps must be >= 1");
-  if (!metrics_complete(r->metrics)) return fail(QUAD_EINVAL, "quad_policy_waypoints: every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_policy_waypoints: trace_envs must be in [0, N]");
-  if (int rc = check_est(&r->est, "quad_policy_waypoints")) return rc;
-  if (!(r->est_dt > 0.0)) return fail(QUAD_EINVAL, "quad_policy_waypoints: est_dt must be > 0");
-  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || wr->trace_reward ||
-                         wr->trace_wp_idx;
-  if (any_trace && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return fail(QUAD_EINVAL, "quad_policy_waypoints: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
-         reinterpret_cast<uintptr_t>(r->trace_obs)) & 15u)
-      return fail(QUAD_EINVAL, "quad_policy_waypoints: the action, state12 and obs traces must be 16-byte aligned");
-  }
-  if (reinterpret_cast<uintptr_t>(packed) & 15u) return fail(QUAD_EINVAL, "quad_policy_waypoints: packed must be 16-byte aligned");
+  EpisodeArgs a{};
+  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_policy_waypoints")) return rc;
   DeviceGuard g(h->device);
-  EpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0,
-                EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
-                r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
   HIP_TRY(launch_policy_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode, packed, a, *wr,
                                   static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- the general actor's episode and laps (kernels: actor_arch.hip): the same checks, the same arguments
+int quad_actor_episode(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                       void* stream) {
+  ActorNet net;
+  if (int rc = actor_net_of(arch, &net)) return rc;
+  EpisodeArgs a{};
+  if (int rc = quadenv::pop::episode_args(h, packed, r, &a, "quad_actor_episode")) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_actor_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net,
+                               packed, a, static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                         const QuadWaypointRun* wr, void* stream) {
+  ActorNet net;
+  if (int rc = actor_net_of(arch, &net)) return rc;
+  EpisodeArgs a{};
+  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_actor_waypoints")) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_actor_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net, packed, a, *wr,
+                                 static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

@@ -22,8 +22,10 @@ waypoint lap (:440-612). Here N evaluations run at once on the GPU:
     controllers: any two of pid / se3 / smc / lqr / model on the same episodes (``--compare A B``).
 
 Actions are ``model.predict(obs, deterministic=True)``: the Gaussian mean clipped to the action
-box (SB3 clips Box actions in predict), computed by the MFMA policy kernel for 12-D obs and by the
-torch policy otherwise (RelPosActWrapper's 7-D obs). The model is an SB3 archive (the reference's
+box (SB3 clips Box actions in predict), computed by the MFMA policy kernels for 12-D obs (the 12-128-128
+ReLU net on its own kernels, any other 12-H1-H2-4 ReLU / tanh net of the reference's family on the general
+actor, ppo.fused.fused_actor_for) and by the torch policy otherwise (RelPosActWrapper's 7-D obs, three hidden
+layers, other widths). The model is an SB3 archive (the reference's
 ``hover_policy_final.zip`` or one written by ``export.save_sb3_zip``), a ``policy.pt`` state dict or
 an ``ActorCritic``; with an archive the wrapper is read from the sibling ``config.json`` like
 evaluate.py:314-321.
@@ -61,10 +63,11 @@ def load_policy(model: Union[str, ActorCritic], device) -> tuple:
         wrapper = None if w in (None, "none") else w
     if path.endswith(".zip"):
         from .export import load_sb3_policy
-        return load_sb3_policy(path, device), wrapper
+        return load_sb3_policy(path, device, activations=("relu", "tanh")), wrapper
     sd = torch.load(path, map_location="cpu", weights_only=True)
     obs_dim = sd["mlp_extractor.policy_net.0.weight"].shape[1]
-    pol = ActorCritic(obs_dim, sd["action_net.weight"].shape[0])
+    hidden = (sd["mlp_extractor.policy_net.0.weight"].shape[0], sd["mlp_extractor.policy_net.2.weight"].shape[0])
+    pol = ActorCritic(obs_dim, sd["action_net.weight"].shape[0], hidden)  # a state dict names no activation: ReLU
     pol.load_state_dict(sd)
     return pol.to(device), wrapper
 
@@ -76,11 +79,9 @@ class _Actor:
         self.policy = policy
         self.out = torch.zeros(n, 4, device=device)
         self.fp = None
-        ex = policy.mlp_extractor
-        if ex.policy_net[0].in_features == 12 and ex.policy_net[0].out_features == 128 \
-                and ex.policy_net[2].out_features == 128:
-            from .ppo.fused import FusedPolicy
-            self.fp = FusedPolicy(policy)
+        from .ppo.fused import _net_supported, fused_actor_for
+        if _net_supported(policy):  # the 128-128 ReLU net's own kernel, the general actor for the rest of the family
+            self.fp = fused_actor_for(policy)
             self.fp.pack()
 
     @torch.no_grad()
@@ -131,13 +132,13 @@ def evaluate_waypoints(model, trajectories: Sequence = ("eight",), spacings: Seq
     """One lap per (waypoint set x replica) env, all at once. Returns per-env numpy arrays
     (name, steps, reached, laps, status, total_reward; with record=True also positions /
     actions / rewards [T, N, ...]) -- status 1 = lap completed, 2 = terminated, 3 = max steps.
-    `fused`: None flies the laps in one quad_policy_waypoints launch where that is supported (a 12-128-128-4
-    policy on a hover env with 12-D observations), else in the per-step loop; both give the same bits for
+    `fused`: None flies the laps in one quad_policy_waypoints / quad_actor_waypoints launch where that is supported
+    (a 12-H1-H2-4 policy of ppo.fused.FusedActor's family on a hover env with 12-D observations), else in the per-step loop; both give the same bits for
     every env up to its last step (the loop goes on stepping a finished env, the launch freezes it and leaves
     its later record rows zero). The launch adds "metrics" (the QuadPidMetrics arrays and vel_err_sq) and
     "pos_errors"; obs_mode="deployed" (fused only) feeds the policy the ROS2 node's observation, velocity
     estimated with `velocity_alpha` (default 0.8)."""
-    from .ppo.fused import FusedPolicy, waypoints_supported
+    from .ppo.fused import fused_actor_for, waypoints_supported
     from .waypoints import WaypointCourse
     device = torch.device(device)
     policy, cfg_wrapper = load_policy(model, device)
@@ -154,12 +155,12 @@ def evaluate_waypoints(model, trajectories: Sequence = ("eight",), spacings: Seq
     ok = waypoints_supported(policy, e)
     use = ok if fused is None else bool(fused)
     if use and not ok:
-        raise ValueError("fused=True: quad_policy_waypoints flies 12-128-128-4 policies on hover envs with 12-D "
-                         "observations")
+        raise ValueError("fused=True: the one-launch laps fly 12-H1-H2-4 policies (ppo.fused.FusedActor's family) on "
+                         "hover envs with 12-D observations")
     if obs_mode == "deployed" and not use:
         raise ValueError("obs_mode=\"deployed\" runs in the fused launch only")
     if use:
-        fp = FusedPolicy(policy)
+        fp = fused_actor_for(policy)
         fp.pack()
         m = fp.waypoints(e, course, max_steps=max_steps, obs_mode=obs_mode, trace_envs=n if record else 0,
                          alpha_all=0.8 if velocity_alpha is None else float(velocity_alpha))
@@ -251,17 +252,27 @@ def _use_fused(fused: Optional[bool], policy, e, obs_mode: str) -> bool:
     ok = episode_supported(policy, e)
     use = ok if fused is None else bool(fused)
     if use and not ok:
-        raise ValueError("fused=True: quad_policy_episode flies 12-128-128-4 policies on hover / trajectory envs "
-                         "with 12-D observations")
+        raise ValueError("fused=True: the one-launch episodes fly 12-H1-H2-4 policies (ppo.fused.FusedActor's family) "
+                         "on hover / trajectory envs with 12-D observations")
     if obs_mode == "deployed" and not use:
         raise ValueError("obs_mode=\"deployed\" runs in the fused launch only")
     return use
 
 
+def _first_obs(e, obs: torch.Tensor) -> torch.Tensor:
+    """The per-step loop's first observation: quad_observe's, which is what the one-launch episodes start from
+    (their contract, include/quadenv.h). quad_reset's returned observation is built from the drawn Euler angles,
+    quad_observe's from the stored quaternion: the attitude features differ by up to 2 ulp in about a third of
+    the envs, enough to move a return by one ulp of a step's reward now and then, so a loop started from
+    reset()'s row is not bit-identical to the launch."""
+    e.observe(out=obs)
+    return obs
+
+
 def _fused_episodes(policy, e, obs_mode: str, velocity_alpha: Optional[float]) -> dict:
-    """One quad_policy_episode launch over e's envs; the metric arrays on the host."""
-    from .ppo.fused import FusedPolicy
-    fp = FusedPolicy(policy)
+    """One quad_policy_episode / quad_actor_episode launch over e's envs; the metric arrays on the host."""
+    from .ppo.fused import fused_actor_for
+    fp = fused_actor_for(policy)
     fp.pack()
     m = fp.episode(e, obs_mode=obs_mode, alpha_all=0.8 if velocity_alpha is None else float(velocity_alpha))
     torch.cuda.synchronize(e.device)
@@ -281,7 +292,8 @@ def evaluate_episodes(model, num_episodes: int = 1024, wrapper: Optional[str] = 
     """``num_episodes`` episodes at once from HoverEnv resets, deterministic policy, each run to
     termination or truncation (evaluate.py:296-437 without the viewer). Returns per-episode
     rewards / lengths / terminated flags and their mean / std. `fused`: None flies them in one
-    quad_policy_episode launch where that is supported, else in the per-step loop (the same bits);
+    quad_policy_episode / quad_actor_episode launch where that is supported, else in the per-step loop (the same
+    bits: the loop starts from quad_observe's observation, as the launch does, see _first_obs);
     obs_mode="deployed" feeds the policy the ROS2 node's observation (velocity estimated with
     `velocity_alpha`, default 0.8; clipped) and adds vel_rmse and pos_errors."""
     device = torch.device(device)
@@ -302,6 +314,7 @@ def evaluate_episodes(model, num_episodes: int = 1024, wrapper: Optional[str] = 
             out["pos_errors"] = m["pos_err_sum"] / np.maximum(l, 1)
         return out
     act = _Actor(policy, num_episodes, device)
+    obs = _first_obs(e, obs)
     ret = torch.zeros(num_episodes, dtype=torch.float64, device=device)
     length = torch.zeros(num_episodes, dtype=torch.int32, device=device)
     running = torch.ones(num_episodes, dtype=torch.bool, device=device)
@@ -405,6 +418,7 @@ def _policy_episodes(model, num_episodes, wrapper, env, max_episode_steps, devic
         e.close()
         return pol, max_steps
     act = _Actor(policy, num_episodes, device)
+    obs = _first_obs(e, obs)
     n = num_episodes
     ret = torch.zeros(n, dtype=torch.float64, device=device)
     perr = torch.zeros(n, dtype=torch.float64, device=device)
@@ -534,7 +548,7 @@ def evaluate_velocity_estimator(model, alphas: Sequence[float] = (0.0, 0.1, 0.2)
     the deployed observation, which the reference never does. Returns {"alphas", "rmse" (per alpha:
     sqrt(sum vel_err_sq / sum steps)), "steps", "start" (the copied start states), "metrics", "table"}, with
     closed_loop=True also "mean_reward", "mean_length", "survival" and "mean_pos_error" per alpha."""
-    from .ppo.fused import FusedPolicy, episode_supported
+    from .ppo.fused import episode_supported, fused_actor_for
     device = torch.device(device)
     alphas = [float(a) for a in alphas]
     if not alphas or num_episodes < 1:
@@ -551,10 +565,11 @@ def evaluate_velocity_estimator(model, alphas: Sequence[float] = (0.0, 0.1, 0.2)
                    auto_reset=False)
     if not episode_supported(policy, e):
         e.close()
-        raise ValueError("evaluate_velocity_estimator needs a 12-128-128-4 policy on a 12-D observation env")
+        raise ValueError("evaluate_velocity_estimator needs a 12-H1-H2-4 policy (ppo.fused.FusedActor's family) on a "
+                         "12-D observation env")
     start = {k: np.tile(v, (A,) + (1,) * (v.ndim - 1)) for k, v in st.items()}
     e.set_state(**start)
-    fp = FusedPolicy(policy)
+    fp = fused_actor_for(policy)
     fp.pack()
     alpha = torch.tensor(alphas, dtype=torch.float64, device=device).repeat_interleave(E)
     m = fp.episode(e, max_steps=max_steps, obs_mode="deployed" if closed_loop else "env", alpha=alpha,

@@ -7,7 +7,7 @@ debug_training.py:94, ros2 policy_node.py:56 -- run it unchanged. Archive member
 
   data                      JSON of the algorithm attributes; entries SB3 cannot express in
                             JSON carry ``":serialized:"`` pickles (``json_to_data``): the policy
-                            class, ``policy_kwargs`` (holds ``nn.ReLU``) and the two spaces
+                            class, ``policy_kwargs`` (holds ``nn.ReLU`` or ``nn.Tanh``) and the two spaces
   policy.pth                ``ActorCriticPolicy.state_dict()`` (names already SB3's)
   policy.optimizer.pth      Adam state in SB3's parameter order (log_std first, see below)
   _stable_baselines3_version
@@ -143,8 +143,9 @@ def _serialized(obj, classes, readable: dict) -> dict:
 
 # ---- SB3 archive ------------------------------------------------------------------------------
 def _sb3_data(cfg, num_timesteps: int, n_envs: int, obs_low, obs_high, act_low, act_high,
-              net_arch, batch_size: int) -> dict:
-    policy_kwargs = {"net_arch": list(net_arch), "activation_fn": nn.ReLU}
+              net_arch, batch_size: int, activation: str = "relu") -> dict:
+    act_cls = {"relu": nn.ReLU, "tanh": nn.Tanh}[activation]
+    policy_kwargs = {"net_arch": list(net_arch), "activation_fn": act_cls}
     return {
         "policy_class": _serialized(_POLICY_CLS, [_POLICY_CLS], {
             ":type:": "<class 'abc.ABCMeta'>", "__module__": "stable_baselines3.common.policies",
@@ -152,7 +153,7 @@ def _sb3_data(cfg, num_timesteps: int, n_envs: int, obs_low, obs_high, act_low, 
         "verbose": 1,
         "policy_kwargs": _serialized(policy_kwargs, [], {
             ":type:": "<class 'dict'>", "net_arch": list(net_arch),
-            "activation_fn": "<class 'torch.nn.modules.activation.ReLU'>"}),
+            "activation_fn": f"<class 'torch.nn.modules.activation.{act_cls.__name__}'>"}),
         "num_timesteps": int(num_timesteps),
         "_total_timesteps": int(num_timesteps),
         "_num_timesteps_at_start": 0,
@@ -227,7 +228,8 @@ def save_sb3_zip(path: str, policy: ActorCritic, optimizer: Optional[torch.optim
     obs_high = np.full(obs_dim, 1.0, np.float32) if obs_high is None else obs_high
     net_arch = [m.out_features for m in policy.mlp_extractor.policy_net if isinstance(m, nn.Linear)]
     data = _sb3_data(cfg, num_timesteps, n_envs, obs_low, obs_high, np.full(act_dim, -1.0, np.float32),
-                     np.full(act_dim, 1.0, np.float32), net_arch, batch_size)
+                     np.full(act_dim, 1.0, np.float32), net_arch, batch_size,
+                     activation=getattr(policy, "activation", "relu"))
     sd = {k: v.detach().cpu().clone() for k, v in policy.state_dict().items()}
     with zipfile.ZipFile(path, "w") as z:
         z.writestr("data", json.dumps(data, indent=4))
@@ -242,9 +244,11 @@ def save_sb3_zip(path: str, policy: ActorCritic, optimizer: Optional[torch.optim
     return path
 
 
-def load_sb3_policy(path: str, device="cpu") -> ActorCritic:
+def load_sb3_policy(path: str, device="cpu", activations=("relu",)) -> ActorCritic:
     """ActorCritic from an SB3 PPO archive (the reference's train.py output). Only the JSON
-    `data` and `policy.pth` (weights_only=True) are read; no pickle in the archive is loaded."""
+    `data` and `policy.pth` (weights_only=True) are read; no pickle in the archive is loaded.
+    `activations`: the activation functions the caller can run ("relu", "tanh"); an archive with another
+    raises ValueError. The default admits what the training kernels run; evaluate.load_policy passes both."""
     with zipfile.ZipFile(path) as z:
         data = json.loads(z.read("data"))
         sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
@@ -255,9 +259,10 @@ def load_sb3_policy(path: str, device="cpu") -> ActorCritic:
     obs_dim = sd["mlp_extractor.policy_net.0.weight"].shape[1]
     act_dim = sd["action_net.weight"].shape[0]
     act = str(pk.get("activation_fn", "ReLU"))
-    if "ReLU" not in act:
-        raise ValueError(f"only ReLU policies are supported, archive has {act}")
-    pol = ActorCritic(obs_dim, act_dim, tuple(arch))
+    name = "relu" if "ReLU" in act else ("tanh" if "Tanh" in act else None)
+    if name is None or name not in activations:
+        raise ValueError(f"only {' / '.join(activations)} policies are supported here, archive has {act}")
+    pol = ActorCritic(obs_dim, act_dim, tuple(arch), activation=name)
     pol.load_state_dict(sd, strict=True)
     return pol.to(device)
 

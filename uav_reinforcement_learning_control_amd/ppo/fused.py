@@ -6,6 +6,10 @@ train.py:50-68 configures) becomes three launches -- policy (both MLPs on MFMA, 
 log-prob, clip, buffer rows), env step, epilogue (TimeLimit bootstrap, episode_starts, Monitor
 statistics) -- instead of ~25 torch kernels. The torch ActorCritic stays the trained model;
 `pack()` refreshes the kernels' copy of its parameters (call it after each update).
+
+`FusedPolicy` is the 12-128-128 ReLU net of the training kernels. `FusedActor` is the deterministic actor of any
+other supported architecture (quad_actor_*: 12-H1-H2-4, ReLU or tanh) for evaluation episodes and waypoint laps;
+`fused_actor_for(policy)` picks between the two.
 """
 from __future__ import annotations
 
@@ -28,6 +32,34 @@ def _need(t: torch.Tensor, shape, dtype, dev, name):
                          f"{t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+def _episode_run(env, dev, T: int, M: int, obs_mode, alpha, alpha_all, max_dt, est_state, laps: bool):
+    """The result tensors and the QuadPolicyRun of one fused episode / lap launch (FusedPolicy.episode's rules)."""
+    n = env.num_envs
+    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+    res["vel_err_sq"] = torch.zeros(n, dtype=torch.float64, device=dev)
+    if M > 0 and T > 0:
+        for k, w in (("actions", 4), ("obs", 12), ("state12", 12), ("vel_est", 3)):
+            res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
+        if laps:
+            res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
+            res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
+    if alpha is not None:
+        alpha = torch.as_tensor(alpha, dtype=torch.float64, device=dev).contiguous()
+        _need(alpha, (n,), torch.float64, dev, "alpha")
+    if est_state is not None:
+        _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
+    tr = lambda k: res[k].data_ptr() if k in res else None
+    run = N.QuadPolicyRun(obs_mode=N.OBS_MODES[obs_mode], max_steps=T, trace_envs=M,
+                          est=N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
+                                           state=_p(est_state)),
+                          est_dt=float(env.dt), trace_actions=tr("actions"), trace_state12=tr("state12"),
+                          trace_obs=tr("obs"), trace_vel_est=tr("vel_est"),
+                          metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
+                          vel_err_sq=res["vel_err_sq"].data_ptr())
+    run._keep = (alpha, est_state)  # the launch reads them: alive as long as the descriptor
+    return res, run
+
+
 class FusedPolicy:
     """Packed fp32 image of an ActorCritic (12 -> 128 -> 128 -> 4 / 1) for the MFMA kernels."""
 
@@ -38,6 +70,8 @@ class FusedPolicy:
                                                   ex.value_net[2], policy.action_net, policy.value_net)]
         if shapes != [(128, 12), (128, 128), (128, 12), (128, 128), (4, 128), (1, 128)]:
             raise ValueError(f"the MFMA policy kernels are built for 12-128-128-(4|1) nets, got {shapes}")
+        if getattr(policy, "activation", "relu") != "relu":
+            raise ValueError(f"the MFMA policy kernels are built for ReLU nets, got {policy.activation!r}")
 
     def __init__(self, policy: ActorCritic):
         self._check_shapes(policy)
@@ -160,27 +194,8 @@ class FusedPolicy:
         QuadPidMetrics fields and "vel_err_sq" ([N]); with trace_envs = M > 0 also "actions" [T, M, 4], "obs"
         and "state12" [T, M, 12] and "vel_est" [T, M, 3] of the first M envs (rows past an env's last step
         stay zero)."""
-        n, dev = env.num_envs, self.device
-        T = int(env.max_episode_steps if max_steps is None else max_steps)
-        M = int(trace_envs)
-        res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
-        res["vel_err_sq"] = torch.zeros(n, dtype=torch.float64, device=dev)
-        if M > 0 and T > 0:
-            for k, w in (("actions", 4), ("obs", 12), ("state12", 12), ("vel_est", 3)):
-                res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
-        if alpha is not None:
-            alpha = torch.as_tensor(alpha, dtype=torch.float64, device=dev).contiguous()
-            _need(alpha, (n,), torch.float64, dev, "alpha")
-        if est_state is not None:
-            _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
-        tr = lambda k: res[k].data_ptr() if k in res else None
-        run = N.QuadPolicyRun(obs_mode=N.OBS_MODES[obs_mode], max_steps=T, trace_envs=M,
-                              est=N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
-                                               state=_p(est_state)),
-                              est_dt=float(env.dt), trace_actions=tr("actions"), trace_state12=tr("state12"),
-                              trace_obs=tr("obs"), trace_vel_est=tr("vel_est"),
-                              metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
-                              vel_err_sq=res["vel_err_sq"].data_ptr())
+        res, run = _episode_run(env, self.device, int(env.max_episode_steps if max_steps is None else max_steps),
+                                int(trace_envs), obs_mode, alpha, alpha_all, max_dt, est_state, laps=False)
         N.check(N.lib().quad_policy_episode(env._h, _p(self.packed), C.byref(run), self._stream()),
                 "quad_policy_episode")
         return res
@@ -195,44 +210,115 @@ class FusedPolicy:
         episode()'s tensors (status PID_LAP where the lap was completed) and, with trace_envs = M > 0, also
         "rewards" [T, M] and "flown_wp" [T, M] (the waypoint each step flew toward). The tracker arrays are
         course.tracker."""
-        n, dev = env.num_envs, self.device
-        T, M = int(max_steps), int(trace_envs)
-        res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
-        res["vel_err_sq"] = torch.zeros(n, dtype=torch.float64, device=dev)
-        if M > 0 and T > 0:
-            for k, w in (("actions", 4), ("obs", 12), ("state12", 12), ("vel_est", 3)):
-                res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
-            res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
-            res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
-        if alpha is not None:
-            alpha = torch.as_tensor(alpha, dtype=torch.float64, device=dev).contiguous()
-            _need(alpha, (n,), torch.float64, dev, "alpha")
-        if est_state is not None:
-            _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
-        tr = lambda k: res[k].data_ptr() if k in res else None
-        run = N.QuadPolicyRun(obs_mode=N.OBS_MODES[obs_mode], max_steps=T, trace_envs=M,
-                              est=N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
-                                               state=_p(est_state)),
-                              est_dt=float(env.dt), trace_actions=tr("actions"), trace_state12=tr("state12"),
-                              trace_obs=tr("obs"), trace_vel_est=tr("vel_est"),
-                              metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
-                              vel_err_sq=res["vel_err_sq"].data_ptr())
+        res, run = _episode_run(env, self.device, int(max_steps), int(trace_envs), obs_mode, alpha, alpha_all, max_dt,
+                                est_state, laps=True)
         wr = course.run(res.get("rewards"), res.get("flown_wp"))
         N.check(N.lib().quad_policy_waypoints(env._h, _p(self.packed), C.byref(run), C.byref(wr), self._stream()),
                 "quad_policy_waypoints")
         return res
 
 
+class FusedActor:
+    """The deterministic actor of an ActorCritic of any supported architecture (12 -> H1 -> H2 -> 4, H1 a multiple
+    of 32 up to 512, H2 in {64, 128, 256}, ReLU or tanh) on the general MFMA actor (csrc/actor_arch.h, quad_actor_*):
+    the forward path only -- act, whole episodes and waypoint laps in one launch. The critic is not packed."""
+
+    @staticmethod
+    def arch_of(policy) -> N.QuadActorArch:
+        """The module's QuadActorArch; ValueError for a net outside the family."""
+        net = policy.mlp_extractor.policy_net
+        lin = [m for m in net if isinstance(m, torch.nn.Linear)]
+        shapes = [tuple(l.weight.shape) for l in lin] + [tuple(policy.action_net.weight.shape)]
+        act = getattr(policy, "activation", "relu")
+        ok = (len(lin) == 2 and len(net) == 4 and shapes[0][1] == 12 and shapes[2] == (4, shapes[1][0])
+              and shapes[1][1] == shapes[0][0] and shapes[0][0] % 32 == 0 and 32 <= shapes[0][0] <= N.ACTOR_MAX_H1
+              and shapes[1][0] in N.ACTOR_H2 and act in N.ACTFNS)
+        if not ok:
+            raise ValueError("the general MFMA actor flies 12-H1-H2-4 nets (H1 a multiple of 32 up to 512, H2 in "
+                             f"{N.ACTOR_H2}, relu / tanh), got {shapes} {act!r}")
+        return N.QuadActorArch(h1=shapes[0][0], h2=shapes[1][0], activation=N.ACTFNS[act])
+
+    def __init__(self, policy: ActorCritic):
+        self.arch = self.arch_of(policy)
+        self.policy = policy
+        self.device = policy.log_std.device
+        if self.device.type != "cuda":
+            raise N.QuadError("FusedActor needs the policy on a ROCm GPU")
+        nf = N.lib().quad_actor_packed_floats(C.byref(self.arch))
+        if nf <= 0:
+            raise N.QuadError("quad_actor_packed_floats rejected the architecture")
+        self.packed = torch.empty(nf, dtype=torch.float32, device=self.device)
+
+    _stream = FusedPolicy._stream
+
+    @torch.no_grad()
+    def pack(self) -> None:
+        pol, net = self.policy, self.policy.mlp_extractor.policy_net
+        ts = [net[0].weight, net[0].bias, net[2].weight, net[2].bias, pol.action_net.weight, pol.action_net.bias]
+        for t in ts:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("policy parameters must be contiguous float32")
+        prm = N.QuadActorParams(*[t.data_ptr() for t in ts])
+        N.check(N.lib().quad_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed), self._stream()),
+                "quad_actor_pack")
+
+    def act(self, obs: torch.Tensor, actions_env: torch.Tensor, mean: Optional[torch.Tensor] = None, *,
+            deterministic: bool = True) -> None:
+        """quad_actor_act: actions_env = clip(mean(obs), -1, 1), and the mean itself into `mean` unless None."""
+        if not deterministic:
+            raise ValueError("FusedActor is the deterministic actor: sampling runs on FusedPolicy or in torch")
+        n, dev, f32 = obs.shape[0], self.device, torch.float32
+        _need(obs, (n, 12), f32, dev, "obs")
+        _need(actions_env, (n, 4), f32, dev, "actions_env")
+        if mean is not None:
+            _need(mean, (n, 4), f32, dev, "mean")
+        N.check(N.lib().quad_actor_act(C.byref(self.arch), _p(self.packed), _p(obs), _p(mean), _p(actions_env), n,
+                                       self._stream()), "quad_actor_act")
+
+    def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
+                max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
+        """quad_actor_episode: FusedPolicy.episode with this actor (the same arguments, the same tensors)."""
+        res, run = _episode_run(env, self.device, int(env.max_episode_steps if max_steps is None else max_steps),
+                                int(trace_envs), obs_mode, alpha, alpha_all, max_dt, est_state, laps=False)
+        N.check(N.lib().quad_actor_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), self._stream()),
+                "quad_actor_episode")
+        return res
+
+    def waypoints(self, env, course, *, max_steps: int = 5000, obs_mode="env", alpha=None, alpha_all: float = 0.8,
+                  max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
+        """quad_actor_waypoints: FusedPolicy.waypoints with this actor."""
+        res, run = _episode_run(env, self.device, int(max_steps), int(trace_envs), obs_mode, alpha, alpha_all, max_dt,
+                                est_state, laps=True)
+        wr = course.run(res.get("rewards"), res.get("flown_wp"))
+        N.check(N.lib().quad_actor_waypoints(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), C.byref(wr),
+                                             self._stream()), "quad_actor_waypoints")
+        return res
+
+
+def fused_actor_for(policy):
+    """The fused forward of `policy`: a FusedPolicy for the 12-128-128 ReLU net (the specialised kernels, the bits
+    every existing path has), a FusedActor for any other member of the family; ValueError outside it."""
+    try:
+        FusedPolicy._check_shapes(policy)
+    except (ValueError, AttributeError, IndexError, TypeError):
+        return FusedActor(policy)
+    return FusedPolicy(policy)
+
+
 def _net_supported(policy) -> bool:
     try:
         FusedPolicy._check_shapes(policy)
     except (ValueError, AttributeError, IndexError, TypeError):
-        return False
+        try:
+            FusedActor.arch_of(policy)
+        except (ValueError, AttributeError, IndexError, TypeError):
+            return False
     return policy.log_std.device.type == "cuda"
 
 
 def episode_supported(policy, env) -> bool:
-    """quad_policy_episode flies a 12-128-128-4 actor on hover / trajectory envs (12-D obs), with or without
+    """quad_policy_episode / quad_actor_episode fly a 12-H1-H2-4 actor of the supported family (FusedActor; the
+    12-128-128-4 ReLU net on its own kernels) on hover / trajectory envs (12-D obs), with or without
     RateControlWrapper; the handle's auto-reset setting does not matter."""
     cfg = getattr(env, "cfg", None)
     return (cfg is not None and getattr(env, "_h", None) is not None
@@ -241,7 +327,8 @@ def episode_supported(policy, env) -> bool:
 
 
 def waypoints_supported(policy, env) -> bool:
-    """quad_policy_waypoints: episode_supported on a hover env (a switch overwrites the target register)."""
+    """quad_policy_waypoints / quad_actor_waypoints: episode_supported on a hover env (a switch overwrites the
+    target register)."""
     return episode_supported(policy, env) and env.cfg.env_kind == N.ENV_HOVER
 
 

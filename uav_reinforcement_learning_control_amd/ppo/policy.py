@@ -1,5 +1,6 @@
 """Actor-critic matching SB3's ActorCriticPolicy as configured by the reference (train.py:50-68):
-net_arch [128, 128], ReLU, separate policy / value MLPs, state-independent log_std (init 0),
+net_arch [128, 128], ReLU (any widths and ReLU or Tanh on request: the reference's optimize.py family),
+separate policy / value MLPs, state-independent log_std (init 0),
 orthogonal init (gain sqrt(2) hidden, 0.01 action head, 1 value head, zero biases), diagonal
 Gaussian actions (not squashed; clipped to the action box only when sent to the env).
 
@@ -62,26 +63,32 @@ def _trunk(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
     return x
 
 
-def _mlp(in_dim: int, hidden=(128, 128)) -> nn.Sequential:
+ACTIVATIONS = {"relu": nn.ReLU, "tanh": nn.Tanh}  # the reference's optimize.py choices (SB3's activation_fn)
+
+
+def _mlp(in_dim: int, hidden=(128, 128), activation: str = "relu") -> nn.Sequential:
     layers, d = [], in_dim
     for h in hidden:
-        layers += [nn.Linear(d, h), nn.ReLU()]
+        layers += [nn.Linear(d, h), ACTIVATIONS[activation]()]
         d = h
     return nn.Sequential(*layers)
 
 
 class MlpExtractor(nn.Module):
-    def __init__(self, obs_dim: int, hidden=(128, 128)):
+    def __init__(self, obs_dim: int, hidden=(128, 128), activation: str = "relu"):
         super().__init__()
-        self.policy_net = _mlp(obs_dim, hidden)
-        self.value_net = _mlp(obs_dim, hidden)
+        self.policy_net = _mlp(obs_dim, hidden, activation)
+        self.value_net = _mlp(obs_dim, hidden, activation)
 
 
 class ActorCritic(nn.Module):
     def __init__(self, obs_dim: int = 12, act_dim: int = 4, hidden=(128, 128),
-                 log_std_init: float = 0.0):
+                 log_std_init: float = 0.0, activation: str = "relu"):
         super().__init__()
-        self.mlp_extractor = MlpExtractor(obs_dim, hidden)
+        if activation not in ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, got {activation!r}")
+        self.activation = activation
+        self.mlp_extractor = MlpExtractor(obs_dim, hidden, activation)
         self.action_net = nn.Linear(hidden[-1], act_dim)
         self.value_net = nn.Linear(hidden[-1], 1)
         self.log_std = nn.Parameter(torch.full((act_dim,), float(log_std_init)))

@@ -50,6 +50,7 @@ class PPOConfig:
     max_grad_norm: float = 0.5
     normalize_advantage: bool = True
     net_arch: tuple = (128, 128)
+    activation: str = "relu"              # "relu" | "tanh" (SB3 activation_fn); tanh trains on the torch path
     adam_eps: float = 1e-5
     fused_policy: bool = True             # rollout policy on the MFMA kernels (ppo/fused.py)
     fused_rollout: bool = True            # whole rollout as quad_rollout launches (needs fused_policy)
@@ -195,7 +196,8 @@ class PPO:
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)  # identical policy init on every rank
         self.obs_dim = int(getattr(env, "obs_dim", 12))
-        self.policy = (policy or ActorCritic(self.obs_dim, 4, self.cfg.net_arch)).to(self.device)
+        self.policy = (policy or ActorCritic(self.obs_dim, 4, self.cfg.net_arch,
+                                                activation=self.cfg.activation)).to(self.device)
         self.params = [p for p in self.policy.parameters()]
         if self.world > 1:
             broadcast_parameters_(self.params, 0)
@@ -232,8 +234,10 @@ class PPO:
         self._graph = None
         # fused path: cursor {t, pending} (buffer row = t % n_steps; t keys the action noise),
         # per-block episode-statistic slots, the epilogue descriptor
-        # (the MFMA kernels are built for the 12-D HoverEnv obs and 128-128 nets)
-        fusable = self.obs_dim == 12 and tuple(self.cfg.net_arch) == (128, 128)
+        # (the MFMA training kernels are built for the 12-D HoverEnv obs and 128-128 ReLU nets; any other config
+        # trains on the torch path, and its evaluations fly on the general actor: fused.fused_actor_for)
+        fusable = (self.obs_dim == 12 and tuple(self.cfg.net_arch) == (128, 128) and self.cfg.activation == "relu"
+                   and getattr(self.policy, "activation", "relu") == "relu")
         self._fp = FusedPolicy(self.policy) if self.cfg.fused_policy and fusable else None
         self._cursor = torch.zeros(4, dtype=torch.int32, device=self.device)
         self._slots = torch.zeros(N.POLICY_STAT_SLOTS, 3, dtype=torch.float64, device=self.device)

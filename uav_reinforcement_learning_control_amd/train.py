@@ -35,6 +35,10 @@ def parse(argv=None):
     ap.add_argument("--n-epochs", type=int, default=20)
     ap.add_argument("--n-minibatches", type=int, default=128)
     ap.add_argument("--learning-rate", type=float, default=PPOConfig.learning_rate)
+    ap.add_argument("--net-arch", nargs=2, type=int, default=[128, 128], metavar=("H1", "H2"),
+                    help="hidden widths of both MLPs (the reference's optimize.py: 128 128, 256 256, 512 256); "
+                         "anything but 128 128 relu trains on the torch path")
+    ap.add_argument("--activation", default="relu", choices=["relu", "tanh"])
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-dir", default="./logs")
     ap.add_argument("--model-dir", default="./models_trained")
@@ -80,7 +84,7 @@ def run_config(a, env, cfg, model, world, stamp) -> dict:
         "ppo": {"learning_rate": cfg.learning_rate, "n_steps": cfg.n_steps, "batch_size": model.batch,
                 "n_epochs": cfg.n_epochs, "gamma": cfg.gamma, "gae_lambda": cfg.gae_lambda,
                 "clip_range": cfg.clip_range, "ent_coef": cfg.ent_coef, "net_arch": list(cfg.net_arch),
-                "activation_fn": "ReLU"},
+                "activation_fn": {"relu": "ReLU", "tanh": "Tanh"}[cfg.activation]},
         "env": a.env,
         "backend": "uav_reinforcement_learning_control_amd (MI355X kernels)",
     }
@@ -162,7 +166,7 @@ def main(argv=None):
     env = QuadVecEnv(a.num_envs, env=a.env, wrapper=wrapper, device=f"cuda:{local}",
                      seed=a.seed, env_id_base=rank * a.num_envs)
     cfg = PPOConfig(learning_rate=a.learning_rate, n_steps=a.n_steps, n_epochs=a.n_epochs,
-                    n_minibatches=a.n_minibatches)
+                    n_minibatches=a.n_minibatches, net_arch=tuple(a.net_arch), activation=a.activation)
     model = PPO(env, cfg, seed=a.seed)
     if a.resume:
         model.load_state_dict(torch.load(a.resume, map_location=env.device, weights_only=True))
