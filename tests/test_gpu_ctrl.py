@@ -1,6 +1,7 @@
 """The controller family (SE(3), sliding mode, LQR) on the GPU: k_ctrl_act against the reference controllers'
 recorded calls, the fused episode kernel against the unfused loop (bit for bit), against quad_pid_episode
-for the PID laws (bit for bit), against the reference's recorded episodes, per-env parameter sets, argument
+for the PID laws (bit for bit: the same kernel body of csrc/ctrl.hip on 22-double gain rows), against the
+reference's recorded episodes, per-env parameter sets, argument
 checks, the comparison and the tuner.
 
 N = 130 is two full 64-thread blocks of k_ctrl_episode plus a ragged one; 514 rows are two full 256-thread

@@ -1,9 +1,10 @@
-"""The cascaded PID baseline on the GPU: k_pid_act against the reference controllers' recorded calls,
-the fused episode kernel against the unfused loop (bit for bit), against the CPU loop (float64 oracle
-env + tests/pid_ref.py) and against the reference's own episodes, its metrics, per-env gain sets,
-argument checks, the tuner and the controller comparison.
+"""The cascaded PID baseline on the GPU (quad_pid_*: the controller kernels of csrc/ctrl.hip on gain rows): the
+law alone against the reference controllers' recorded calls, the fused episode kernel against the unfused loop
+(bit for bit), against the CPU loop (float64 oracle env + tests/pid_ref.py) and against the reference's own
+episodes, its metrics, per-env gain sets, the gain rows' own output widths, argument checks, the tuner and the
+controller comparison.
 
-N = 130 is two full 64-thread blocks of k_pid_episode plus a ragged one."""
+N = 130 is two full 64-thread blocks of the episode kernel plus a ragged one."""
 import ctypes as C
 import os
 
@@ -68,7 +69,7 @@ def _three_sets():
     return [g0, g1, g2]
 
 
-# (k_pid_act and k_target_info run 256-thread blocks: NWIDE = 2 * 256 + 2 rows cross two block boundaries
+# (the act kernel and k_target_info run 256-thread blocks: NWIDE = 2 * 256 + 2 rows cross two block boundaries
 # and leave a ragged third block)
 @pytest.mark.parametrize("rows", [NENV, NWIDE])
 @pytest.mark.parametrize("mode", ["yaw", "world"])
@@ -93,6 +94,73 @@ def test_pid_act_with_scattered_gain_sets(fx, mode, rows):
         assert np.abs(a[i].astype(np.float64) - ra).max() <= ACT_TOL, i
         assert np.abs(integ[:, i] - c.integ).max() <= INTEG_TOL, i
         assert np.abs(diag[i] - rd).max() <= DIAG_TOL, i
+
+
+SENTINEL = 0x7FF8DEADBEEF1234  # a NaN no law produces; compared as bits
+
+
+def _guarded(words, guard, fill=None):
+    """One float64 allocation of words + guard doubles: (all of it as int64 bits, the leading `words` doubles).
+    The tail is the guard; the head holds `fill` or the sentinel too."""
+    buf = torch.full((words + guard,), SENTINEL, dtype=torch.int64, device=DEV)
+    head = buf[:words].view(torch.float64)
+    if fill is not None:
+        head.copy_(_cuda(fill).reshape(-1))
+    return buf, head
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int64).cpu().numpy()
+
+
+@pytest.mark.parametrize("mode", ["yaw", "world"])
+def test_pid_rows_keep_their_widths_and_equal_the_family(fx, mode):
+    """quad_pid_* run the controller family's kernels on 22-double gain rows: diag is [n,6] and integ [6][n], not
+    the family's [n,7] and [8][n]. Each output sits in one allocation with a sentinel tail (a [n,7] diag or an
+    [8][n] state block would land in it, never past it); the tails stay as they were and the outputs equal
+    quad_ctrl_*'s with the same PID law, bit for bit."""
+    law = "pid_" + mode
+    sets = _three_sets()
+    # the law alone, NWIDE rows: two 256-thread blocks plus two rows
+    n = NWIDE
+    S, T = _cuda(fx[mode + "_state"][:n]), _cuda(fx[mode + "_target9"][:n])
+    assert S.shape[0] == n
+    set_of = (np.arange(n) * 7 + 1) % 3
+    integ0 = np.random.default_rng(3).uniform(-0.005, 0.005, (6, n))
+    env = QuadVecEnv(8, device=DEV, auto_reset=False)  # the handle supplies the plant constants only
+    dbuf, dhead = _guarded(n * 6, n)
+    ibuf, ihead = _guarded(6 * n, 2 * n, integ0)
+    diag, integ = dhead.view(n, 6), ihead.view(6, n)
+    a = env.pid_act(S, T, integ, gains=sets, set_of=set_of, mode=MODE_ID[mode], diag=diag)
+    state = torch.zeros(N.CTRL_NSTATE, n, dtype=torch.float64, device=DEV)
+    state[:6] = _cuda(integ0)
+    diag7 = torch.zeros(n, N.CTRL_NDIAG, dtype=torch.float64, device=DEV)
+    ac = env.ctrl_act(S, T, state, params=sets, set_of=set_of, law=law, diag=diag7)
+    env.close()
+    assert np.all(_bits(dbuf[n * 6:]) == SENTINEL) and np.all(_bits(ibuf[6 * n:]) == SENTINEL)
+    assert not np.any(_bits(diag) == SENTINEL) and not np.array_equal(integ.cpu().numpy(), integ0)
+    assert np.array_equal(_bits(diag), _bits(diag7[:, :6])) and np.array_equal(_bits(integ), _bits(state[:6]))
+    assert np.array_equal(a.cpu().numpy().view(np.uint32), ac.cpu().numpy().view(np.uint32))
+    # the fused episode, NENV envs: two 64-thread blocks plus a ragged one, 8 steps
+    n = NENV
+    set_of = (np.arange(n) * 5) % 3
+    integ0 = np.random.default_rng(4).uniform(-0.005, 0.005, (6, n))
+    envs = [QuadVecEnv(n, device=DEV, seed=11, auto_reset=False) for _ in range(2)]
+    for e in envs:
+        e.reset()
+    ibuf, ihead = _guarded(6 * n, 2 * n, integ0)
+    integ = ihead.view(6, n)
+    f = envs[0].pid_episode(sets, set_of=set_of, mode=MODE_ID[mode], max_steps=8, integ=integ)
+    state = torch.zeros(N.CTRL_NSTATE, n, dtype=torch.float64, device=DEV)
+    state[:6] = _cuda(integ0)
+    c = envs[1].ctrl_episode(sets, set_of=set_of, law=law, max_steps=8, state=state)
+    for e in envs:
+        e.close()
+    assert np.all(_bits(ibuf[6 * n:]) == SENTINEL)
+    assert np.all(f["steps"].cpu().numpy() == 8) and not np.array_equal(integ.cpu().numpy(), integ0)
+    assert np.array_equal(_bits(integ), _bits(state[:6])) and not state[6:].any()
+    for k, _ in N.PID_METRIC_FIELDS:
+        assert np.array_equal(f[k].cpu().numpy().view(np.uint8), c[k].cpu().numpy().view(np.uint8)), k
 
 
 # ---------------------------------------------------------------------------------------------
@@ -163,7 +231,7 @@ def test_current_target_info_is_what_step_reports(kind):
 # 6. fused = unfused, bit for bit
 # (time limit 64: truncation inside the run, generic constant block; the last case keeps the default
 # 512-step limit, whose handles take the kernels with compiled-in constants)
-# (NWIDE envs: the unfused loop's k_pid_act and k_target_info run three 256-thread blocks)
+# (NWIDE envs: the unfused loop's act kernel and k_target_info run three 256-thread blocks)
 @pytest.mark.parametrize("kind,mode,T,limit,n", [("hover", "yaw_frame", 80, 64, NENV),
                                                  ("trajectory", "world_frame", 80, 64, NENV),
                                                  ("hover", "yaw_frame", 40, 64, NENV),

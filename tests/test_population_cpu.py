@@ -12,6 +12,8 @@ LAYOUT = os.path.join(REPO, "tests", "native_population", "_build", "pop_layout"
 
 
 def _layout():
+    # builds on first use, like the host shims (tests/pid_host.py): no build product has to survive under tests/
+    subprocess.run(["make", "-s", "-C", os.path.dirname(os.path.dirname(LAYOUT))], check=True)
     out = subprocess.run([LAYOUT], capture_output=True, text=True, check=True).stdout
     return {k: int(v) for k, v in (line.split() for line in out.splitlines())}
 

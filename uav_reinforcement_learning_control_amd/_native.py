@@ -124,10 +124,8 @@ class QuadCtrlParams(C.Structure):
     _fields_ = [("base", QuadPidGains), ("lqr_k", C.c_double * 3)] + [(n, C.c_double) for n in CTRL_EXTRA_FIELDS[3:]]
 
 
-class QuadCtrlRun(C.Structure):
-    _fields_ = [("params", C.c_void_p), ("set_of", C.c_void_p), ("n_sets", C.c_int32), ("law", C.c_int32),
-                ("max_steps", C.c_int32), ("trace_envs", C.c_int32), ("state", C.c_void_p),
-                ("trace_actions", C.c_void_p), ("trace_state12", C.c_void_p), ("metrics", QuadPidMetrics)]
+class QuadCtrlRun(C.Structure):  # QuadPidRun's layout, field for field, under the family's names
+    _fields_ = [({"gains": "params", "mode": "law", "integ": "state"}.get(n, n), t) for n, t in QuadPidRun._fields_]
 
 
 # the deployed observation path (policy_node.py's estimator and builder) and the policy's fused episode

@@ -143,24 +143,60 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _act(env, entry: str, table_of, rows, set_of, law_id: int, state12, target9, state, n_state: int, out, diag,
+         n_diag: int) -> torch.Tensor:
+    """pid_act / ctrl_act: the shape checks, the action rows, the table (table_of(rows, device)) and the call."""
+    n = int(state12.shape[0])
+    env._check(state12, (n, 12), torch.float32)
+    env._check(target9, (n, 9), torch.float32)
+    env._check(state, (n_state, n), torch.float64)
+    out = torch.empty(n, 4, dtype=torch.float32, device=env.device) if out is None else out
+    env._check(out, (n, 4), torch.float32)
+    if diag is not None:
+        env._check(diag, (n, n_diag), torch.float64)
+    tab = table_of(rows, env.device)
+    so = _set_of(set_of, n, env.device)
+    N.check(getattr(N.lib(), entry)(env._h, _ptr(tab), tab.shape[0], _ptr(so), law_id, _ptr(state12), _ptr(target9),
+                                    n, _ptr(state), _ptr(out), _ptr(diag), env._stream()), entry)
+    return out
+
+
+def _episode(env, entry: str, run_type, tab: torch.Tensor, set_of, law_id: int, max_steps: int, trace_envs: int,
+             state, n_state: int, course=None) -> dict:
+    """pid_episode / ctrl_episode / ctrl_waypoints after the table: the metric tensors, the trace tensors of the
+    first trace_envs envs (a lap's own when `course` is given), the run struct (run_type: N.QuadPidRun or
+    N.QuadCtrlRun, one layout) and the call."""
+    n, dev = env.num_envs, env.device
+    T, M = int(max_steps), int(trace_envs)
+    so = _set_of(set_of, n, dev)
+    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
+    if M > 0 and T > 0:
+        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
+        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
+        if course is not None:
+            res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
+            res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
+    if state is not None:
+        env._check(state, (n_state, n), torch.float64)
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+    run = run_type(ptr(tab), ptr(so), tab.shape[0], law_id, T, M, ptr(state), ptr(res.get("actions")),
+                   ptr(res.get("state12")), N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
+    args = (C.byref(run),)
+    if course is not None:
+        wr = course.run(res.get("rewards"), res.get("flown_wp"))
+        args += (C.byref(wr),)
+    N.check(getattr(N.lib(), entry)(env._h, *args, env._stream()), entry)
+    return res
+
+
 def pid_act(env, state12: torch.Tensor, target9: torch.Tensor, integ: torch.Tensor, gains: GainsLike = None,
             set_of=None, mode="yaw_frame", out: Optional[torch.Tensor] = None, diag: Optional[torch.Tensor] = None):
     """One CascadedPIDController.compute per row. state12 [n,12], target9 [n,9] float32; integ float64
     [6,n] (field-major; read and updated in place; zero it at an episode start); gains: see gain_table;
     set_of [n] int32 or None (set 0). Returns the actions [n,4] (and fills diag [n,6] float64 when given)."""
-    n = int(state12.shape[0])
-    env._check(state12, (n, 12), torch.float32)
-    env._check(target9, (n, 9), torch.float32)
-    env._check(integ, (6, n), torch.float64)
-    out = torch.empty(n, 4, dtype=torch.float32, device=env.device) if out is None else out
-    env._check(out, (n, 4), torch.float32)
-    if diag is not None:
-        env._check(diag, (n, 6), torch.float64)
-    tab = gain_table(gains, env.device)
-    so = _set_of(set_of, n, env.device)
-    N.check(N.lib().quad_pid_act(env._h, _ptr(tab), tab.shape[0], _ptr(so), MODES[mode], _ptr(state12), _ptr(target9),
-                                 n, _ptr(integ), _ptr(out), _ptr(diag), env._stream()), "quad_pid_act")
-    return out
+    return _act(env, "quad_pid_act", gain_table, gains, set_of, MODES[mode], state12, target9, integ, 6, out, diag, 6)
 
 
 def target_info(env, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -178,25 +214,9 @@ def pid_episode(env, gains: GainsLike = None, set_of=None, mode="yaw_frame", max
     then frozen, not reset. Returns the QuadPidMetrics arrays as tensors ([N]; status codes in STATUS);
     with trace_envs = M > 0 also "actions" [max_steps, M, 4] and "state12" [max_steps, M, 12] of the
     first M envs (rows past an env's last step stay zero)."""
-    n, dev = env.num_envs, env.device
-    T = int(env.max_episode_steps if max_steps is None else max_steps)
-    M = int(trace_envs)
-    tab = gain_table(gains, dev)
-    so = _set_of(set_of, n, dev)
-    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
-    if M > 0 and T > 0:
-        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
-        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
-    if integ is not None:
-        env._check(integ, (6, n), torch.float64)
-    run = N.QuadPidRun(gains=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
-                       mode=MODES[mode], max_steps=T, trace_envs=M,
-                       integ=None if integ is None else integ.data_ptr(),
-                       trace_actions=res["actions"].data_ptr() if "actions" in res else None,
-                       trace_state12=res["state12"].data_ptr() if "state12" in res else None,
-                       metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
-    N.check(N.lib().quad_pid_episode(env._h, C.byref(run), env._stream()), "quad_pid_episode")
-    return res
+    T = env.max_episode_steps if max_steps is None else max_steps
+    return _episode(env, "quad_pid_episode", N.QuadPidRun, gain_table(gains, env.device), set_of, MODES[mode], T,
+                    trace_envs, integ, 6)
 
 
 def pid_score(metrics: dict) -> dict:
@@ -318,42 +338,16 @@ def ctrl_act(env, state12: torch.Tensor, target9: torch.Tensor, state: torch.Ten
              set_of=None, law="se3", out: Optional[torch.Tensor] = None, diag: Optional[torch.Tensor] = None):
     """One compute() of the law's reference class per row. As pid_act, with `state` float64 [8,n] (the six
     integrators, v_yaw, des_wz_prev; zero it at an episode start) and diag [n,7] (des_rate 3, des_att 3, |e_R|)."""
-    n = int(state12.shape[0])
-    env._check(state12, (n, 12), torch.float32)
-    env._check(target9, (n, 9), torch.float32)
-    env._check(state, (N.CTRL_NSTATE, n), torch.float64)
-    out = torch.empty(n, 4, dtype=torch.float32, device=env.device) if out is None else out
-    env._check(out, (n, 4), torch.float32)
-    if diag is not None:
-        env._check(diag, (n, N.CTRL_NDIAG), torch.float64)
-    tab = param_table(params, env.device)
-    so = _set_of(set_of, n, env.device)
-    N.check(N.lib().quad_ctrl_act(env._h, _ptr(tab), tab.shape[0], _ptr(so), LAWS[law], _ptr(state12), _ptr(target9),
-                                  n, _ptr(state), _ptr(out), _ptr(diag), env._stream()), "quad_ctrl_act")
-    return out
+    return _act(env, "quad_ctrl_act", param_table, params, set_of, LAWS[law], state12, target9, state, N.CTRL_NSTATE,
+                out, diag, N.CTRL_NDIAG)
 
 
 def ctrl_episode(env, params: ParamsLike = None, set_of=None, law="se3", max_steps: Optional[int] = None,
                  trace_envs: int = 0, state: Optional[torch.Tensor] = None) -> dict:
     """pid_episode for any law of LAWS: the same metrics, traces and freezing rules, one launch."""
-    n, dev = env.num_envs, env.device
-    T = int(env.max_episode_steps if max_steps is None else max_steps)
-    M = int(trace_envs)
-    tab = param_table(params, dev)
-    so = _set_of(set_of, n, dev)
-    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
-    if M > 0 and T > 0:
-        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
-        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
-    if state is not None:
-        env._check(state, (N.CTRL_NSTATE, n), torch.float64)
-    run = N.QuadCtrlRun(params=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
-                        law=LAWS[law], max_steps=T, trace_envs=M, state=None if state is None else state.data_ptr(),
-                        trace_actions=res["actions"].data_ptr() if "actions" in res else None,
-                        trace_state12=res["state12"].data_ptr() if "state12" in res else None,
-                        metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
-    N.check(N.lib().quad_ctrl_episode(env._h, C.byref(run), env._stream()), "quad_ctrl_episode")
-    return res
+    T = env.max_episode_steps if max_steps is None else max_steps
+    return _episode(env, "quad_ctrl_episode", N.QuadCtrlRun, param_table(params, env.device), set_of, LAWS[law], T,
+                    trace_envs, state, N.CTRL_NSTATE)
 
 
 def ctrl_waypoints(env, course, params: ParamsLike = None, set_of=None, law="pid_world", max_steps: int = 5000,
@@ -364,26 +358,8 @@ def ctrl_waypoints(env, course, params: ParamsLike = None, set_of=None, law="pid
     metric tensors (status PID_LAP where the lap was completed); with trace_envs = M > 0 also "actions",
     "state12", "rewards" [T, M] and "flown_wp" [T, M] (the waypoint each step flew toward). The tracker arrays
     are course.tracker."""
-    n, dev = env.num_envs, env.device
-    T, M = int(max_steps), int(trace_envs)
-    tab = param_table(params, dev)
-    so = _set_of(set_of, n, dev)
-    res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.PID_METRIC_FIELDS}
-    if M > 0 and T > 0:
-        res["actions"] = torch.zeros(T, M, 4, dtype=torch.float32, device=dev)
-        res["state12"] = torch.zeros(T, M, 12, dtype=torch.float32, device=dev)
-        res["rewards"] = torch.zeros(T, M, dtype=torch.float32, device=dev)
-        res["flown_wp"] = torch.zeros(T, M, dtype=torch.int32, device=dev)
-    if state is not None:
-        env._check(state, (N.CTRL_NSTATE, n), torch.float64)
-    run = N.QuadCtrlRun(params=tab.data_ptr(), set_of=None if so is None else so.data_ptr(), n_sets=tab.shape[0],
-                        law=LAWS[law], max_steps=T, trace_envs=M, state=None if state is None else state.data_ptr(),
-                        trace_actions=res["actions"].data_ptr() if "actions" in res else None,
-                        trace_state12=res["state12"].data_ptr() if "state12" in res else None,
-                        metrics=N.QuadPidMetrics(**{k: res[k].data_ptr() for k, _ in N.PID_METRIC_FIELDS}))
-    wr = course.run(res.get("rewards"), res.get("flown_wp"))
-    N.check(N.lib().quad_ctrl_waypoints(env._h, C.byref(run), C.byref(wr), env._stream()), "quad_ctrl_waypoints")
-    return res
+    return _episode(env, "quad_ctrl_waypoints", N.QuadCtrlRun, param_table(params, env.device), set_of, LAWS[law],
+                    max_steps, trace_envs, state, N.CTRL_NSTATE, course)
 
 
 __all__ = ["PIDGains", "gain_table", "pid_act", "pid_episode", "pid_score", "target_info", "gains_from_vector",

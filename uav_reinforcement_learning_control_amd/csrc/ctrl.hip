@@ -1,17 +1,29 @@
-// ctrl.hip -- the controller family on gfx950 (the laws: quad_ctrl.h; the PID ids call quad_pid.h).
+// ctrl.hip -- the controller kernels on gfx950: the cascaded PID baseline (quad_pid_*) and the controller
+// family (quad_ctrl_*) are one kernel family (the laws: quad_pid.h, quad_ctrl.h).
 //
 // Kernels
-//   k_ctrl_act<LAW>                 the law alone over [n,12] states and [n,9] targets, caller-owned state block
-//   k_ctrl_episode<KIND, LAW, SPEC> the fused closed loop in k_pid_episode's shape (pid.hip): one thread per
-//                                   env in 64-thread blocks, env loaded once, (law -> env_step) up to
-//                                   max_steps times with the env, the eight controller states, the
-//                                   parameter set and the metric accumulators in registers, one store
-//   k_ctrl_waypoints<LAW, SPEC>     the same body with the waypoint tracker (quad_waypoints.h) after every
-//                                   step: hover kind, (law -> env_step -> tracker) until the tracker's
-//                                   status leaves 0 (quad_ctrl_waypoints)
+//   k_ctrl_act<ROW, LAW>                 the law alone over [n,12] states and [n,9] targets, caller-owned state block
+//   k_ctrl_episode<ROW, KIND, LAW, SPEC> the fused closed loop: one thread per env, env loaded once, (law ->
+//                                        env_step) up to max_steps times in registers, metrics and state stored once
+//   k_ctrl_waypoints<LAW, SPEC>          the same body with the waypoint tracker (quad_waypoints.h) after every
+//                                        step: hover kind, (law -> env_step -> tracker) until the tracker's
+//                                        status leaves 0 (quad_ctrl_waypoints)
+//   k_target_info<KIND>                  info["target" / "target_vel" / "target_acc"] for the envs' current step count
 //
-// The law is a template argument, so each instantiation keeps only its own law's parameters and state
-// rows live: the SMC rows 6-7 of the state block are loaded and stored by the SMC instantiation alone.
+// ROW is the table's row type and fixes, at compile time, the row load, the law call and the diag width:
+//   QuadPidGains    22 doubles; pid_law on the row itself; diag [n,6]          (quad_pid_act, quad_pid_episode)
+//   QuadCtrlParams  33 doubles; ctrl_law<LAW>;             diag [n,CTRL_NDIAG] (quad_ctrl_*)
+// so quad_pid_episode and quad_ctrl_episode with a PID law run the same body on the same law and give the
+// same bits. The law is a template argument too, so each instantiation keeps only its own law's parameters
+// and state rows live: the SMC rows 6-7 of the state block are loaded and stored by the SMC instantiation alone.
+//
+// The episode kernels run 64-thread blocks at every size: 65,536 envs are 1,024 waves, one per SIMD of the
+// 256 CUs, and below that a wider block would only leave CUs empty; above it the launch is
+// throughput-bound on the same per-wave chain and the block size does not enter. One wave per SIMD
+// may hold all 512 VGPRs, so the env state, the controller states, the parameter set (per lane: set_of is
+// lane-varying) and the metric accumulators stay in registers across the loop.
+// A wave leaves the loop when its last lane has finished, which is why callers lay batches out
+// candidate-major (a wave's 64 lanes share a parameter set and tend to finish together).
 #include <hip/hip_runtime.h>
 
 #include "../../include/quadenv.h"
@@ -34,9 +46,13 @@ constexpr int EP_BLOCK = 64;
 template <int LAW>
 constexpr int rows_of() { return LAW == QUAD_CTRL_SMC ? CTRL_NSTATE : 6; }
 
-template <int LAW>
-__global__ __launch_bounds__(ACT_BLOCK) void k_ctrl_act(PidPlant plant, const QuadCtrlParams* __restrict__ params,
-                                                        int32_t n_sets, const int32_t* __restrict__ set_of,
+// a gain row carries the two PID laws (LAW = the mode), calls pid_law on itself and reports pid_law's six diag columns
+template <class ROW>
+constexpr bool PID_ROW = std::is_same<ROW, QuadPidGains>::value;
+
+template <class ROW, int LAW>
+__global__ __launch_bounds__(ACT_BLOCK) void k_ctrl_act(PidPlant plant, const ROW* __restrict__ rows, int32_t n_sets,
+                                                        const int32_t* __restrict__ set_of,
                                                         const float* __restrict__ state12,
                                                         const float* __restrict__ target9, int32_t n,
                                                         double* __restrict__ state, float4* __restrict__ actions,
@@ -48,56 +64,57 @@ __global__ __launch_bounds__(ACT_BLOCK) void k_ctrl_act(PidPlant plant, const Qu
     actions[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     return;
   }
-  const QuadCtrlParams C = params[set];
+  const ROW C = rows[set];
   float s[12], t[9];
 #pragma unroll
   for (int j = 0; j < 12; j++) s[j] = state12[size_t(i) * 12 + j];
 #pragma unroll
   for (int j = 0; j < 9; j++) t[j] = target9[size_t(i) * 9 + j];
-  constexpr int ROWS = rows_of<LAW>();
+  constexpr int ROWS = rows_of<LAW>(), NDIAG = PID_ROW<ROW> ? 6 : CTRL_NDIAG;
   double cs[CTRL_NSTATE] = {};
 #pragma unroll
   for (int j = 0; j < ROWS; j++) cs[j] = state[size_t(j) * size_t(n) + size_t(i)];
   float a[4];
-  double d[CTRL_NDIAG];
-  ctrl_law<LAW>(C, plant, s, t, cs, a, d);
+  double d[NDIAG];
+  if constexpr (PID_ROW<ROW>) {
+    pid_law<LAW>(C, plant, s, t, cs, a, d);
+  } else {
+    ctrl_law<LAW>(C, plant, s, t, cs, a, d);
+  }
 #pragma unroll
   for (int j = 0; j < ROWS; j++) state[size_t(j) * size_t(n) + size_t(i)] = cs[j];
   actions[i] = make_float4(a[0], a[1], a[2], a[3]);
   if (diag) {
 #pragma unroll
-    for (int j = 0; j < CTRL_NDIAG; j++) diag[size_t(i) * CTRL_NDIAG + j] = d[j];
+    for (int j = 0; j < NDIAG; j++) diag[size_t(i) * NDIAG + j] = d[j];
   }
 }
 
-// k_pid_episode's store (pid.hip), for the same QuadPidMetrics layout
-__device__ __forceinline__ void store_metrics(const QuadPidMetrics& o, int i, const PidAcc& m, int32_t status) {
-  o.steps[i] = m.steps;
-  o.status[i] = status;
-  o.total_reward[i] = m.total_reward;
-  o.pos_err_sum[i] = m.pe_sum;
-  o.pos_err_sq[i] = m.pe_sq;
-  o.pos_err_max[i] = m.pe_max;
-  o.yaw_rate_abs_sum[i] = m.yr_abs_sum;
-  o.yaw_rate_sum[i] = m.yr_sum;
-  o.yaw_rate_sq[i] = m.yr_sq;
-  o.yaw_rate_abs_max[i] = m.yr_abs_max;
-  o.yaw_rate_sign_changes[i] = m.sign_changes;
-  o.yaw_rate_delta_sum[i] = m.yr_delta;
+// QuadPidRun / QuadCtrlRun as the kernels take it: the two have one layout, field for field, and differ in the
+// table's row type (law: the mode of a QuadPidRun; the host dispatches on it)
+template <class ROW>
+struct Run {
+  const ROW* rows;
+  const int32_t* set_of;
+  int32_t n_sets, law, max_steps, trace_envs;
+  double* state;
+  float *trace_actions, *trace_state12;
+  QuadPidMetrics metrics;
+};
+Run<QuadPidGains> run_of(const QuadPidRun& r) {
+  return {r.gains, r.set_of, r.n_sets, r.mode, r.max_steps, r.trace_envs, r.integ, r.trace_actions, r.trace_state12,
+          r.metrics};
 }
-
-// the metric status of a tracker status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
-__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
-  return tracker_status == 1 ? QUAD_PID_LAP
-                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
-                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
+Run<QuadCtrlParams> run_of(const QuadCtrlRun& r) {
+  return {r.params, r.set_of, r.n_sets, r.law, r.max_steps, r.trace_envs, r.state, r.trace_actions, r.trace_state12,
+          r.metrics};
 }
 
 // WP: the waypoint tracker runs after every step and ends the env's run (wr: the kernel's QuadWaypointRun;
 // never read otherwise)
-template <int KIND, int LAW, bool WP>
+template <class ROW, int KIND, int LAW, bool WP>
 __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const KParams& p, const PidPlant& plant,
-                                                  const QuadCtrlRun& r, const QuadWaypointRun* wr) {
+                                                  const Run<ROW>& r, const QuadWaypointRun* wr) {
   const int i = blockIdx.x * EP_BLOCK + threadIdx.x;
   if (i >= p.n) return;
   PidAcc m;
@@ -106,7 +123,7 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
     store_metrics(r.metrics, i, m, QUAD_PID_INVALID);
     return;
   }
-  const QuadCtrlParams C = r.params[set];
+  const ROW C = r.rows[set];
   WpTrack tk = {};
   const double* wp = nullptr;
   int cnt = 1;
@@ -135,7 +152,11 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
   int32_t status = QUAD_PID_RUNNING;
   for (int t = 0; t < r.max_steps; t++) {
     float a[4];
-    ctrl_law<LAW>(C, plant, s12, ti, cs, a, nullptr);
+    if constexpr (PID_ROW<ROW>) {
+      pid_law<LAW>(C, plant, s12, ti, cs, a, nullptr);
+    } else {
+      ctrl_law<LAW>(C, plant, s12, ti, cs, a, nullptr);
+    }
     const float tgt[3] = {ti[0], ti[1], ti[2]};  // the target read before the step
     StepRes sr;
     env_step<float, false>(K, e, a, sr);
@@ -153,7 +174,7 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
     target_info_of<KIND>(K, p, i, e, ep, ti);
     pid_acc_step(m, s12, tgt, sr.reward);
     if (traced) {
-      const uint32_t row = uint32_t(t) * M + uint32_t(i);  // < 2^32 / 48: checked by quad_ctrl_episode
+      const uint32_t row = uint32_t(t) * M + uint32_t(i);  // < 2^32 / 48: checked by the entry point
       if (r.trace_actions) sto(reinterpret_cast<float4*>(r.trace_actions), 16u * row, make_float4(a[0], a[1], a[2], a[3]));
       if (r.trace_state12) {
 #pragma unroll
@@ -185,79 +206,134 @@ __device__ __forceinline__ void ctrl_episode_body(const KConsts<float>& K, const
   if constexpr (WP) store_track(wr->s, i, tk);
 }
 
-template <int KIND, int LAW, bool SPEC>
+template <class ROW, int KIND, int LAW, bool SPEC>
 __global__ __launch_bounds__(EP_BLOCK) void k_ctrl_episode(const KConsts<float>* __restrict__ kc, KParams p,
-                                                           PidPlant plant, QuadCtrlRun r) {
+                                                           PidPlant plant, Run<ROW> r) {
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<KIND, false>();
-    ctrl_episode_body<KIND, LAW, false>(K, p, plant, r, nullptr);
+    ctrl_episode_body<ROW, KIND, LAW, false>(K, p, plant, r, nullptr);
   } else {
-    ctrl_episode_body<KIND, LAW, false>(*kc, p, plant, r, nullptr);
+    ctrl_episode_body<ROW, KIND, LAW, false>(*kc, p, plant, r, nullptr);
   }
 }
 
-// the WP form of k_ctrl_episode: hover kind only (a switch overwrites the target register), the tracker's
-// tables and rows in a kernel argument of its own so k_ctrl_episode's arguments stay as they are
+// the WP form of k_ctrl_episode: hover kind only (a switch overwrites the target register), QuadCtrlParams
+// rows only, the tracker's tables and rows in a kernel argument of its own
 template <int LAW, bool SPEC>
 __global__ __launch_bounds__(EP_BLOCK) void k_ctrl_waypoints(const KConsts<float>* __restrict__ kc, KParams p,
-                                                             PidPlant plant, QuadCtrlRun r, QuadWaypointRun wr) {
+                                                             PidPlant plant, Run<QuadCtrlParams> r,
+                                                             QuadWaypointRun wr) {
   p.kc = kc;
   if constexpr (SPEC) {
     constexpr KConsts<float> K = kdef_block<QUAD_ENV_HOVER, false>();
-    ctrl_episode_body<QUAD_ENV_HOVER, LAW, true>(K, p, plant, r, &wr);
+    ctrl_episode_body<QuadCtrlParams, QUAD_ENV_HOVER, LAW, true>(K, p, plant, r, &wr);
   } else {
-    ctrl_episode_body<QUAD_ENV_HOVER, LAW, true>(*kc, p, plant, r, &wr);
+    ctrl_episode_body<QuadCtrlParams, QUAD_ENV_HOVER, LAW, true>(*kc, p, plant, r, &wr);
   }
 }
 
-// f(law): law = std::integral_constant<int, QUAD_CTRL_*>; the caller has checked the range
-template <class F>
+template <int KIND>
+__global__ __launch_bounds__(ACT_BLOCK) void k_target_info(const KConsts<float>* __restrict__ kc, KParams p,
+                                                           float* __restrict__ out) {
+  p.kc = kc;
+  const int i = blockIdx.x * ACT_BLOCK + threadIdx.x;
+  if (i >= p.n) return;
+  EnvRegs<float> e;
+  load_env(p, i, e, false);
+  const uint32_t ep = Tiles(p).ldu(F_EP, env_off(uint32_t(i)));
+  float o[9];
+  target_info_of<KIND>(*kc, p, i, e, ep, o);
+#pragma unroll
+  for (int j = 0; j < 9; j++) out[size_t(i) * 9 + j] = o[j];
+}
+
+// f(law): law = std::integral_constant<int, id>, over the ids a ROW table carries (QuadPidGains: the two PID
+// modes = the two PID law ids; QuadCtrlParams: every QUAD_CTRL_*); the caller has checked the range
+template <class ROW, class F>
 void with_law(int law, F&& f) {
-  switch (law) {
-    case QUAD_CTRL_PID_YAW: f(std::integral_constant<int, QUAD_CTRL_PID_YAW>{}); break;
-    case QUAD_CTRL_PID_WORLD: f(std::integral_constant<int, QUAD_CTRL_PID_WORLD>{}); break;
-    case QUAD_CTRL_SE3: f(std::integral_constant<int, QUAD_CTRL_SE3>{}); break;
-    case QUAD_CTRL_SMC: f(std::integral_constant<int, QUAD_CTRL_SMC>{}); break;
-    default: f(std::integral_constant<int, QUAD_CTRL_LQR>{}); break;
+  if constexpr (!PID_ROW<ROW>) {
+    switch (law) {
+      case QUAD_CTRL_SE3: return f(std::integral_constant<int, QUAD_CTRL_SE3>{});
+      case QUAD_CTRL_SMC: return f(std::integral_constant<int, QUAD_CTRL_SMC>{});
+      case QUAD_CTRL_LQR: return f(std::integral_constant<int, QUAD_CTRL_LQR>{});
+      default: break;
+    }
   }
+  static_assert(QUAD_CTRL_PID_YAW == QUAD_PID_YAW_FRAME && QUAD_CTRL_PID_WORLD == QUAD_PID_WORLD_FRAME, "PID ids");
+  if (law == QUAD_CTRL_PID_WORLD) return f(std::integral_constant<int, QUAD_CTRL_PID_WORLD>{});
+  return f(std::integral_constant<int, QUAD_CTRL_PID_YAW>{});
+}
+
+template <class ROW>
+hipError_t launch_act(const PidPlant& plant, const ROW* rows, int32_t n_sets, const int32_t* set_of, int32_t law,
+                      const float* state12, const float* target9, int32_t n, double* state, float* actions,
+                      double* diag, hipStream_t s) {
+  const dim3 grid((n + ACT_BLOCK - 1) / ACT_BLOCK), blk(ACT_BLOCK);
+  with_law<ROW>(law, [&](auto lw) {
+    hipLaunchKernelGGL((k_ctrl_act<ROW, decltype(lw)::value>), grid, blk, 0, s, plant, rows, n_sets, set_of, state12,
+                       target9, n, state, reinterpret_cast<float4*>(actions), diag);
+  });
+  return hipGetLastError();
+}
+
+template <class ROW>
+hipError_t launch_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec, const PidPlant& plant,
+                          const Run<ROW>& r, hipStream_t s) {
+  const dim3 grid((kp.n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
+  with_law<ROW>(r.law, [&](auto lw) {
+    with_kind(env_kind == QUAD_ENV_TRAJ, spec, [&](auto kind, auto sp) {
+      hipLaunchKernelGGL((k_ctrl_episode<ROW, decltype(kind)::value, decltype(lw)::value, decltype(sp)::value>), grid,
+                         blk, 0, s, kc, kp, plant, r);
+    });
+  });
+  return hipGetLastError();
 }
 
 }  // namespace
 
 namespace quadenv {
 
+hipError_t launch_pid_act(const PidPlant& plant, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of,
+                          int32_t mode, const float* state12, const float* target9, int32_t n, double* integ,
+                          float* actions, double* diag, hipStream_t s) {
+  return launch_act(plant, gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag, s);
+}
+
 hipError_t launch_ctrl_act(const PidPlant& plant, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of,
                            int32_t law, const float* state12, const float* target9, int32_t n, double* state,
                            float* actions, double* diag, hipStream_t s) {
-  const dim3 grid((n + ACT_BLOCK - 1) / ACT_BLOCK), blk(ACT_BLOCK);
-  with_law(law, [&](auto lw) {
-    hipLaunchKernelGGL(k_ctrl_act<decltype(lw)::value>, grid, blk, 0, s, plant, params, n_sets, set_of, state12,
-                       target9, n, state, reinterpret_cast<float4*>(actions), diag);
-  });
-  return hipGetLastError();
+  return launch_act(plant, params, n_sets, set_of, law, state12, target9, n, state, actions, diag, s);
+}
+
+hipError_t launch_pid_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec,
+                              const PidPlant& plant, const QuadPidRun& r, hipStream_t s) {
+  return launch_episode(kc, kp, env_kind, spec, plant, run_of(r), s);
 }
 
 hipError_t launch_ctrl_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec,
                                const PidPlant& plant, const QuadCtrlRun& r, hipStream_t s) {
-  const dim3 grid((kp.n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
-  with_law(r.law, [&](auto lw) {
-    with_kind(env_kind == QUAD_ENV_TRAJ, spec, [&](auto kind, auto sp) {
-      hipLaunchKernelGGL((k_ctrl_episode<decltype(kind)::value, decltype(lw)::value, decltype(sp)::value>), grid, blk,
-                         0, s, kc, kp, plant, r);
-    });
-  });
-  return hipGetLastError();
+  return launch_episode(kc, kp, env_kind, spec, plant, run_of(r), s);
 }
 
 hipError_t launch_ctrl_waypoints(const KConsts<float>* kc, const KParams& kp, bool spec, const PidPlant& plant,
                                  const QuadCtrlRun& r, const QuadWaypointRun& wr, hipStream_t s) {
   const dim3 grid((kp.n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
-  with_law(r.law, [&](auto lw) {
+  with_law<QuadCtrlParams>(r.law, [&](auto lw) {
     with_bool(spec, [&](auto sp) {
       hipLaunchKernelGGL((k_ctrl_waypoints<decltype(lw)::value, decltype(sp)::value>), grid, blk, 0, s, kc, kp, plant,
-                         r, wr);
+                         run_of(r), wr);
     });
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_target_info(const KConsts<float>* kc, const KParams& kp, int env_kind, float* target_info,
+                              hipStream_t s) {
+  const dim3 grid((kp.n + ACT_BLOCK - 1) / ACT_BLOCK), blk(ACT_BLOCK);
+  with_bool(env_kind == QUAD_ENV_TRAJ, [&](auto tr) {
+    constexpr int KIND = decltype(tr)::value ? QUAD_ENV_TRAJ : QUAD_ENV_HOVER;
+    hipLaunchKernelGGL(k_target_info<KIND>, grid, blk, 0, s, kc, kp, target_info);
   });
   return hipGetLastError();
 }

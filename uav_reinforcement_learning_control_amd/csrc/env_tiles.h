@@ -128,7 +128,7 @@ __device__ __forceinline__ void load_env_motion(const KParams& p, int i, EnvRegs
 // info["target", "target_vel", "target_acc"] for step count e.step of the running episode: of the step
 // just taken (before any auto-reset), or what reset() reported when e.step == 0. `ep` is the episode
 // counter as loaded (the running episode is ep - 1). One definition for the step kernels (quadenv.hip)
-// and the PID kernels (pid.hip), whose fused loop must hand the law the same words quad_step reports.
+// and the controller kernels (ctrl.hip), whose fused loop must hand the law the same words quad_step reports.
 template <int KIND>
 __device__ __forceinline__ void target_info_of(const KConsts<float>& K, const KParams& p, int i,
                                                const EnvRegs<float>& e, uint32_t ep, float o[9]) {

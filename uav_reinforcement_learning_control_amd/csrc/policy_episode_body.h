@@ -23,21 +23,8 @@
 
 namespace quadenv {
 
-// k_pid_episode's store (pid.hip), for the same QuadPidMetrics layout
-__device__ __forceinline__ void store_metrics(const QuadPidMetrics& o, int i, const PidAcc& m, int32_t status) {
-  o.steps[i] = m.steps;
-  o.status[i] = status;
-  o.total_reward[i] = m.total_reward;
-  o.pos_err_sum[i] = m.pe_sum;
-  o.pos_err_sq[i] = m.pe_sq;
-  o.pos_err_max[i] = m.pe_max;
-  o.yaw_rate_abs_sum[i] = m.yr_abs_sum;
-  o.yaw_rate_sum[i] = m.yr_sum;
-  o.yaw_rate_sq[i] = m.yr_sq;
-  o.yaw_rate_abs_max[i] = m.yr_abs_max;
-  o.yaw_rate_sign_changes[i] = m.sign_changes;
-  o.yaw_rate_delta_sum[i] = m.yr_delta;
-}
+// The metric store and the tracker's status codes are the controller kernels' (store_metrics, metric_status_of:
+// quad_pid.h).
 
 __device__ __forceinline__ void store_row12(float* base, uint32_t row, const float v[12]) {
 #pragma unroll
@@ -48,13 +35,6 @@ __device__ __forceinline__ void store_row12(float* base, uint32_t row, const flo
 // NT = 2: wave w of a block owns envs 64w .. 64w + 63 = its two MFMA tiles. NT = 1: wave w owns the 32
 // envs 32w .. 32w + 31; lanes l and l + 32 both carry env l & 31 (the same bits), the lower half stores.
 // EB: envs per block (256: k_rollout's shape; 64: one or two waves, for evaluation-sized batches).
-// the metric status of a tracker status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
-__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
-  return tracker_status == 1 ? QUAD_PID_LAP
-                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
-                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
-}
-
 // WP: the waypoint tracker runs after every committed step and ends the env's run (wr: the kernel's
 // QuadWaypointRun; never read otherwise)
 template <int KIND, bool CTBR, int NT, int MODE, int EB, bool WP, typename FWD>

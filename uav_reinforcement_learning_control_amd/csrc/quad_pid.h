@@ -6,7 +6,7 @@
 // in float64 on the float32 state and target words, cast to float32 and clipped to [-1, 1] at the
 // end like the reference (np.array(..., dtype=np.float32), np.clip). The operation order is the
 // reference's; np.clip / Python's max / min keep their NaN behaviour (clipn and the selects below).
-// k_pid_act and k_pid_episode (pid.hip) and the host shim (tests/native_pid) instantiate this one
+// k_ctrl_act and k_ctrl_episode (ctrl.hip) and the host shim (tests/native_pid) instantiate this one
 // function, so under -ffp-contract=on the two kernels compute the same bits.
 #pragma once
 
@@ -170,6 +170,28 @@ QD_HD void pid_acc_step(PidAcc& m, const float s12[12], const float tgt[3], floa
   }
   m.prev_yr = yr;
   m.steps += 1;
+}
+
+// env i's QuadPidMetrics entries, once, at the end of a fused run (the controller and the policy episode kernels)
+__device__ __forceinline__ void store_metrics(const QuadPidMetrics& o, int i, const PidAcc& m, int32_t status) {
+  o.steps[i] = m.steps;
+  o.status[i] = status;
+  o.total_reward[i] = m.total_reward;
+  o.pos_err_sum[i] = m.pe_sum;
+  o.pos_err_sq[i] = m.pe_sq;
+  o.pos_err_max[i] = m.pe_max;
+  o.yaw_rate_abs_sum[i] = m.yr_abs_sum;
+  o.yaw_rate_sum[i] = m.yr_sum;
+  o.yaw_rate_sq[i] = m.yr_sq;
+  o.yaw_rate_abs_max[i] = m.yr_abs_max;
+  o.yaw_rate_sign_changes[i] = m.sign_changes;
+  o.yaw_rate_delta_sum[i] = m.yr_delta;
+}
+// the metric status of a waypoint tracker's status: lap -> QUAD_PID_LAP, terminated / truncated -> their codes
+__device__ __forceinline__ int32_t metric_status_of(int32_t tracker_status) {
+  return tracker_status == 1 ? QUAD_PID_LAP
+                             : (tracker_status == 2 ? QUAD_PID_TERMINATED
+                                                    : (tracker_status == 3 ? QUAD_PID_TRUNCATED : QUAD_PID_RUNNING));
 }
 
 }  // namespace quadenv

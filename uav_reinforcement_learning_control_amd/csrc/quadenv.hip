@@ -22,8 +22,8 @@
 //   k_mem_floor          the step's loads and stores alone (bench.py's DRAM floor)
 //   k_random_actions     action_space.sample() stand-in (Philox), config 2
 //   k_gae                SB3 GAE(lambda) reverse scan, one thread per env
-// The cascaded PID baseline's kernels (k_pid_act, k_pid_episode, k_target_info) are in pid.hip.
-// The controller family's kernels (k_ctrl_act, k_ctrl_episode) are in ctrl.hip.
+// The kernels of the cascaded PID baseline and of the controller family (k_ctrl_act, k_ctrl_episode,
+// k_ctrl_waypoints, k_target_info) are in ctrl.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -39,7 +39,6 @@
 #include "env_tiles.h"
 #include "kconsts_default.h"
 #include "ctrl.h"
-#include "pid.h"
 #include "policy_episode.h"
 #include "population.h"
 #include "quad_waypoints.h"
@@ -1280,23 +1279,75 @@ int quad_rollout(QuadHandle* h, const float* packed, const QuadRollout* r, void*
   return QUAD_OK;
 }
 
-// ---- cascaded PID baseline (kernels: pid.hip)
-int quad_pid_default_gains(QuadPidGains* g) {
-  if (!g) return fail(QUAD_EINVAL, "gains is NULL");
-  pid_default_gains_fill(g);
+// ---- what the fused runs and the controller calls check alike; who: the entry point the messages name
+static int check_est(const QuadVelEst* e, const char* who) {
+  const std::string w(who);
+  if (!e->alpha && !std::isfinite(e->alpha_all)) return fail(QUAD_EINVAL, w + ": alpha_all must be finite");
+  if (!(e->max_dt > 0.0)) return fail(QUAD_EINVAL, w + ": max_dt must be > 0");
   return QUAD_OK;
 }
 
-// what quad_pid_act and quad_pid_episode ask of the handle and of the gain table
-static int check_pid(const QuadHandle* h, const char* who, const QuadPidGains* gains, int32_t n_sets, int32_t mode) {
+// The common fields of a run (QuadPidRun, QuadCtrlRun, QuadPolicyRun), in this order: max_steps, the twelve
+// metrics arrays, trace_envs' range, a policy run's estimator (est and est_dt; NULL for a controller run) and,
+// with a trace requested, the 32-bit bound on the trace rows' byte offsets and the 16-byte alignment of
+// `aligned`: the OR of the pointers the kernels store 16 bytes at a time, which align_what names.
+static int check_run(const char* who, int32_t n, int32_t max_steps, int32_t trace_envs, const QuadPidMetrics& m,
+                     uintptr_t aligned, bool any_trace, const char* align_what, const QuadVelEst* est = nullptr,
+                     double est_dt = 1.0) {
+  const auto bad = [who](const std::string& msg) { return fail(QUAD_EINVAL, std::string(who) + ": " + msg); };
+  if (max_steps < 1) return bad("max_steps must be >= 1");
+  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
+      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
+      !m.yaw_rate_delta_sum)
+    return bad("every metrics array is required");
+  if (trace_envs < 0 || trace_envs > n) return bad("trace_envs must be in [0, N]");
+  if (est) {
+    if (int rc = check_est(est, who)) return rc;
+    if (!(est_dt > 0.0)) return bad("est_dt must be > 0");
+  }
+  if (any_trace && trace_envs > 0) {
+    if (int64_t(max_steps) * trace_envs * 48 > int64_t(UINT32_MAX))
+      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if (aligned & 15u) return bad(std::string(align_what) + " must be 16-byte aligned");
+  }
+  return QUAD_OK;
+}
+
+// what quad_pid_* (ids: the modes) and quad_ctrl_* (ids: the laws) ask of the handle and of the table
+struct LawIds {
+  int32_t lo, hi;            // the valid ids
+  const char *what, *table;  // the words the messages print
+};
+constexpr LawIds PID_MODES{QUAD_PID_YAW_FRAME, QUAD_PID_WORLD_FRAME, "mode", "gains"};
+constexpr LawIds CTRL_LAWS{QUAD_CTRL_PID_YAW, QUAD_CTRL_LQR, "law", "params"};
+static int check_law_table(const QuadHandle* h, const char* who, const LawIds& ids, int32_t id, int32_t n_sets,
+                           const void* table) {
   const std::string w(who);
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
     return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
   if (h->cfg.wrapper != QUAD_WRAP_NONE)
     return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
-  if (mode != QUAD_PID_YAW_FRAME && mode != QUAD_PID_WORLD_FRAME) return fail(QUAD_EINVAL, w + ": unknown mode");
+  if (id < ids.lo || id > ids.hi) return fail(QUAD_EINVAL, w + ": unknown " + ids.what);
   if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
-  if (!gains) return fail(QUAD_EINVAL, w + ": gains is NULL");
+  if (!table) return fail(QUAD_EINVAL, w + ": " + ids.table + " is NULL");
+  return QUAD_OK;
+}
+
+// the rows of quad_pid_act / quad_ctrl_act; state_name: "integ" / "state"
+static int check_act_rows(const char* who, const float* state12, const float* target9, const double* state,
+                          const char* state_name, const float* actions, int32_t n) {
+  const std::string w(who);
+  if (!state12 || !target9 || !state || !actions)
+    return fail(QUAD_EINVAL, w + ": state12, target9, " + state_name + " and actions are required");
+  if (n < 1) return fail(QUAD_EINVAL, w + ": n must be >= 1");
+  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, w + ": actions must be 16-byte aligned");
+  return QUAD_OK;
+}
+
+// ---- cascaded PID baseline (kernels: ctrl.hip, on QuadPidGains rows)
+int quad_pid_default_gains(QuadPidGains* g) {
+  if (!g) return fail(QUAD_EINVAL, "gains is NULL");
+  pid_default_gains_fill(g);
   return QUAD_OK;
 }
 
@@ -1304,11 +1355,8 @@ int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const
                  const float* state12, const float* target9, int32_t n, double* integ, float* actions,
                  double* diag, void* stream) {
   if (!h) return fail(QUAD_EINVAL, "handle is NULL");
-  if (int rc = check_pid(h, "quad_pid_act", gains, n_sets, mode)) return rc;
-  if (!state12 || !target9 || !integ || !actions)
-    return fail(QUAD_EINVAL, "quad_pid_act: state12, target9, integ and actions are required");
-  if (n < 1) return fail(QUAD_EINVAL, "quad_pid_act: n must be >= 1");
-  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, "quad_pid_act: actions must be 16-byte aligned");
+  if (int rc = check_law_table(h, "quad_pid_act", PID_MODES, mode, n_sets, gains)) return rc;
+  if (int rc = check_act_rows("quad_pid_act", state12, target9, integ, "integ", actions, n)) return rc;
   DeviceGuard g(h->device);
   HIP_TRY(launch_pid_act(make_pid_plant(h->cfg), gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag,
                          static_cast<hipStream_t>(stream)));
@@ -1317,23 +1365,15 @@ int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const
 
 int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream) {
   if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
-  if (int rc = check_pid(h, "quad_pid_episode", r->gains, r->n_sets, r->mode)) return rc;
-  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_pid_episode: max_steps must be >= 1");
-  const QuadPidMetrics& m = r->metrics;
-  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
-      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
-      !m.yaw_rate_delta_sum)
-    return fail(QUAD_EINVAL, "quad_pid_episode: every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_pid_episode: trace_envs must be in [0, N]");
-  if ((r->trace_actions || r->trace_state12) && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return fail(QUAD_EINVAL, "quad_pid_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
-      return fail(QUAD_EINVAL, "quad_pid_episode: traces must be 16-byte aligned");
-  }
+  if (int rc = check_law_table(h, "quad_pid_episode", PID_MODES, r->mode, r->n_sets, r->gains)) return rc;
+  const bool any_trace = r->trace_actions || r->trace_state12;
+  if (int rc = check_run("quad_pid_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
   DeviceGuard g(h->device);
   QuadPidRun run = *r;
-  if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
+  if (!any_trace) run.trace_envs = 0;
   HIP_TRY(launch_pid_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
                              static_cast<hipStream_t>(stream)));
   return QUAD_OK;
@@ -1346,27 +1386,12 @@ int quad_ctrl_default_params(QuadCtrlParams* p) {
   return QUAD_OK;
 }
 
-static int check_ctrl(const QuadHandle* h, const char* who, const QuadCtrlParams* params, int32_t n_sets, int32_t law) {
-  const std::string w(who);
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
-  if (h->cfg.wrapper != QUAD_WRAP_NONE)
-    return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
-  if (law < QUAD_CTRL_PID_YAW || law > QUAD_CTRL_LQR) return fail(QUAD_EINVAL, w + ": unknown law");
-  if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
-  if (!params) return fail(QUAD_EINVAL, w + ": params is NULL");
-  return QUAD_OK;
-}
-
 int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of, int32_t law,
                   const float* state12, const float* target9, int32_t n, double* state, float* actions,
                   double* diag, void* stream) {
   if (!h) return fail(QUAD_EINVAL, "handle is NULL");
-  if (int rc = check_ctrl(h, "quad_ctrl_act", params, n_sets, law)) return rc;
-  if (!state12 || !target9 || !state || !actions)
-    return fail(QUAD_EINVAL, "quad_ctrl_act: state12, target9, state and actions are required");
-  if (n < 1) return fail(QUAD_EINVAL, "quad_ctrl_act: n must be >= 1");
-  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, "quad_ctrl_act: actions must be 16-byte aligned");
+  if (int rc = check_law_table(h, "quad_ctrl_act", CTRL_LAWS, law, n_sets, params)) return rc;
+  if (int rc = check_act_rows("quad_ctrl_act", state12, target9, state, "state", actions, n)) return rc;
   DeviceGuard g(h->device);
   HIP_TRY(launch_ctrl_act(make_pid_plant(h->cfg), params, n_sets, set_of, law, state12, target9, n, state, actions, diag,
                           static_cast<hipStream_t>(stream)));
@@ -1375,36 +1400,21 @@ int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, c
 
 int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream) {
   if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
-  if (int rc = check_ctrl(h, "quad_ctrl_episode", r->params, r->n_sets, r->law)) return rc;
-  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_ctrl_episode: max_steps must be >= 1");
-  const QuadPidMetrics& m = r->metrics;
-  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
-      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
-      !m.yaw_rate_delta_sum)
-    return fail(QUAD_EINVAL, "quad_ctrl_episode: every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_ctrl_episode: trace_envs must be in [0, N]");
-  if ((r->trace_actions || r->trace_state12) && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return fail(QUAD_EINVAL, "quad_ctrl_episode: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
-      return fail(QUAD_EINVAL, "quad_ctrl_episode: traces must be 16-byte aligned");
-  }
+  if (int rc = check_law_table(h, "quad_ctrl_episode", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
+  const bool any_trace = r->trace_actions || r->trace_state12;
+  if (int rc = check_run("quad_ctrl_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
   DeviceGuard g(h->device);
   QuadCtrlRun run = *r;
-  if (!run.trace_actions && !run.trace_state12) run.trace_envs = 0;
+  if (!any_trace) run.trace_envs = 0;
   HIP_TRY(launch_ctrl_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
                               static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 
 // ---- the deployed observation path and the policy's fused episode (kernels: policy_episode.hip)
-static int check_est(const QuadVelEst* e, const char* who) {
-  const std::string w(who);
-  if (!e->alpha && !std::isfinite(e->alpha_all)) return fail(QUAD_EINVAL, w + ": alpha_all must be finite");
-  if (!(e->max_dt > 0.0)) return fail(QUAD_EINVAL, w + ": max_dt must be > 0");
-  return QUAD_OK;
-}
-
 int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
                     double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
   if (!h || !est) return fail(QUAD_EINVAL, "handle/est is NULL");
@@ -1430,23 +1440,12 @@ static int policy_run_args(const QuadHandle* h, const float* packed, const QuadP
   const auto bad = [who](const char* m) { return fail(QUAD_EINVAL, std::string(who) + ": " + m); };
   if (wrap_relpos(h->cfg.wrapper)) return bad("the policy takes 12-D obs (no RELPOS)");
   if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED) return bad("unknown obs_mode");
-  if (r->max_steps < 1) return bad("max_steps must be >= 1");
-  const QuadPidMetrics& m = r->metrics;
-  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
-      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
-      !m.yaw_rate_delta_sum)
-    return bad("every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return bad("trace_envs must be in [0, N]");
-  if (int rc = check_est(&r->est, who)) return rc;
-  if (!(r->est_dt > 0.0)) return bad("est_dt must be > 0");
   const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || lap_traces;
-  if (any_trace && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
-         reinterpret_cast<uintptr_t>(r->trace_obs)) & 15u)
-      return bad("the action, state12 and obs traces must be 16-byte aligned");
-  }
+  if (int rc = check_run(who, h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
+                             reinterpret_cast<uintptr_t>(r->trace_obs),
+                         any_trace, "the action, state12 and obs traces", &r->est, r->est_dt))
+    return rc;
   if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
   *out = EpisodeArgs{r->max_steps, any_trace ? r->trace_envs : 0,
                      EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
@@ -1475,12 +1474,6 @@ int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun*
 }
 
 // ---- waypoint laps in one launch (kernels: k_ctrl_waypoints, k_policy_waypoints)
-static bool metrics_complete(const QuadPidMetrics& m) {
-  return m.steps && m.status && m.total_reward && m.pos_err_sum && m.pos_err_sq && m.pos_err_max &&
-         m.yaw_rate_abs_sum && m.yaw_rate_sum && m.yaw_rate_sq && m.yaw_rate_abs_max && m.yaw_rate_sign_changes &&
-         m.yaw_rate_delta_sum;
-}
-
 // what both lap calls ask of the handle and of the tracker; the wrapper is the caller's to check
 static int check_waypoint_run(const QuadHandle* h, const char* who, const QuadWaypointRun* wr) {
   const std::string w(who);
@@ -1497,17 +1490,12 @@ static int check_waypoint_run(const QuadHandle* h, const char* who, const QuadWa
 int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointRun* wr, void* stream) {
   if (!h || !r || !wr) return fail(QUAD_EINVAL, "handle/run/waypoints is NULL");
   if (int rc = check_waypoint_run(h, "quad_ctrl_waypoints", wr)) return rc;
-  if (int rc = check_ctrl(h, "quad_ctrl_waypoints", r->params, r->n_sets, r->law)) return rc;
-  if (r->max_steps < 1) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: max_steps must be >= 1");
-  if (!metrics_complete(r->metrics)) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return fail(QUAD_EINVAL, "quad_ctrl_waypoints: trace_envs must be in [0, N]");
+  if (int rc = check_law_table(h, "quad_ctrl_waypoints", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
   const bool any_trace = r->trace_actions || r->trace_state12 || wr->trace_reward || wr->trace_wp_idx;
-  if (any_trace && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 48 > int64_t(UINT32_MAX))
-      return fail(QUAD_EINVAL, "quad_ctrl_waypoints: max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if ((reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12)) & 15u)
-      return fail(QUAD_EINVAL, "quad_ctrl_waypoints: traces must be 16-byte aligned");
-  }
+  if (int rc = check_run("quad_ctrl_waypoints", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
   DeviceGuard g(h->device);
   QuadCtrlRun run = *r;
   if (!any_trace) run.trace_envs = 0;
