@@ -560,6 +560,58 @@ int quad_actor_episode(QuadHandle* h, const QuadActorArch* arch, const float* pa
 int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
                          const QuadWaypointRun* wr, void* stream);
 
+/* ---- The Brax-profile policy on MFMA: ppo/brax_ppo.py BraxActorCritic.policy with two hidden layers on
+ * the 21-D observation of the brax env kinds, logits[8] = W3 act(W2 act(W1 xh + b1) + b2) + b3 with
+ * xh = (obs - mean) / std in f32 (RunningStats.normalize), h1 a multiple of 32 in [32, 512], h2 in {64, 128, 256},
+ * act ReLU, tanh or SiLU; loc = logits[0:4], scale = softplus(logits[4:8]) + min_std (NormalTanhDistribution).
+ * quad_actor_act's arithmetic. Forward path only (evaluation); no log-probs, no critic. Kernels are device fp32 in
+ * flax's [in, out] layout (BraxMLP.kernels): w0 [21,h1] b0 [h1] w1 [h1,h2] b1 [h2] w2 [h2,8] b2 [8]; mean, std [21].
+ * An arch outside the family is QUAD_EINVAL (quad_brax_actor_packed_floats: < 0). Added within ABI v8. */
+enum { QUAD_ACTFN_SILU = 2 };
+typedef struct QuadBraxActorArch { int32_t h1, h2, activation; } QuadBraxActorArch;
+typedef struct QuadBraxActorParams {
+  const float *w0, *b0, *w1, *b1, *w2, *b2, *mean, *std;
+  float min_std;
+} QuadBraxActorParams;
+int64_t quad_brax_actor_packed_floats(const QuadBraxActorArch* arch);
+/* `packed`: device, 16-byte aligned, quad_brax_actor_packed_floats(arch) floats (stream-ordered). */
+int quad_brax_actor_pack(const QuadBraxActorArch* arch, const QuadBraxActorParams* p, float* packed, void* stream);
+/* logits [n,8] (or NULL) and actions_env [n,4] (16-byte aligned) of obs [n,21]: deterministic != 0: tanh(loc);
+ * otherwise tanh(loc + scale z), z the four Box-Muller normals of Philox(seed; env_id_base + row, noise_step, 0x400).
+ * A row's result depends on neither n nor the other rows; a non-finite row stays in its row. */
+int quad_brax_actor_act(const QuadBraxActorArch* arch, const float* packed, const float* obs, float* logits,
+                        float* actions_env, int32_t n, int32_t deterministic, uint64_t seed, uint64_t env_id_base,
+                        uint32_t noise_step, void* stream);
+/* Per-env episode metrics of quad_brax_episode (device [N] arrays, all required), as evaluate_brax_ppo.py:315-362
+ * accumulates them. status: QUAD_PID_RUNNING / TERMINATED / TRUNCATED. */
+typedef struct QuadBraxMetrics {
+  double* ret;          /* sum of the rewards in step order */
+  int32_t* steps;
+  double* err_sum;      /* sum of |pos - target| (float32 norm) after the step, with the step's target, where finite */
+  double* err_sq_sum;   /* sum of its squares */
+  int32_t* err_count;   /* steps whose error was finite */
+  int32_t* status;
+} QuadBraxMetrics;
+/* Whole episodes in ONE launch from the envs' current state, on a handle of kind QUAD_ENV_BRAX_HOVER or _BRAX_TRAJ:
+ * per step the observation (what quad_observe / quad_step report), the actor, the env step, the metrics. Every env
+ * runs until its first terminated or truncated step or for max_steps iterations; it is then frozen and never reset
+ * (auto_reset is not consulted). Step t draws its noise with noise_step0 + t and env id = the handle's env_id_base +
+ * env. Traces (NULL to skip), time-major [max_steps, trace_envs, .] of the first trace_envs envs, rows past an env's
+ * last step untouched: actions (4, 16-byte aligned), obs (21, the row the action was taken from), pos and target (3
+ * each, after the step); max_steps * trace_envs * 84 < 2^32.
+ * Contract: bit-identical, for every env up to its last step, to this loop on a second handle with auto_reset = 0:
+ * quad_observe once; per step quad_brax_actor_act (same deterministic, seed, env_id_base, noise_step0 + t), then
+ * quad_step. */
+typedef struct QuadBraxRun {
+  int32_t max_steps, trace_envs, deterministic;
+  uint32_t noise_step0;
+  uint64_t seed;
+  QuadBraxMetrics metrics;
+  float *trace_actions, *trace_obs, *trace_pos, *trace_target;
+} QuadBraxRun;
+int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
+                      void* stream);
+
 /* Finish the pending step (end of a rollout): the epilogue for row (t-1) % rows if the cursor
  * marks one pending, then clears the mark. A no-op otherwise. */
 int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* cursor, int32_t n,

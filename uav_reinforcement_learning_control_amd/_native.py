@@ -159,6 +159,38 @@ class QuadActorParams(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
 
 
+# the Brax-profile policy (quad_brax_*): 21 -> h1 -> h2 -> 8 behind the running statistics' normaliser; the general
+# actor's widths, and SiLU beside ReLU and tanh
+ACTFN_SILU = 2
+BRAX_ACTFNS = {"relu": ACTFN_RELU, "tanh": ACTFN_TANH, "silu": ACTFN_SILU}
+BRAX_OBS, BRAX_LOGITS = 21, 8
+
+
+class QuadBraxActorArch(C.Structure):
+    _fields_ = [("h1", C.c_int32), ("h2", C.c_int32), ("activation", C.c_int32)]
+
+
+class QuadBraxActorParams(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w0", "b0", "w1", "b1", "w2", "b2", "mean", "std")] + \
+               [("min_std", C.c_float)]
+
+
+# QuadBraxMetrics: device [N] arrays; (name, torch dtype name)
+BRAX_METRIC_FIELDS = (("ret", "float64"), ("steps", "int32"), ("err_sum", "float64"), ("err_sq_sum", "float64"),
+                      ("err_count", "int32"), ("status", "int32"))
+
+
+class QuadBraxMetrics(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n, _ in BRAX_METRIC_FIELDS]
+
+
+class QuadBraxRun(C.Structure):
+    _fields_ = [("max_steps", C.c_int32), ("trace_envs", C.c_int32), ("deterministic", C.c_int32),
+                ("noise_step0", C.c_uint32), ("seed", C.c_uint64), ("metrics", QuadBraxMetrics),
+                ("trace_actions", C.c_void_p), ("trace_obs", C.c_void_p), ("trace_pos", C.c_void_p),
+                ("trace_target", C.c_void_p)]
+
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -191,7 +223,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode",
            "quad_deploy_obs", "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints",
            "quad_actor_packed_floats", "quad_actor_pack", "quad_actor_act", "quad_actor_episode",
-           "quad_actor_waypoints")
+           "quad_actor_waypoints",
+           "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode")
 
 
 class QuadRollout(C.Structure):
@@ -323,6 +356,16 @@ def _declare(L):
     L.quad_actor_episode.argtypes = [vp, arch, vp, C.POINTER(QuadPolicyRun), vp]
     L.quad_actor_waypoints.argtypes = [vp, arch, vp, C.POINTER(QuadPolicyRun), C.POINTER(QuadWaypointRun), vp]
     for n in ("quad_actor_pack", "quad_actor_act", "quad_actor_episode", "quad_actor_waypoints"):
+        getattr(L, n).restype = C.c_int
+    if not hasattr(L, "quad_brax_episode"):  # the version number did not change with the quad_brax_* additions
+        raise QuadError(f"{LIB_PATH} was built before the Brax policy's entry points (quad_brax_*); rebuild it")
+    barch = C.POINTER(QuadBraxActorArch)
+    L.quad_brax_actor_packed_floats.argtypes = [barch]
+    L.quad_brax_actor_packed_floats.restype = C.c_int64
+    L.quad_brax_actor_pack.argtypes = [barch, C.POINTER(QuadBraxActorParams), vp, vp]
+    L.quad_brax_actor_act.argtypes = [barch, vp, vp, vp, vp, i32, i32, u64, u64, u32, vp]
+    L.quad_brax_episode.argtypes = [vp, barch, vp, C.POINTER(QuadBraxRun), vp]
+    for n in ("quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode"):
         getattr(L, n).restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")

@@ -1,0 +1,29 @@
+// brax_episode.h -- host-side entries of the Brax-profile policy's launches (brax_actor.hip), called by
+// quad_brax_episode (quadenv.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/quadenv.h"
+#include "env_tiles.h"
+
+namespace quadenv {
+
+struct BraxNet {  // a checked QuadBraxActorArch: H1 / 32, H2 / 32 (2, 4 or 8), QUAD_ACTFN_*
+  int nb1, mb, actfn;
+};
+// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
+int brax_net_of(const QuadBraxActorArch* a, BraxNet* out);
+struct BraxEpisodeArgs {  // QuadBraxRun, flattened (trace_envs 0 when no trace is requested)
+  int32_t max_steps, trace_envs, deterministic;
+  uint32_t noise_step0;
+  uint64_t seed;
+  QuadBraxMetrics metrics;
+  float *trace_actions, *trace_obs, *trace_pos, *trace_target;
+};
+// k_brax_episode<env_kind, mb> over all envs of kp, 64-env blocks of two one-tile waves
+hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const BraxNet& net,
+                               const float* packed, const BraxEpisodeArgs& a, hipStream_t s);
+
+}  // namespace quadenv

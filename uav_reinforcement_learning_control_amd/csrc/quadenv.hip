@@ -38,6 +38,7 @@
 #include "dispatch.h"
 #include "env_tiles.h"
 #include "kconsts_default.h"
+#include "brax_episode.h"
 #include "ctrl.h"
 #include "policy_episode.h"
 #include "population.h"
@@ -1544,6 +1545,34 @@ int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* 
   DeviceGuard g(h->device);
   HIP_TRY(launch_actor_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net, packed, a, *wr,
                                  static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- the Brax-profile policy's episodes on the brax kinds (kernels: brax_actor.hip)
+int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
+                      void* stream) {
+  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_episode: ") + m); };
+  BraxNet net;
+  if (int rc = brax_net_of(arch, &net)) return rc;
+  if (!h || !packed || !r) return bad("handle/packed/run is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
+    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
+  if (r->max_steps < 1) return bad("max_steps must be >= 1");
+  const QuadBraxMetrics& m = r->metrics;
+  if (!m.ret || !m.steps || !m.err_sum || !m.err_sq_sum || !m.err_count || !m.status)
+    return bad("every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return bad("trace_envs must be in [0, N]");
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
+  const bool any_trace = r->trace_actions || r->trace_obs || r->trace_pos || r->trace_target;
+  if (any_trace && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 84 > int64_t(UINT32_MAX))
+      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if (reinterpret_cast<uintptr_t>(r->trace_actions) & 15u) return bad("the action trace must be 16-byte aligned");
+  }
+  const BraxEpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0, r->deterministic, r->noise_step0, r->seed,
+                          r->metrics, r->trace_actions, r->trace_obs, r->trace_pos, r->trace_target};
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_brax_episode(h->kdev, h->kp, h->cfg.env_kind, net, packed, a, static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

@@ -220,6 +220,27 @@ class BraxStepStats:
     losses: dict = field(default_factory=dict)
 
 
+@torch.no_grad()
+def brax_eval_loop(model, env, max_steps: int, deterministic: bool):
+    """The per-step form of BraxPPO.evaluate: torch forward + env.step until every env has finished its first
+    episode or `max_steps` pass, from the env's current state. `model` has act(obs, deterministic). Returns
+    (return [N] float64, steps [N] int32); an env's later (auto-reset) steps are not counted."""
+    n, dev = env.num_envs, env.device
+    obs = env.observe().clone() if hasattr(env, "observe") else env.obs.clone()
+    ret = torch.zeros(n, dtype=torch.float64, device=dev)
+    steps = torch.zeros(n, dtype=torch.int32, device=dev)
+    active = torch.ones(n, dtype=torch.bool, device=dev)
+    for t in range(int(max_steps)):
+        o, rw, te, tr, _ = env.step(model.act(obs, deterministic=deterministic).contiguous(), info="raw")
+        ret += torch.where(active, rw.double(), torch.zeros((), dtype=torch.float64, device=dev))
+        steps += active.int()
+        active &= ~(te | tr)
+        obs = o.clone()
+        if t % 16 == 15 and not bool(active.any()):
+            break
+    return ret, steps
+
+
 class BraxPPO:
     """brax ``ppo.train``'s training step on a ``QuadVecEnv`` brax kind (env="brax_hover" or
     "brax_jax_mjx"), one process per GPU (gradients averaged with one flat all_reduce)."""
@@ -232,6 +253,9 @@ class BraxPPO:
         if (c.batch_size * c.num_minibatches) % c.num_envs:
             raise ValueError("batch_size * num_minibatches must be a multiple of num_envs (brax)")
         self.device = env.device
+        self.seed = int(seed)
+        self._fused = None       # FusedBraxActor of self.net, built by the first evaluate() that takes the launch
+        self._eval_count = 0
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)
         self.net = BraxActorCritic(env.obs_dim, 4, c).to(self.device)
@@ -328,6 +352,39 @@ class BraxPPO:
     def act(self, obs: torch.Tensor, deterministic: bool = True) -> torch.Tensor:
         logits = self.net.policy(self.norm.normalize(obs))
         return self.net.dist.mode(logits) if deterministic else torch.tanh(self.net.dist.sample_raw(logits, self.gen))
+
+    def evaluate(self, eval_env, deterministic: bool = False, *, max_steps: Optional[int] = None,
+                 seed: Optional[int] = None, noise_step0: Optional[int] = None, reset: bool = True,
+                 force_loop: bool = False):
+        """brax's Evaluator.run_evaluation (brax/training/acting.py; restated from the published algorithm, parity
+        unpinned): every env of `eval_env` (a brax kind, separate from the training env) flies one episode from a
+        fresh reset under the current policy and statistics -- sampled actions unless `deterministic` -- to its
+        first terminated / truncated step or `max_steps` (default: the env's episode length). Returns (mean
+        episode reward, mean episode length) over the eval envs: brax's eval/episode_reward and
+        eval/avg_episode_length.
+
+        One launch (FusedBraxActor.episode) when the policy is in the MFMA family (ppo.fused.brax_launch_chosen);
+        otherwise -- three hidden layers, say -- a torch per-step loop with the same semantics and return shape,
+        drawing its noise from torch's generator instead of the launch's Philox stream."""
+        from .fused import FusedBraxActor, brax_launch_chosen
+        c = self.cfg
+        T = int(eval_env.max_episode_steps if max_steps is None else max_steps)
+        if reset:
+            eval_env.reset()
+        k = self._eval_count
+        self._eval_count += 1
+        if not force_loop and brax_launch_chosen(c.policy_hidden_sizes, c.activation, eval_env):
+            if self._fused is None:
+                self._fused = FusedBraxActor(self.net, self.norm)
+            self._fused.pack()
+            res = self._fused.episode(eval_env, max_steps=T, deterministic=deterministic,
+                                      seed=self.seed + 1 if seed is None else seed,
+                                      noise_step0=k * T if noise_step0 is None else noise_step0)
+            self.last_eval = res
+            return float(res["ret"].mean().item()), float(res["steps"].double().mean().item())
+        ret, steps = brax_eval_loop(self, eval_env, T, deterministic)
+        self.last_eval = dict(ret=ret, steps=steps)
+        return float(ret.mean().item()), float(steps.double().mean().item())
 
     def params(self):
         """(normalizer, policy, value) as brax ppo.train returns them (numpy leaves)."""

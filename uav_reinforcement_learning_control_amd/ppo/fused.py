@@ -9,7 +9,9 @@ statistics) -- instead of ~25 torch kernels. The torch ActorCritic stays the tra
 
 `FusedPolicy` is the 12-128-128 ReLU net of the training kernels. `FusedActor` is the deterministic actor of any
 other supported architecture (quad_actor_*: 12-H1-H2-4, ReLU or tanh) for evaluation episodes and waypoint laps;
-`fused_actor_for(policy)` picks between the two.
+`fused_actor_for(policy)` picks between the two. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
+21-H1-H2-8 behind the running statistics, ReLU / tanh / SiLU, NormalTanh sampling) for evaluation episodes of the
+brax env kinds.
 """
 from __future__ import annotations
 
@@ -337,3 +339,137 @@ def rollout_supported(env) -> bool:
     cfg = getattr(env, "cfg", None)
     return (cfg is not None and getattr(env, "_h", None) is not None and cfg.auto_reset == 1
             and cfg.env_kind in (N.ENV_HOVER, N.ENV_TRAJ) and cfg.wrapper in (N.WRAP_NONE, N.WRAP_CTBR))
+
+
+def _brax_parts(net_or_params, activation=None, min_std=None):
+    """([w0, b0, w1, b1, w2, b2], activation, min_std) of a BraxActorCritic, a BraxMLP, or a flax policy-params dict
+    ({"params": {"hidden_i": {"kernel" [in, out], "bias"}}}); kernels stay in flax's [in, out] layout."""
+    pol = getattr(net_or_params, "policy", net_or_params)
+    if isinstance(pol, dict):
+        p = pol.get("params", pol)
+        names = sorted(p, key=lambda k: int(k.rsplit("_", 1)[1]))
+        ts = [torch.as_tensor(p[k][f]) for k in names for f in ("kernel", "bias")]
+        return ts, activation, min_std
+    act = {v: k for k, v in _brax_act_table().items()}.get(pol.act, activation)
+    ms = getattr(getattr(net_or_params, "dist", None), "min_std", min_std)
+    return [t for k, b in zip(pol.kernels, pol.biases) for t in (k.detach(), b.detach())], act, ms
+
+
+def _brax_act_table():
+    from .brax_ppo import _ACT
+    return _ACT
+
+
+def brax_arch_of(policy_sizes, activation) -> N.QuadBraxActorArch:
+    """The QuadBraxActorArch of hidden sizes (H1, H2) and an activation name; ValueError outside the family."""
+    s = tuple(int(x) for x in policy_sizes)
+    ok = (len(s) == 2 and s[0] % 32 == 0 and 32 <= s[0] <= N.ACTOR_MAX_H1 and s[1] in N.ACTOR_H2
+          and activation in N.BRAX_ACTFNS)
+    if not ok:
+        raise ValueError("the MFMA Brax actor flies 21-H1-H2-8 nets (H1 a multiple of 32 up to 512, H2 in "
+                         f"{N.ACTOR_H2}, relu / tanh / silu), got {s} {activation!r}")
+    return N.QuadBraxActorArch(h1=s[0], h2=s[1], activation=N.BRAX_ACTFNS[activation])
+
+
+def brax_episode_supported(policy_sizes, activation, env) -> bool:
+    """quad_brax_episode flies a two-hidden-layer Brax policy of the supported family on a brax env kind."""
+    cfg = getattr(env, "cfg", None)
+    if cfg is None or getattr(env, "_h", None) is None or cfg.env_kind not in (N.ENV_BRAX_HOVER, N.ENV_BRAX_TRAJ):
+        return False
+    try:
+        brax_arch_of(policy_sizes, activation)
+    except (ValueError, TypeError):
+        return False
+    return True
+
+
+# (hidden sizes, activation) the drivers keep on the per-step loop because the launch lost to it in
+# profiles/brax_eval/bench.json (DESIGN 20's rule, 19's): none of the measured sizes did
+BRAX_KEEP_LOOP = frozenset()
+
+
+def brax_launch_chosen(policy_sizes, activation, env) -> bool:
+    """The drivers' dispatch: the one-launch episode where it is supported and did not lose to the loop."""
+    return (brax_episode_supported(policy_sizes, activation, env)
+            and (tuple(int(x) for x in policy_sizes), activation) not in BRAX_KEEP_LOOP)
+
+
+class FusedBraxActor:
+    """The Brax-profile policy (ppo/brax_ppo.py BraxActorCritic.policy, two hidden layers) with its running-statistics
+    normaliser on MFMA (csrc/brax_actor.h, quad_brax_*): act on observation rows, and whole evaluation episodes of a
+    brax env kind in one launch.
+
+    net_or_params: a BraxActorCritic / BraxMLP, or the flax policy-params dict of a saved archive (then give
+    `activation`, and `min_std` if it is not 0.001). norm: a RunningStats, or a mapping with "mean" and "std"."""
+
+    def __init__(self, net_or_params, norm, activation: Optional[str] = None, min_std: Optional[float] = None,
+                 device=None):
+        self.source, self.norm = net_or_params, norm
+        ts, act, ms = _brax_parts(net_or_params, activation, min_std)
+        if len(ts) != 6:
+            raise ValueError(f"the MFMA Brax actor flies two hidden layers, got {len(ts) // 2 - 1}")
+        if tuple(ts[0].shape)[0] != N.BRAX_OBS or tuple(ts[4].shape)[1] != N.BRAX_LOGITS:
+            raise ValueError(f"expected a 21 -> .. -> 8 policy, got {[tuple(t.shape) for t in ts[::2]]}")
+        self.arch = brax_arch_of((ts[0].shape[1], ts[2].shape[1]), act)
+        self.min_std = 0.001 if ms is None else float(ms)
+        self.device = torch.device(device) if device is not None else (
+            ts[0].device if ts[0].device.type == "cuda" else torch.device("cuda", torch.cuda.current_device()))
+        if self.device.type != "cuda":
+            raise N.QuadError("FusedBraxActor needs a ROCm GPU")
+        nf = N.lib().quad_brax_actor_packed_floats(C.byref(self.arch))
+        if nf <= 0:
+            raise N.QuadError("quad_brax_actor_packed_floats rejected the architecture")
+        self.packed = torch.empty(nf, dtype=torch.float32, device=self.device)
+        self._noise_step = 0
+
+    _stream = FusedPolicy._stream
+
+    def _mean_std(self):
+        g = (lambda k: self.norm[k]) if isinstance(self.norm, dict) else (lambda k: getattr(self.norm, k))
+        return g("mean"), g("std")
+
+    @torch.no_grad()
+    def pack(self) -> None:
+        """Refresh the kernels' copy of the parameters and of the normaliser (call after an update)."""
+        ts = _brax_parts(self.source)[0] + list(self._mean_std())
+        ts = [torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in ts]
+        prm = N.QuadBraxActorParams(*[t.data_ptr() for t in ts], min_std=self.min_std)
+        N.check(N.lib().quad_brax_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed), self._stream()),
+                "quad_brax_actor_pack")
+        self._packed_from = ts  # the launch reads them: alive until the next pack
+
+    def act(self, obs: torch.Tensor, actions_env: torch.Tensor, logits: Optional[torch.Tensor] = None, *,
+            deterministic: bool = True, seed: int = 0, env_id_base: int = 0, noise_step: int = 0) -> None:
+        """quad_brax_actor_act: actions_env = tanh(loc) or tanh(loc + scale z), and the logits unless None."""
+        n, dev, f32 = obs.shape[0], self.device, torch.float32
+        _need(obs, (n, N.BRAX_OBS), f32, dev, "obs")
+        _need(actions_env, (n, 4), f32, dev, "actions_env")
+        if logits is not None:
+            _need(logits, (n, N.BRAX_LOGITS), f32, dev, "logits")
+        N.check(N.lib().quad_brax_actor_act(C.byref(self.arch), _p(self.packed), _p(obs), _p(logits), _p(actions_env),
+                                            n, int(bool(deterministic)), int(seed) & (2**64 - 1),
+                                            int(env_id_base) & (2**64 - 1), int(noise_step) & 0xFFFFFFFF,
+                                            self._stream()), "quad_brax_actor_act")
+
+    def episode(self, env, *, max_steps: Optional[int] = None, deterministic: bool = False, seed: int = 0,
+                trace_envs: int = 0, noise_step0: int = 0) -> dict:
+        """quad_brax_episode: whole episodes from the envs' current state (call env.reset() first) in one launch.
+        Every env runs to its first terminated / truncated step or `max_steps` (default: the env's episode length)
+        and is then frozen, not reset. Returns device tensors: the QuadBraxMetrics fields ([N]) and, with
+        trace_envs = M > 0, "actions" [T, M, 4], "obs" [T, M, 21], "pos" and "target" [T, M, 3] of the first M envs
+        (rows past an env's last step stay zero)."""
+        n, dev = env.num_envs, self.device
+        T, M = int(env.max_episode_steps if max_steps is None else max_steps), int(trace_envs)
+        res = {k: torch.zeros(n, dtype=getattr(torch, dt), device=dev) for k, dt in N.BRAX_METRIC_FIELDS}
+        if M > 0 and T > 0:
+            for k, w in (("actions", 4), ("obs", N.BRAX_OBS), ("pos", 3), ("target", 3)):
+                res[k] = torch.zeros(T, M, w, dtype=torch.float32, device=dev)
+        tr = lambda k: res[k].data_ptr() if k in res else None
+        run = N.QuadBraxRun(max_steps=T, trace_envs=M, deterministic=int(bool(deterministic)),
+                            noise_step0=int(noise_step0) & 0xFFFFFFFF, seed=int(seed) & (2**64 - 1),
+                            metrics=N.QuadBraxMetrics(**{k: res[k].data_ptr() for k, _ in N.BRAX_METRIC_FIELDS}),
+                            trace_actions=tr("actions"), trace_obs=tr("obs"), trace_pos=tr("pos"),
+                            trace_target=tr("target"))
+        N.check(N.lib().quad_brax_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), self._stream()),
+                "quad_brax_episode")
+        return res

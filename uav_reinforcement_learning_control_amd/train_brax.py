@@ -3,7 +3,9 @@
     python -m uav_reinforcement_learning_control_amd.train_brax --env jax_mjx_quad --num-envs 65536
 
 Same arguments and defaults as train_brax_ppo.py where they apply (the JAX/MJX-specific --xml,
---impl, --backend, Orbax checkpoints and --num-evals have no counterpart here). Outputs mirror the
+--impl, --backend and Orbax checkpoints have no counterpart here). --num-evals K runs brax's in-training
+evaluation (K evaluations evenly spaced over the run on a separate eval env, BraxPPO.evaluate: one launch per
+evaluation); its default here is 0, so a run without the flag prints and writes what it always did. Outputs mirror the
 reference's run directory: <output-dir>/<timestamp>/ppo_params.msgpack (brax model.save_params
 format, ppo/brax_ppo.py + export.save_brax_params), checkpoints/params_step_<n>.msgpack every
 --checkpoint-interval steps, and training_summary.json.
@@ -31,6 +33,33 @@ def _sizes(v: str):
     return out
 
 
+def eval_schedule(num_timesteps: int, steps_per_training_step: int, num_evals: int):
+    """The training-step counts after which an evaluation runs (0: before training). brax ppo.train (restated from
+    the published algorithm, parity unpinned) runs max(num_evals - 1, 1) epochs of equal length with an evaluation
+    after each, and one before training when num_evals > 1, sizing the epochs so that they reach num_timesteps.
+    The run here is the fixed number of training steps that reaches num_timesteps, so epoch j ends after
+    round(j * training steps / epochs) of them: num_evals evaluations, evenly spaced, the last at the end (fewer
+    when the run has fewer training steps than epochs). Empty for num_evals <= 0."""
+    if num_evals <= 0:
+        return []
+    total = max(1, -(-int(num_timesteps) // int(steps_per_training_step)))
+    epochs = max(num_evals - 1, 1)
+    pts = sorted({max(1, (2 * j * total + epochs) // (2 * epochs)) for j in range(1, epochs + 1)})
+    return ([0] if num_evals > 1 else []) + pts
+
+
+def progress_line(step: int, train_reward, eval_reward, sps: float) -> str:
+    """train_brax_ppo.py:563-573's progress line."""
+    fin = lambda v: v is not None and v == v and abs(v) != float("inf")
+    if fin(eval_reward) and fin(train_reward):
+        return f"step={step:,} train_reward={train_reward:.4f} eval_reward={eval_reward:.4f} sps={sps:.1f}"
+    if fin(eval_reward):
+        return f"step={step:,} eval_reward={eval_reward:.4f} sps={sps:.1f}"
+    if fin(train_reward):
+        return f"step={step:,} train_reward={train_reward:.4f} sps={sps:.1f}"
+    return f"step={step:,} train_reward=invalid eval_reward=invalid sps={sps:.1f}"
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawTextHelpFormatter)
     ap.add_argument("--env", default="hover", choices=["hover", "jax_mjx_quad"])
@@ -54,6 +83,11 @@ def parse(argv=None):
     ap.add_argument("--checkpoint-interval", type=int, default=200_000)
     ap.add_argument("--restore-checkpoint-path", default=None, help="a params .msgpack to start from")
     ap.add_argument("--output-dir", default="models_brax")
+    ap.add_argument("--num-evals", type=int, default=0,
+                    help="in-training evaluations, evenly spaced (one before training when > 1); the reference's\n"
+                         "default is 10, here 0: no evaluation, the output of a run without the flag is unchanged")
+    ap.add_argument("--num-eval-envs", type=int, default=128, help="envs of the separate eval env (brax: 128)")
+    ap.add_argument("--deterministic-eval", action="store_true", help="evaluate tanh(loc) instead of samples")
     return ap.parse_args(argv)
 
 
@@ -86,15 +120,33 @@ def main(argv=None):
     ckdir = os.path.join(run, "checkpoints")
     if rank == 0:
         os.makedirs(ckdir, exist_ok=True)
+    # brax's eval_env: a second env of the same kind with its own key (here: the run's seed + 1, ids past the
+    # training envs'), rank 0 only; each evaluation resets it, so each flies fresh episodes
+    sched = eval_schedule(a.num_timesteps, cfg.unroll_length * model.num_unrolls * a.num_envs * world, a.num_evals)
+    eval_env = None
+    if sched and rank == 0:
+        eval_env = QuadVecEnv(a.num_eval_envs, env=kind, device=f"cuda:{local}", seed=a.seed + 1,
+                              env_id_base=world * a.num_envs, max_episode_steps=a.episode_length, auto_reset=False,
+                              cfg_overrides={"traj_duration": a.traj_duration_seconds})
+    eval_reward = None
     t0 = time.time()
     last_ck = 0
     stats = None
+    done_steps = 0
+    if 0 in sched and rank == 0:
+        eval_reward, _ = model.evaluate(eval_env, deterministic=a.deterministic_eval)
+        print(progress_line(0, None, eval_reward, 0.0), flush=True)
     while model.num_timesteps < a.num_timesteps:
         stats = model.training_step()
+        done_steps += 1
         if rank == 0:
             sps = stats.env_steps * world / stats.seconds
-            print(f"step={model.num_timesteps:,} train_reward={stats.mean_episode_reward:.4f} sps={sps:.1f}",
-                  flush=True)
+            if done_steps in sched:
+                eval_reward, _ = model.evaluate(eval_env, deterministic=a.deterministic_eval)
+                print(progress_line(model.num_timesteps, stats.mean_episode_reward, eval_reward, sps), flush=True)
+            else:
+                print(f"step={model.num_timesteps:,} train_reward={stats.mean_episode_reward:.4f} sps={sps:.1f}",
+                      flush=True)
             if a.checkpoint_interval > 0 and model.num_timesteps - last_ck >= a.checkpoint_interval:
                 save_brax_params(os.path.join(ckdir, f"params_step_{model.num_timesteps}.msgpack"), model.params())
                 last_ck = model.num_timesteps
@@ -114,6 +166,9 @@ def main(argv=None):
                    "final_metrics": {"training/episode_reward": stats.mean_episode_reward if stats else None,
                                      **(stats.losses if stats else {})},
                    "params_path": params_path}
+        if a.num_evals > 0:
+            summary["num_evals"] = a.num_evals
+            summary["final_metrics"]["eval/episode_reward"] = eval_reward
         json.dump(summary, open(os.path.join(run, "training_summary.json"), "w"), indent=2)
         print(f"Saved parameters: {params_path}", flush=True)
     if world > 1:
