@@ -10,7 +10,7 @@ import torch
 import policy_x3_ref as R
 
 N_ROWS = 1024
-ARCHS = ((64, 64), (96, 64), (128, 128), (256, 256), (512, 256))
+ARCHS = ((32, 64), (64, 64), (96, 64), (128, 128), (256, 256), (512, 256))
 ACTIVATIONS = ("relu", "tanh")
 NAMES = ("w0", "b0", "w1", "b1", "w2", "b2")  # QuadActorParams' order (FusedActor.pack)
 STYLES = ("a", "b", "c")

@@ -14,7 +14,7 @@ import torch
 import policy_x3_ref as R
 
 N_ROWS = 1024
-ARCHS = ((64, 64), (96, 64), (128, 128), (256, 256), (512, 256))
+ARCHS = ((32, 64), (64, 64), (96, 64), (128, 128), (256, 256), (512, 256))
 ACTIVATIONS = ("relu", "tanh", "silu")
 NAMES = ("w0", "b0", "w1", "b1", "w2", "b2")  # QuadBraxActorParams' order; kernels are [in, out]
 STYLES = ("a", "b", "c")
@@ -198,7 +198,7 @@ def softplus_model(x):
 
 
 def tanh_model(x):
-    """arch::tanh_f32 in numpy float32."""
+    """actor::tanh_f32 (csrc/actor_core.h) in numpy float32."""
     x = np.asarray(x, np.float32)
     t = np.abs(x)
     z = t * t

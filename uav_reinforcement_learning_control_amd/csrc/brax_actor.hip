@@ -3,7 +3,8 @@
 // of the brax env kinds that flies it (quad_brax_episode).
 //
 // Kernels
-//   k_brax_pack               flax [in, out] parameters + mean / std / min_std -> the packed image
+//   actor::k_pack<brax::Layout, ..>
+//                             flax [in, out] parameters + mean / std / min_std -> the packed image
 //   k_brax_act<MB>            logits and the env action of n rows, one wave per 32-row tile, grid-stride
 //   k_brax_episode<KIND, MB>  whole episodes: 64-env blocks of two one-tile waves, every env's state in registers,
 //                             per step forward -> NormalTanh -> brax_step -> metrics; the handle's constant block
@@ -14,7 +15,7 @@
 // built with quadenv.o's floating-point flags (-ffp-contract=on, no SLP vectorizer), so brax_step has k_step_brax's
 // bits.
 //
-// This file is compiled once without BA_KIND (the C entry points, k_brax_pack, k_brax_act, the launch dispatch) and
+// This file is compiled once without BA_KIND (the C entry points, the pack kernel, k_brax_act, the launch dispatch) and
 // once per (BA_KIND, BA_MB): BA_KIND = 0 brax hover / 1 brax trajectory, BA_MB = H2 / 32 = 2 / 4 / 8.
 #include <hip/hip_runtime.h>
 
@@ -28,11 +29,9 @@
 
 namespace quadenv {
 
-int set_error(int code, const char* msg);  // quadenv.hip
-
-// one (kind, MB) object's instantiation
+// one (kind, MB) object's instantiation, defined and explicitly instantiated in that object
 template <int BKIND, int MB>
-hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const BraxNet& net, const float* packed,
+hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
                             const BraxEpisodeArgs& a, hipStream_t s);
 
 #if defined(BA_KIND)
@@ -65,7 +64,7 @@ __device__ __forceinline__ int32_t entry_status(const KConsts<float>& k, const E
 
 template <int KIND, int MB>
 __global__ __launch_bounds__(128) void k_brax_episode(const KConsts<float>* __restrict__ kc, KParams p,
-                                                      const float* __restrict__ packed, brax::Net net,
+                                                      const float* __restrict__ packed, actor::Net net,
                                                       BraxEpisodeArgs a) {
   extern __shared__ float lds[];
   p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
@@ -81,7 +80,7 @@ __global__ __launch_bounds__(128) void k_brax_episode(const KConsts<float>* __re
 
   EnvRegs<float> e;
   load_env(p, i, e, true);
-  brax::stage<128>(lds, packed, lay);
+  actor::stage<128>(lds, packed, lay.lds_floats());
   const float min_std = lds[lay.misc()];
   float ob[brax::OBSB];  // what quad_observe reports: the raw [qpos, qvel]
 #pragma unroll
@@ -158,155 +157,64 @@ __global__ __launch_bounds__(128) void k_brax_episode(const KConsts<float>* __re
 
 }  // namespace
 
-template <>
-hipError_t launch_brax_inst<BA_KIND, BA_MB>(const KConsts<float>* kc, const KParams& kp, const BraxNet& net,
-                                            const float* packed, const BraxEpisodeArgs& a, hipStream_t s) {
-  const brax::Net dn{net.nb1, net.actfn};
-  const int bytes = brax::Layout{net.nb1, BA_MB}.lds_floats() * int(sizeof(float));  // <= 64 KB: no opt-in
-  constexpr int KIND = BA_KIND == 1 ? QUAD_ENV_BRAX_TRAJ : QUAD_ENV_BRAX_HOVER;
-  hipLaunchKernelGGL((k_brax_episode<KIND, BA_MB>), dim3((kp.n + 63) / 64), dim3(128), bytes, s, kc, kp, packed, dn, a);
+template <int BKIND, int MB>
+hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
+                            const BraxEpisodeArgs& a, hipStream_t s) {
+  const actor::Net dn{net.nb1, net.actfn};
+  const int bytes = brax::Layout{net.nb1, MB}.lds_bytes();  // <= 64 KB: no opt-in
+  constexpr int KIND = BKIND == 1 ? QUAD_ENV_BRAX_TRAJ : QUAD_ENV_BRAX_HOVER;
+  hipLaunchKernelGGL((k_brax_episode<KIND, MB>), dim3((kp.n + 63) / 64), dim3(128), bytes, s, kc, kp, packed, dn, a);
   return hipGetLastError();
 }
+template hipError_t launch_brax_inst<BA_KIND, BA_MB>(const KConsts<float>*, const KParams&, const ActorNet&, const float*,
+                                                     const BraxEpisodeArgs&, hipStream_t);
 
 }  // namespace quadenv
 
 #else  // the C entry points' object
 
-#define BA_DECLARE(K, M)                                                                                       \
-  template <>                                                                                                  \
-  hipError_t launch_brax_inst<K, M>(const KConsts<float>*, const KParams&, const BraxNet&, const float*,      \
-                                    const BraxEpisodeArgs&, hipStream_t);
-BA_DECLARE(0, 2) BA_DECLARE(0, 4) BA_DECLARE(0, 8)
-BA_DECLARE(1, 2) BA_DECLARE(1, 4) BA_DECLARE(1, 8)
-#undef BA_DECLARE
-
 namespace {
 
 int bfail(int code, const char* m) { return set_error(code, m); }
 
-template <int BKIND>
-hipError_t launch_by_mb(const KConsts<float>* kc, const KParams& kp, const BraxNet& net, const float* packed,
-                        const BraxEpisodeArgs& a, hipStream_t s) {
-  switch (net.mb) {
-    case 2: return launch_brax_inst<BKIND, 2>(kc, kp, net, packed, a, s);
-    case 4: return launch_brax_inst<BKIND, 4>(kc, kp, net, packed, a, s);
-    case 8: return launch_brax_inst<BKIND, 8>(kc, kp, net, packed, a, s);
-  }
-  return hipErrorInvalidValue;  // brax_net_of admits no other
-}
-
-// ---- pack: one thread per float of the f32 regions, then one per (block n, lane) unit of the two W1 piece
-// regions and one per (k-step g, lane) unit of the W2 pieces. Kernels are flax's [in, out].
-__global__ void k_brax_pack(QuadBraxActorParams p, int h1, int h2, float* __restrict__ out) {
-  const brax::Layout lay{h1 / 32, h2 / 32};
-  const int nf = lay.w1p(), n1 = lay.nb1 * 64, n2 = lay.steps() * 64;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= nf + 2 * n1 + n2) return;
-  if (idx < nf) {
-    float v;
-    if (idx < lay.w3()) {  // B1 | B2: [block][half][reg]
-      const bool second = idx >= lay.b2();
-      const int t = idx - (second ? lay.b2() : 0);
-      v = (second ? p.b1 : p.b0)[32 * (t / 32) + acc_row(t % 16, (t / 16) % 2)];
-    } else if (idx < lay.b3()) {  // W3: [m][reg][half][out]
-      const int t = idx - lay.w3();
-      v = p.w2[size_t(32 * (t / 256) + acc_row((t / 16) % 16, (t / 8) % 2)) * brax::NLOG + t % 8];
-    } else if (idx < lay.mean()) {
-      v = p.b2[idx - lay.b3()];
-    } else if (idx < lay.stdv()) {
-      const int f = idx - lay.mean();
-      v = f < brax::OBSB ? p.mean[f] : 0.f;
-    } else if (idx < lay.misc()) {
-      const int f = idx - lay.stdv();
-      v = f < brax::OBSB ? p.std[f] : 1.f;
-    } else {
-      v = idx == lay.misc() ? p.min_std : 0.f;
-    }
-    out[idx] = v;
-    return;
-  }
-  const int u = idx - nf;
-  const int lane = u % 64, r = lane & 31, h = lane >> 5;
-  float v8[8];
-  bf16x8* dst;
-  if (u < 2 * n1) {  // A[neuron 32 n + r][feature 16 t + 8 h + j]
-    const int t = u / n1, n = (u % n1) / 64;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int f = 16 * t + 8 * h + j;
-      v8[j] = f < brax::OBSB ? p.w0[size_t(f) * h1 + 32 * n + r] : 0.f;
-    }
-    dst = reinterpret_cast<bf16x8*>(out + (t ? lay.w1q() : lay.w1p())) + n * 3 * 64 + lane;
-  } else {  // A[neuron 32 m + r][input 32 n + acc_row(8 t + j, h)] of k-step g = (n * 2 + t) * MB + m
-    const int g = (u - 2 * n1) / 64, m = g % lay.mb, t = (g / lay.mb) % 2, n = g / (2 * lay.mb);
-#pragma unroll
-    for (int j = 0; j < 8; j++) v8[j] = p.w1[size_t(32 * n + acc_row(8 * t + j, h)) * h2 + 32 * m + r];
-    dst = reinterpret_cast<bf16x8*>(out + lay.w2p()) + g * 3 * 64 + lane;
-  }
-  const P3 x = split8(v8);
-#pragma unroll
-  for (int q = 0; q < 3; q++) dst[q * 64] = x.p[q];
-}
-
-// ---- act: wave w of the grid takes the 32-row tiles w, w + waves, ...; lanes l and l + 32 carry row l & 31
-constexpr int ACT_BLK = 256;
+// ---- act (actor_core.h act_tiles): logits and the NormalTanh action of a row
 template <int MB>
-__global__ __launch_bounds__(ACT_BLK) void k_brax_act(const float* __restrict__ packed, brax::Net net,
-                                                      const float* __restrict__ obs, float* __restrict__ logits,
-                                                      float* __restrict__ actions_env, int32_t n, int deterministic,
-                                                      uint64_t seed, uint64_t env_id_base, uint32_t noise_step) {
+__global__ __launch_bounds__(actor::ACT_BLK) void k_brax_act(const float* __restrict__ packed, actor::Net net,
+                                                             const float* __restrict__ obs, float* __restrict__ logits,
+                                                             float* __restrict__ actions_env, int32_t n,
+                                                             int deterministic, uint64_t seed, uint64_t env_id_base,
+                                                             uint32_t noise_step) {
   extern __shared__ float lds[];
   const brax::Layout lay{net.nb1, MB};
-  brax::stage<ACT_BLK>(lds, packed, lay);
+  actor::stage<actor::ACT_BLK>(lds, packed, lay.lds_floats());
   const float min_std = lds[lay.misc()];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
-  const int tiles = (n + TILE - 1) / TILE;
-  for (int tile = blockIdx.x * (ACT_BLK / 64) + wave; tile < tiles; tile += gridDim.x * (ACT_BLK / 64)) {
-    const int row = tile * TILE + (lane & 31);
-    const bool ok = row < n;
+  actor::act_tiles(n, [&](int row, bool ok, int h) {
     float ob[brax::OBSB], lg[brax::NLOG], ac[4];
 #pragma unroll
     for (int k = 0; k < brax::OBSB; k++) ob[k] = ok ? obs[size_t(row) * brax::OBSB + k] : 0.f;
     brax::forward<MB>(lds, packed, net, ob, lg);
     brax::env_action(lg, min_std, deterministic != 0, seed, env_id_base + uint64_t(row), noise_step, ac);
-    if (!ok || h) continue;  // one lane per row stores
+    if (!ok || h) return;  // one lane per row stores
     if (logits) {
 #pragma unroll
       for (int k = 0; k < 2; k++)
         reinterpret_cast<float4*>(logits)[size_t(row) * 2 + k] = make_float4(lg[4 * k], lg[4 * k + 1], lg[4 * k + 2], lg[4 * k + 3]);
     }
     reinterpret_cast<float4*>(actions_env)[row] = make_float4(ac[0], ac[1], ac[2], ac[3]);
-  }
-}
-
-template <int MB>
-hipError_t launch_act(const BraxNet& net, const float* packed, const float* obs, float* logits, float* actions_env,
-                      int32_t n, int deterministic, uint64_t seed, uint64_t base, uint32_t step, hipStream_t s) {
-  const int tiles = (n + TILE - 1) / TILE, want = (tiles + ACT_BLK / 64 - 1) / (ACT_BLK / 64);
-  const int bytes = brax::Layout{net.nb1, MB}.lds_floats() * int(sizeof(float));
-  hipLaunchKernelGGL((k_brax_act<MB>), dim3(want < 512 ? want : 512), dim3(ACT_BLK), bytes, s, packed,
-                     brax::Net{net.nb1, net.actfn}, obs, logits, actions_env, n, deterministic, seed, base, step);
-  return hipGetLastError();
+  });
 }
 
 }  // namespace
 
-int brax_net_of(const QuadBraxActorArch* a, BraxNet* out) {
-  if (!a) return bfail(QUAD_EINVAL, "brax actor arch is NULL");
-  if (a->h1 < 32 || a->h1 > arch::MAX_H1 || a->h1 % 32 != 0)
-    return bfail(QUAD_EINVAL, "brax actor arch: h1 must be a multiple of 32 in [32, 512]");
-  if (a->h2 != 64 && a->h2 != 128 && a->h2 != 256)
-    return bfail(QUAD_EINVAL, "brax actor arch: h2 must be 64, 128 or 256");
-  if (a->activation != QUAD_ACTFN_RELU && a->activation != QUAD_ACTFN_TANH && a->activation != QUAD_ACTFN_SILU)
-    return bfail(QUAD_EINVAL, "brax actor arch: activation must be QUAD_ACTFN_RELU, _TANH or _SILU");
-  *out = BraxNet{a->h1 / 32, a->h2 / 32, a->activation};
-  return QUAD_OK;
-}
+int brax_net_of(const QuadBraxActorArch* a, ActorNet* out) { return actor::net_of(a, "brax actor arch", true, out); }
 
-hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const BraxNet& net,
+hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
                                const float* packed, const BraxEpisodeArgs& a, hipStream_t s) {
-  return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_by_mb<1>(kc, kp, net, packed, a, s)
-                                        : launch_by_mb<0>(kc, kp, net, packed, a, s);
+  return with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_inst<1, MB>(kc, kp, net, packed, a, s)
+                                          : launch_brax_inst<0, MB>(kc, kp, net, packed, a, s);
+  });
 }
 
 }  // namespace quadenv
@@ -316,41 +224,42 @@ using namespace quadenv;
 extern "C" {
 
 int64_t quad_brax_actor_packed_floats(const QuadBraxActorArch* a) {
-  BraxNet net;
+  ActorNet net;
   if (brax_net_of(a, &net)) return -1;
   return brax::Layout{net.nb1, net.mb}.floats();
 }
 
 int quad_brax_actor_pack(const QuadBraxActorArch* a, const QuadBraxActorParams* p, float* packed, void* stream) {
-  BraxNet net;
+  ActorNet net;
   if (int rc = brax_net_of(a, &net)) return rc;
   if (!p || !packed) return bfail(QUAD_EINVAL, "quad_brax_actor_pack: params/packed is NULL");
   if (!p->w0 || !p->b0 || !p->w1 || !p->b1 || !p->w2 || !p->b2 || !p->mean || !p->std)
     return bfail(QUAD_EINVAL, "quad_brax_actor_pack: a parameter pointer is NULL");
   if (reinterpret_cast<uintptr_t>(packed) & 15u)
     return bfail(QUAD_EINVAL, "quad_brax_actor_pack: packed must be 16-byte aligned");
-  const brax::Layout lay{net.nb1, net.mb};
-  const int threads = lay.w1p() + 2 * lay.nb1 * 64 + lay.steps() * 64;
-  hipLaunchKernelGGL(k_brax_pack, dim3((threads + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), *p,
-                     a->h1, a->h2, packed);
-  return hipGetLastError() == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_pack launch failed");
+  const hipError_t e = actor::launch_pack<brax::Layout, false, brax::OBSB>(brax::Layout{net.nb1, net.mb}, *p, packed,
+                                                                          static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_pack launch failed");
 }
 
 int quad_brax_actor_act(const QuadBraxActorArch* a, const float* packed, const float* obs, float* logits,
                         float* actions_env, int32_t n, int32_t deterministic, uint64_t seed, uint64_t env_id_base,
                         uint32_t noise_step, void* stream) {
-  BraxNet net;
+  ActorNet net;
   if (int rc = brax_net_of(a, &net)) return rc;
   if (!packed || !obs || !actions_env) return bfail(QUAD_EINVAL, "quad_brax_actor_act: NULL argument");
   if (n <= 0) return bfail(QUAD_EINVAL, "quad_brax_actor_act: n must be > 0");
   if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(actions_env) |
        reinterpret_cast<uintptr_t>(logits)) & 15u)
     return bfail(QUAD_EINVAL, "quad_brax_actor_act: packed, logits and actions_env must be 16-byte aligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const hipError_t e =
-      net.mb == 2   ? launch_act<2>(net, packed, obs, logits, actions_env, n, deterministic, seed, env_id_base, noise_step, s)
-      : net.mb == 4 ? launch_act<4>(net, packed, obs, logits, actions_env, n, deterministic, seed, env_id_base, noise_step, s)
-                    : launch_act<8>(net, packed, obs, logits, actions_env, n, deterministic, seed, env_id_base, noise_step, s);
+  const hipError_t e = with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    const int bytes = brax::Layout{net.nb1, MB}.lds_bytes();
+    hipLaunchKernelGGL((k_brax_act<MB>), actor::act_grid(n), dim3(actor::ACT_BLK), bytes,
+                       static_cast<hipStream_t>(stream), packed, actor::Net{net.nb1, net.actfn}, obs, logits, actions_env,
+                       n, deterministic, seed, env_id_base, noise_step);
+    return hipGetLastError();
+  });
   return e == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_act launch failed");
 }
 

@@ -7,14 +7,12 @@
 
 #include "../../include/quadenv.h"
 #include "env_tiles.h"
+#include "policy_episode.h"  // ActorNet
 
 namespace quadenv {
 
-struct BraxNet {  // a checked QuadBraxActorArch: H1 / 32, H2 / 32 (2, 4 or 8), QUAD_ACTFN_*
-  int nb1, mb, actfn;
-};
 // QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
-int brax_net_of(const QuadBraxActorArch* a, BraxNet* out);
+int brax_net_of(const QuadBraxActorArch* a, ActorNet* out);
 struct BraxEpisodeArgs {  // QuadBraxRun, flattened (trace_envs 0 when no trace is requested)
   int32_t max_steps, trace_envs, deterministic;
   uint32_t noise_step0;
@@ -23,7 +21,7 @@ struct BraxEpisodeArgs {  // QuadBraxRun, flattened (trace_envs 0 when no trace 
   float *trace_actions, *trace_obs, *trace_pos, *trace_target;
 };
 // k_brax_episode<env_kind, mb> over all envs of kp, 64-env blocks of two one-tile waves
-hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const BraxNet& net,
+hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
                                const float* packed, const BraxEpisodeArgs& a, hipStream_t s);
 
 }  // namespace quadenv

@@ -53,8 +53,8 @@ hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, 
 
 // ---- the general actor's forms (actor_arch.hip; quad_actor_episode / quad_actor_waypoints): the same closed loop
 // with actor_arch.h's forward, in 64-env blocks of two one-tile waves, the constant block read from memory
-struct ActorNet {  // a checked QuadActorArch: H1 / 32, H2 / 32 (2, 4 or 8), tanh (1) or ReLU (0)
-  int nb1, mb, tanh_act;
+struct ActorNet {  // a checked QuadActorArch or QuadBraxActorArch: H1 / 32, H2 / 32 (2, 4 or 8), QUAD_ACTFN_*
+  int nb1, mb, actfn;
 };
 // QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
 int actor_net_of(const QuadActorArch* a, ActorNet* out);

@@ -1552,7 +1552,7 @@ int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* 
 int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
                       void* stream) {
   const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_episode: ") + m); };
-  BraxNet net;
+  ActorNet net;
   if (int rc = brax_net_of(arch, &net)) return rc;
   if (!h || !packed || !r) return bad("handle/packed/run is NULL");
   if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
