@@ -612,6 +612,49 @@ typedef struct QuadBraxRun {
 int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
                       void* stream);
 
+/* ---- The Brax learner's unrolls: sampled actions with their behaviour log-probs, per step in two
+ * launches or `steps` whole steps of ppo/brax_ppo.py BraxPPO._unrolls in one. Added within ABI v8.
+ *
+ * quad_brax_actor_sample: quad_brax_actor_act for sampled actions, with two more outputs per row.
+ * raw [n,4] = loc + scale z, the value the env action's tanh is taken of; log_prob [n] =
+ * NormalTanh.log_prob(logits, raw), computed from raw (not from z) with the expression the loss evaluates later:
+ * sum over the four components of -1/2 ((raw - loc) / scale)^2 - 1/2 log 2 pi - log scale
+ * - 2 (log 2 - raw - softplus(-2 raw)), in f32, every operation rounded on its own. Noise: quad_brax_actor_act's
+ * stream and key, so for equal arguments logits and actions_env (= tanh(raw), quad_brax_actor_act's tanh: within
+ * 2 ulp of the exact tanh of the stored raw) have quad_brax_actor_act's bits for deterministic = 0. logits (or NULL), raw and
+ * actions_env are 16-byte aligned. A row's result depends on neither n nor the other rows. */
+int quad_brax_actor_sample(const QuadBraxActorArch* arch, const float* packed, const float* obs, float* logits,
+                           float* raw, float* log_prob, float* actions_env, int32_t n, uint64_t seed,
+                           uint64_t env_id_base, uint32_t noise_step, void* stream);
+/* `steps` whole steps of the learner's unroll loop in ONE launch, on a handle of kind QUAD_ENV_BRAX_HOVER or
+ * _BRAX_TRAJ with auto_reset = 1. Step t (0 <= t < steps) of env i writes row t * N + i of the time-major buffers
+ * (all required, device): obs [steps,N,21] the observation the action is taken from; raw [steps,N,4] (16-byte
+ * aligned) and log_prob [steps,N] as quad_brax_actor_sample gives them with noise step noise_step0 + t and env id =
+ * the handle's env_id_base + i; reward; discount = 1 - (terminated | truncated); truncation = truncated &
+ * ~terminated (EpisodeWrapper's), as floats. A finished env is reset as quad_step resets it (the first state of its
+ * episode) and the next row starts there. After each group of unroll_length steps the current (post-reset)
+ * observation goes to next_obs [steps / unroll_length, N, 21].
+ * Monitor-style accounting: ep_ret [N] f32, read at entry and written at exit, accumulates an env's rewards; when
+ * the env finishes, ep_ret and a count of one are added to stats [QUAD_POLICY_STAT_SLOTS][2] (double: return sum,
+ * episodes; the caller zeroes it and sums over the slots) and ep_ret is cleared.
+ * Contract: every output, the handle's final state and ep_ret are bit-identical to this loop on a second handle
+ * with auto_reset = 1: quad_observe once; per step quad_brax_actor_sample (same seed and env_id_base,
+ * noise_step0 + t), then quad_step. The episode count equals the loop's; the return sum may differ by the order of
+ * the double additions. QUAD_EINVAL, with nothing launched: another env kind, auto_reset = 0, an arch outside the
+ * family, a NULL or misaligned buffer, steps < 1, unroll_length < 1, steps not a multiple of unroll_length,
+ * steps * N * 84 >= 2^32 (rows use 32-bit byte offsets). */
+typedef struct QuadBraxUnroll {
+  float *obs, *raw, *log_prob, *reward, *discount, *truncation;
+  float* next_obs;
+  float* ep_ret;
+  double* stats;
+  int32_t steps, unroll_length;
+  uint32_t noise_step0;
+  uint64_t seed;
+} QuadBraxUnroll;
+int quad_brax_unroll(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxUnroll* u,
+                     void* stream);
+
 /* Finish the pending step (end of a rollout): the epilogue for row (t-1) % rows if the cursor
  * marks one pending, then clears the mark. A no-op otherwise. */
 int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* cursor, int32_t n,

@@ -194,6 +194,15 @@ class QuadBraxRun(C.Structure):
 POLICY_STAT_SLOTS = 1024
 
 
+class QuadBraxUnroll(C.Structure):
+    """quad_brax_unroll's descriptor: time-major row buffers [steps, N, .], next_obs [steps / unroll_length, N, 21],
+    ep_ret [N], stats [POLICY_STAT_SLOTS, 2] float64 (return sum, episodes)."""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "raw", "log_prob", "reward", "discount", "truncation", "next_obs",
+                                          "ep_ret", "stats")] + \
+               [("steps", C.c_int32), ("unroll_length", C.c_int32), ("noise_step0", C.c_uint32),
+                ("seed", C.c_uint64)]
+
+
 class QuadRolloutPost(C.Structure):
     _fields_ = [("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p),
                 ("terminal_obs", C.c_void_p), ("buf_rew", C.c_void_p), ("last_start", C.c_void_p),
@@ -224,7 +233,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_deploy_obs", "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints",
            "quad_actor_packed_floats", "quad_actor_pack", "quad_actor_act", "quad_actor_episode",
            "quad_actor_waypoints",
-           "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode")
+           "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode",
+           "quad_brax_actor_sample", "quad_brax_unroll")
 
 
 class QuadRollout(C.Structure):
@@ -366,6 +376,12 @@ def _declare(L):
     L.quad_brax_actor_act.argtypes = [barch, vp, vp, vp, vp, i32, i32, u64, u64, u32, vp]
     L.quad_brax_episode.argtypes = [vp, barch, vp, C.POINTER(QuadBraxRun), vp]
     for n in ("quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode"):
+        getattr(L, n).restype = C.c_int
+    if not hasattr(L, "quad_brax_unroll"):  # nor with the learner's unroll entry points
+        raise QuadError(f"{LIB_PATH} was built before the Brax unroll's entry points (quad_brax_unroll); rebuild it")
+    L.quad_brax_actor_sample.argtypes = [barch, vp, vp, vp, vp, vp, vp, i32, u64, u64, u32, vp]
+    L.quad_brax_unroll.argtypes = [vp, barch, vp, C.POINTER(QuadBraxUnroll), vp]
+    for n in ("quad_brax_actor_sample", "quad_brax_unroll"):
         getattr(L, n).restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")

@@ -129,8 +129,21 @@ __device__ __forceinline__ void gauss4_brax(uint64_t seed, uint64_t env, uint32_
   }
 }
 
-// NormalTanh on the logits: tanh(loc) or tanh(loc + scale z), scale = softplus(raw) + min_std; the products and
-// sums are separate f32 roundings (no contraction), as torch forms them
+// NormalTanh's sample on the logits: raw = loc + scale z, scale = softplus(raw scale) + min_std; the products and
+// sums are separate f32 roundings (no contraction), as torch forms them. The one definition of the draw: the
+// env action below, quad_brax_actor_sample and the unroll kernel (brax_unroll.hip) all take raw from here.
+__device__ __forceinline__ void sample_raw(const float (&lg)[NLOG], float min_std, uint64_t seed, uint64_t env,
+                                           uint32_t step, float (&raw)[4], float (&sc)[4]) {
+  float z[4];
+  gauss4_brax(seed, env, step, z);
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    sc[k] = __fadd_rn(softplus_f32(lg[4 + k]), min_std);
+    raw[k] = __fadd_rn(lg[k], __fmul_rn(sc[k], z[k]));
+  }
+}
+
+// NormalTanh on the logits: tanh(loc) or tanh(raw)
 __device__ __forceinline__ void env_action(const float (&lg)[NLOG], float min_std, bool deterministic, uint64_t seed,
                                            uint64_t env, uint32_t step, float (&a)[4]) {
   if (deterministic) {
@@ -138,13 +151,40 @@ __device__ __forceinline__ void env_action(const float (&lg)[NLOG], float min_st
     for (int k = 0; k < 4; k++) a[k] = actor::tanh_f32(lg[k]);
     return;
   }
-  float z[4];
-  gauss4_brax(seed, env, step, z);
+  float raw[4], sc[4];
+  sample_raw(lg, min_std, seed, env, step, raw, sc);
+#pragma unroll
+  for (int k = 0; k < 4; k++) a[k] = actor::tanh_f32(raw[k]);
+}
+
+// NormalTanh.log_prob(logits, raw) (ppo/brax_ppo.py) from the stored raw action, not from z -- the expression the
+// loss evaluates later on the same raw: sum over the four components of
+//   -0.5 ((raw - loc) / scale)^2 - 0.5 log 2 pi - log scale - 2 (log 2 - raw - softplus(-2 raw)),
+// every operation its own f32 rounding in torch's order (no contraction), libm's logf, softplus_f32 above and the
+// correctly rounded division. sc: sample_raw's scale.
+__device__ __forceinline__ float log_prob(const float (&lg)[NLOG], const float (&raw)[4], const float (&sc)[4]) {
+  constexpr float HALF_LOG_2PI = 0.918938533204672742f, LOG2 = 0.693147180559945309f;
+  float lp[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const float sc = __fadd_rn(softplus_f32(lg[4 + k]), min_std);
-    a[k] = actor::tanh_f32(__fadd_rn(lg[k], __fmul_rn(sc, z[k])));
+    const float t = __fdiv_rn(__fsub_rn(raw[k], lg[k]), sc[k]);
+    const float n = __fsub_rn(__fsub_rn(__fmul_rn(-0.5f, __fmul_rn(t, t)), HALF_LOG_2PI), logf(sc[k]));
+    const float sp = softplus_f32(__fmul_rn(-2.0f, raw[k]));
+    const float det = __fmul_rn(2.0f, __fsub_rn(__fsub_rn(LOG2, raw[k]), sp));
+    lp[k] = __fsub_rn(n, det);
   }
+  return __fadd_rn(__fadd_rn(__fadd_rn(lp[0], lp[1]), lp[2]), lp[3]);
+}
+
+// One sampled step of a row, the definition quad_brax_actor_sample and the unroll kernel share: raw, its log-prob
+// and the env action tanh(raw) (env_action's bits for deterministic = 0)
+__device__ __forceinline__ void sample_action(const float (&lg)[NLOG], float min_std, uint64_t seed, uint64_t env,
+                                              uint32_t step, float (&raw)[4], float& logp, float (&a)[4]) {
+  float sc[4];
+  sample_raw(lg, min_std, seed, env, step, raw, sc);
+  logp = log_prob(lg, raw, sc);
+#pragma unroll
+  for (int k = 0; k < 4; k++) a[k] = actor::tanh_f32(raw[k]);
 }
 
 }  // namespace brax

@@ -1,11 +1,13 @@
 // brax_actor.hip -- the Brax-profile policy (brax_actor.h: 21 -> H1 -> H2 -> 8, ReLU / tanh / SiLU, the running
-// statistics' normaliser in front) behind quad_brax_actor_pack / quad_brax_actor_act, and the fused episode kernel
-// of the brax env kinds that flies it (quad_brax_episode).
+// statistics' normaliser in front) behind quad_brax_actor_pack / quad_brax_actor_act / quad_brax_actor_sample, and the
+// fused episode kernel of the brax env kinds that flies it (quad_brax_episode). The learner's unroll kernel
+// (quad_brax_unroll) is brax_unroll.hip.
 //
 // Kernels
 //   actor::k_pack<brax::Layout, ..>
 //                             flax [in, out] parameters + mean / std / min_std -> the packed image
-//   k_brax_act<MB>            logits and the env action of n rows, one wave per 32-row tile, grid-stride
+//   k_brax_act<MB, SAMPLE>    logits and the env action of n rows, one wave per 32-row tile, grid-stride; SAMPLE: the
+//                             sampled action with its raw value and log-prob
 //   k_brax_episode<KIND, MB>  whole episodes: 64-env blocks of two one-tile waves, every env's state in registers,
 //                             per step forward -> NormalTanh -> brax_step -> metrics; the handle's constant block
 //                             is read from memory
@@ -33,6 +35,11 @@ namespace quadenv {
 template <int BKIND, int MB>
 hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
                             const BraxEpisodeArgs& a, hipStream_t s);
+
+// brax_unroll.hip's, one per (kind, MB) object of its own
+template <int BKIND, int MB>
+hipError_t launch_brax_unroll_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
+                                   const BraxUnrollArgs& a, hipStream_t s);
 
 #if defined(BA_KIND)
 namespace {
@@ -177,10 +184,12 @@ namespace {
 
 int bfail(int code, const char* m) { return set_error(code, m); }
 
-// ---- act (actor_core.h act_tiles): logits and the NormalTanh action of a row
-template <int MB>
+// ---- act / sample (actor_core.h act_tiles): logits and the NormalTanh action of a row; SAMPLE: the sampled action
+// with its raw value and log-prob (brax_actor.h sample_action)
+template <int MB, bool SAMPLE>
 __global__ __launch_bounds__(actor::ACT_BLK) void k_brax_act(const float* __restrict__ packed, actor::Net net,
                                                              const float* __restrict__ obs, float* __restrict__ logits,
+                                                             float* __restrict__ raw_out, float* __restrict__ logp_out,
                                                              float* __restrict__ actions_env, int32_t n,
                                                              int deterministic, uint64_t seed, uint64_t env_id_base,
                                                              uint32_t noise_step) {
@@ -189,18 +198,40 @@ __global__ __launch_bounds__(actor::ACT_BLK) void k_brax_act(const float* __rest
   actor::stage<actor::ACT_BLK>(lds, packed, lay.lds_floats());
   const float min_std = lds[lay.misc()];
   actor::act_tiles(n, [&](int row, bool ok, int h) {
-    float ob[brax::OBSB], lg[brax::NLOG], ac[4];
+    float ob[brax::OBSB], lg[brax::NLOG], ac[4], raw[4], logp = 0.f;
 #pragma unroll
     for (int k = 0; k < brax::OBSB; k++) ob[k] = ok ? obs[size_t(row) * brax::OBSB + k] : 0.f;
     brax::forward<MB>(lds, packed, net, ob, lg);
-    brax::env_action(lg, min_std, deterministic != 0, seed, env_id_base + uint64_t(row), noise_step, ac);
+    if constexpr (SAMPLE)
+      brax::sample_action(lg, min_std, seed, env_id_base + uint64_t(row), noise_step, raw, logp, ac);
+    else
+      brax::env_action(lg, min_std, deterministic != 0, seed, env_id_base + uint64_t(row), noise_step, ac);
     if (!ok || h) return;  // one lane per row stores
     if (logits) {
 #pragma unroll
       for (int k = 0; k < 2; k++)
         reinterpret_cast<float4*>(logits)[size_t(row) * 2 + k] = make_float4(lg[4 * k], lg[4 * k + 1], lg[4 * k + 2], lg[4 * k + 3]);
     }
+    if constexpr (SAMPLE) {
+      reinterpret_cast<float4*>(raw_out)[row] = make_float4(raw[0], raw[1], raw[2], raw[3]);
+      logp_out[row] = logp;
+    }
     reinterpret_cast<float4*>(actions_env)[row] = make_float4(ac[0], ac[1], ac[2], ac[3]);
+  });
+}
+
+// the launch of both entry points (arguments checked by the caller)
+template <bool SAMPLE>
+hipError_t launch_brax_act(const ActorNet& net, const float* packed, const float* obs, float* logits, float* raw,
+                           float* log_prob, float* actions_env, int32_t n, int deterministic, uint64_t seed,
+                           uint64_t env_id_base, uint32_t noise_step, void* stream) {
+  return with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    const int bytes = brax::Layout{net.nb1, MB}.lds_bytes();
+    hipLaunchKernelGGL((k_brax_act<MB, SAMPLE>), actor::act_grid(n), dim3(actor::ACT_BLK), bytes,
+                       static_cast<hipStream_t>(stream), packed, actor::Net{net.nb1, net.actfn}, obs, logits, raw,
+                       log_prob, actions_env, n, deterministic, seed, env_id_base, noise_step);
+    return hipGetLastError();
   });
 }
 
@@ -214,6 +245,15 @@ hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int 
     constexpr int MB = decltype(mb)::value;
     return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_inst<1, MB>(kc, kp, net, packed, a, s)
                                           : launch_brax_inst<0, MB>(kc, kp, net, packed, a, s);
+  });
+}
+
+hipError_t launch_brax_unroll(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
+                              const float* packed, const BraxUnrollArgs& a, hipStream_t s) {
+  return with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_unroll_inst<1, MB>(kc, kp, net, packed, a, s)
+                                          : launch_brax_unroll_inst<0, MB>(kc, kp, net, packed, a, s);
   });
 }
 
@@ -252,14 +292,26 @@ int quad_brax_actor_act(const QuadBraxActorArch* a, const float* packed, const f
   if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(actions_env) |
        reinterpret_cast<uintptr_t>(logits)) & 15u)
     return bfail(QUAD_EINVAL, "quad_brax_actor_act: packed, logits and actions_env must be 16-byte aligned");
-  const hipError_t e = with_mb(net.mb, [&](auto mb) {
-    constexpr int MB = decltype(mb)::value;
-    const int bytes = brax::Layout{net.nb1, MB}.lds_bytes();
-    hipLaunchKernelGGL((k_brax_act<MB>), actor::act_grid(n), dim3(actor::ACT_BLK), bytes,
-                       static_cast<hipStream_t>(stream), packed, actor::Net{net.nb1, net.actfn}, obs, logits, actions_env,
-                       n, deterministic, seed, env_id_base, noise_step);
-    return hipGetLastError();
-  });
+  const hipError_t e = launch_brax_act<false>(net, packed, obs, logits, nullptr, nullptr, actions_env, n, deterministic,
+                                             seed, env_id_base, noise_step, stream);
+  return e == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_act launch failed");
+}
+
+int quad_brax_actor_sample(const QuadBraxActorArch* a, const float* packed, const float* obs, float* logits, float* raw,
+                           float* log_prob, float* actions_env, int32_t n, uint64_t seed, uint64_t env_id_base,
+                           uint32_t noise_step, void* stream) {
+  ActorNet net;
+  if (int rc = brax_net_of(a, &net)) return rc;
+  if (!packed || !obs || !raw || !log_prob || !actions_env)
+    return bfail(QUAD_EINVAL, "quad_brax_actor_sample: NULL argument");
+  if (n <= 0) return bfail(QUAD_EINVAL, "quad_brax_actor_sample: n must be > 0");
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(actions_env) |
+       reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(logits)) & 15u)
+    return bfail(QUAD_EINVAL, "quad_brax_actor_sample: packed, logits, raw and actions_env must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(log_prob) & 3u)
+    return bfail(QUAD_EINVAL, "quad_brax_actor_sample: log_prob must be 4-byte aligned");
+  const hipError_t e = launch_brax_act<true>(net, packed, obs, logits, raw, log_prob, actions_env, n, 0, seed,
+                                            env_id_base, noise_step, stream);
   return e == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_act launch failed");
 }
 

@@ -1576,6 +1576,36 @@ int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float*
   return QUAD_OK;
 }
 
+// ---- the Brax learner's unrolls on the brax kinds (kernel: brax_unroll.hip)
+int quad_brax_unroll(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxUnroll* u,
+                     void* stream) {
+  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_unroll: ") + m); };
+  ActorNet net;
+  if (int rc = brax_net_of(arch, &net)) return rc;
+  if (!h || !packed || !u) return bad("handle/packed/unroll is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
+    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
+  if (!h->cfg.auto_reset) return bad("the handle must have auto_reset = 1");
+  if (u->steps < 1 || u->unroll_length < 1) return bad("steps and unroll_length must be >= 1");
+  if (u->steps % u->unroll_length) return bad("steps must be a multiple of unroll_length");
+  if (!u->obs || !u->raw || !u->log_prob || !u->reward || !u->discount || !u->truncation || !u->next_obs ||
+      !u->ep_ret || !u->stats)
+    return bad("every buffer is required");
+  const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if ((at(packed) | at(u->raw)) & 15u) return bad("packed and raw must be 16-byte aligned");
+  if ((at(u->obs) | at(u->log_prob) | at(u->reward) | at(u->discount) | at(u->truncation) | at(u->next_obs) |
+       at(u->ep_ret)) & 3u)
+    return bad("the float buffers must be 4-byte aligned");
+  if (at(u->stats) & 7u) return bad("stats must be 8-byte aligned");
+  if (int64_t(u->steps) * h->n * 84 > int64_t(UINT32_MAX))
+    return bad("steps * N too large (rows use 32-bit byte offsets)");
+  const BraxUnrollArgs a{u->obs, u->raw, u->log_prob, u->reward, u->discount, u->truncation, u->next_obs, u->ep_ret,
+                         u->stats, u->steps, u->unroll_length, u->noise_step0, u->seed};
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_brax_unroll(h->kdev, h->kp, h->cfg.env_kind, net, packed, a, static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
 int quad_target_info(QuadHandle* h, float* target_info, void* stream) {
   if (!h || !target_info) return fail(QUAD_EINVAL, "handle/target_info is NULL");
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)

@@ -59,6 +59,9 @@ class BraxPPOConfig:
     value_hidden_sizes: tuple = (128, 128)
     activation: str = "relu"
     min_std: float = 0.001
+    # collect the unrolls in one launch per training step (FusedBraxActor.unroll: Philox noise) instead of the torch
+    # per-step loop (torch.Generator noise): another sample path of the same algorithm
+    fused_unroll: bool = False
 
 
 _ACT = {"relu": F.relu, "tanh": torch.tanh, "silu": F.silu}
@@ -256,6 +259,13 @@ class BraxPPO:
         self.seed = int(seed)
         self._fused = None       # FusedBraxActor of self.net, built by the first evaluate() that takes the launch
         self._eval_count = 0
+        self._noise_t = 0        # noise step of the next fused unroll: advances by U * L per training step, never reset
+        if c.fused_unroll:
+            from .fused import brax_arch_of, brax_unroll_supported
+            brax_arch_of(c.policy_hidden_sizes, c.activation)  # ValueError naming the family
+            if not brax_unroll_supported(c.policy_hidden_sizes, c.activation, env):
+                raise ValueError("fused_unroll=True needs a brax env kind (brax_hover / brax_jax_mjx) with auto-reset "
+                                 "and a policy the one-launch unroll is chosen for (ppo.fused.brax_unroll_supported)")
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)
         self.net = BraxActorCritic(env.obs_dim, 4, c).to(self.device)
@@ -272,7 +282,26 @@ class BraxPPO:
         bind_grad_bucket(list(self.net.parameters()), self._flat)  # in-place all-reduce
 
     @torch.no_grad()
+    def _unrolls_fused(self):
+        """_unrolls in one launch: the env's state stays in its handle, the noise is Philox(seed; env, _noise_t + t)."""
+        from .fused import FusedBraxActor
+        c, env = self.cfg, self.env
+        if self._obs is None:
+            self._obs = env.reset()  # first use; afterwards the handle carries the state from launch to launch
+        if self._fused is None:
+            self._fused = FusedBraxActor(self.net, self.norm)
+        self._fused.pack()  # this training step's policy and the previous statistics
+        U, L = self.num_unrolls, c.unroll_length
+        r = self._fused.unroll(env, num_unrolls=U, unroll_length=L, seed=self.seed, noise_step0=self._noise_t,
+                               ep_ret=self._ep_ret)
+        self._noise_t += U * L
+        return (r["obs"], r["nxt"], r["raw"], r["logp"], r["rew"], r["disc"], r["trunc"], r["finished"].float(),
+                r["ret_sum"])
+
+    @torch.no_grad()
     def _unrolls(self):
+        if self.cfg.fused_unroll:
+            return self._unrolls_fused()
         c, env = self.cfg, self.env
         if self._obs is None:
             self._obs = env.reset().clone()

@@ -11,7 +11,7 @@ statistics) -- instead of ~25 torch kernels. The torch ActorCritic stays the tra
 other supported architecture (quad_actor_*: 12-H1-H2-4, ReLU or tanh) for evaluation episodes and waypoint laps;
 `fused_actor_for(policy)` picks between the two. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
 21-H1-H2-8 behind the running statistics, ReLU / tanh / SiLU, NormalTanh sampling) for evaluation episodes of the
-brax env kinds.
+brax env kinds and for the learner's unrolls (sample, unroll).
 """
 from __future__ import annotations
 
@@ -394,6 +394,18 @@ def brax_launch_chosen(policy_sizes, activation, env) -> bool:
             and (tuple(int(x) for x in policy_sizes), activation) not in BRAX_KEEP_LOOP)
 
 
+# (hidden sizes, activation) for which the launch did not beat the torch unroll loop in
+# profiles/brax_unroll/bench.json (by 19's and 20's rule): it won every measured row
+BRAX_UNROLL_KEEP_LOOP = frozenset()
+
+
+def brax_unroll_supported(policy_sizes, activation, env) -> bool:
+    """quad_brax_unroll collects the learner's unrolls where quad_brax_episode flies, on an env that resets itself;
+    (sizes, activation) in BRAX_UNROLL_KEEP_LOOP stay on the torch loop."""
+    return (brax_episode_supported(policy_sizes, activation, env) and env.cfg.auto_reset == 1
+            and (tuple(int(x) for x in policy_sizes), activation) not in BRAX_UNROLL_KEEP_LOOP)
+
+
 class FusedBraxActor:
     """The Brax-profile policy (ppo/brax_ppo.py BraxActorCritic.policy, two hidden layers) with its running-statistics
     normaliser on MFMA (csrc/brax_actor.h, quad_brax_*): act on observation rows, and whole evaluation episodes of a
@@ -473,3 +485,49 @@ class FusedBraxActor:
         N.check(N.lib().quad_brax_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), self._stream()),
                 "quad_brax_episode")
         return res
+
+    def sample(self, obs: torch.Tensor, actions_env: torch.Tensor, raw: torch.Tensor, log_prob: torch.Tensor,
+               logits: Optional[torch.Tensor] = None, *, seed: int = 0, env_id_base: int = 0,
+               noise_step: int = 0) -> None:
+        """quad_brax_actor_sample: raw = loc + scale z, log_prob = NormalTanh.log_prob(logits, raw),
+        actions_env = tanh(raw) (act's bits for deterministic=False), and the logits unless None."""
+        n, dev, f32 = obs.shape[0], self.device, torch.float32
+        _need(obs, (n, N.BRAX_OBS), f32, dev, "obs")
+        _need(actions_env, (n, 4), f32, dev, "actions_env")
+        _need(raw, (n, 4), f32, dev, "raw")
+        _need(log_prob, (n,), f32, dev, "log_prob")
+        if logits is not None:
+            _need(logits, (n, N.BRAX_LOGITS), f32, dev, "logits")
+        N.check(N.lib().quad_brax_actor_sample(C.byref(self.arch), _p(self.packed), _p(obs), _p(logits), _p(raw),
+                                               _p(log_prob), _p(actions_env), n, int(seed) & (2**64 - 1),
+                                               int(env_id_base) & (2**64 - 1), int(noise_step) & 0xFFFFFFFF,
+                                               self._stream()), "quad_brax_actor_sample")
+
+    def unroll(self, env, *, num_unrolls: int, unroll_length: int, seed: int = 0, noise_step0: int = 0,
+               ep_ret: torch.Tensor, stats: Optional[torch.Tensor] = None) -> dict:
+        """quad_brax_unroll: num_unrolls x unroll_length steps of BraxPPO._unrolls from the envs' current state in one
+        launch (the env resets itself: auto_reset). ep_ret [N] f32 carries the running episode returns between calls.
+        Returns device tensors with _unrolls' shapes -- obs [U, L, N, 21], nxt [U, N, 21], raw [U, L, N, 4], logp,
+        rew, disc, trunc [U, L, N], views of the launch's time-major buffers -- and finished (episodes) and ret_sum
+        (float64, their returns' sum), reduced from the slots. stats [POLICY_STAT_SLOTS, 2] float64, if given, is
+        accumulated into and not zeroed."""
+        U, L, n, dev, f32 = int(num_unrolls), int(unroll_length), env.num_envs, self.device, torch.float32
+        T = U * L
+        _need(ep_ret, (n,), f32, dev, "ep_ret")
+        if stats is None:
+            stats = torch.zeros(N.POLICY_STAT_SLOTS, 2, dtype=torch.float64, device=dev)
+        else:
+            _need(stats, (N.POLICY_STAT_SLOTS, 2), torch.float64, dev, "stats")
+        before = stats.sum(0)
+        e = lambda *shape: torch.empty(*shape, dtype=f32, device=dev)
+        buf = dict(obs=e(T, n, N.BRAX_OBS), raw=e(T, n, 4), log_prob=e(T, n), reward=e(T, n), discount=e(T, n),
+                   truncation=e(T, n), next_obs=e(U, n, N.BRAX_OBS))
+        u = N.QuadBraxUnroll(**{k: t.data_ptr() for k, t in buf.items()}, ep_ret=ep_ret.data_ptr(),
+                             stats=stats.data_ptr(), steps=T, unroll_length=L,
+                             noise_step0=int(noise_step0) & 0xFFFFFFFF, seed=int(seed) & (2**64 - 1))
+        N.check(N.lib().quad_brax_unroll(env._h, C.byref(self.arch), _p(self.packed), C.byref(u), self._stream()),
+                "quad_brax_unroll")
+        tot = stats.sum(0) - before
+        v = lambda k, *tail: buf[k].view(U, L, n, *tail)
+        return dict(obs=v("obs", N.BRAX_OBS), nxt=buf["next_obs"], raw=v("raw", 4), logp=v("log_prob"),
+                    rew=v("reward"), disc=v("discount"), trunc=v("truncation"), finished=tot[1], ret_sum=tot[0])

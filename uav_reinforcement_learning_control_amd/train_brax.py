@@ -5,7 +5,8 @@
 Same arguments and defaults as train_brax_ppo.py where they apply (the JAX/MJX-specific --xml,
 --impl, --backend and Orbax checkpoints have no counterpart here). --num-evals K runs brax's in-training
 evaluation (K evaluations evenly spaced over the run on a separate eval env, BraxPPO.evaluate: one launch per
-evaluation); its default here is 0, so a run without the flag prints and writes what it always did. Outputs mirror the
+evaluation); its default here is 0, so a run without the flag prints and writes what it always did. --fused-unroll
+collects each training step's unrolls in one launch (ppo/fused.py FusedBraxActor.unroll), off by default. Outputs mirror the
 reference's run directory: <output-dir>/<timestamp>/ppo_params.msgpack (brax model.save_params
 format, ppo/brax_ppo.py + export.save_brax_params), checkpoints/params_step_<n>.msgpack every
 --checkpoint-interval steps, and training_summary.json.
@@ -88,6 +89,10 @@ def parse(argv=None):
                          "default is 10, here 0: no evaluation, the output of a run without the flag is unchanged")
     ap.add_argument("--num-eval-envs", type=int, default=128, help="envs of the separate eval env (brax: 128)")
     ap.add_argument("--deterministic-eval", action="store_true", help="evaluate tanh(loc) instead of samples")
+    ap.add_argument("--fused-unroll", action="store_true",
+                    help="collect each training step's unrolls in one launch (Philox action noise) instead of the\n"
+                         "torch per-step loop; needs a two-hidden-layer policy of the MFMA family. Off by default:\n"
+                         "the output of a run without the flag is unchanged")
     return ap.parse_args(argv)
 
 
@@ -104,7 +109,8 @@ def main(argv=None):
                         batch_size=a.batch_size, num_minibatches=a.num_minibatches,
                         num_updates_per_batch=a.num_updates_per_batch, gae_lambda=a.gae_lambda,
                         reward_scaling=a.reward_scaling, policy_hidden_sizes=_sizes(a.policy_hidden_sizes),
-                        value_hidden_sizes=_sizes(a.value_hidden_sizes), activation=a.activation)
+                        value_hidden_sizes=_sizes(a.value_hidden_sizes), activation=a.activation,
+                        fused_unroll=a.fused_unroll)
     kind = {"hover": "brax_hover", "jax_mjx_quad": "brax_jax_mjx"}[a.env]
     env = QuadVecEnv(a.num_envs, env=kind, device=f"cuda:{local}", seed=a.seed, env_id_base=rank * a.num_envs,
                      max_episode_steps=a.episode_length, cfg_overrides={"traj_duration": a.traj_duration_seconds})
@@ -115,6 +121,9 @@ def main(argv=None):
         model.net.value.load_flax_params(val)
         for k in ("count", "mean", "summed_variance", "std"):
             getattr(model.norm, k).copy_(torch.as_tensor(norm[k]))
+    if a.fused_unroll and rank == 0:
+        print(f"unrolls: one launch per training step ({model.num_unrolls} x {cfg.unroll_length} steps, "
+              f"quad_brax_unroll)", flush=True)
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     run = os.path.abspath(os.path.join(a.output_dir, stamp))
     ckdir = os.path.join(run, "checkpoints")
@@ -166,6 +175,8 @@ def main(argv=None):
                    "final_metrics": {"training/episode_reward": stats.mean_episode_reward if stats else None,
                                      **(stats.losses if stats else {})},
                    "params_path": params_path}
+        if a.fused_unroll:
+            summary["fused_unroll"] = True
         if a.num_evals > 0:
             summary["num_evals"] = a.num_evals
             summary["final_metrics"]["eval/episode_reward"] = eval_reward
