@@ -9,7 +9,7 @@ up, 5 alternating repetitions), at 1,024 and 65,536 envs:
                                It does strictly more per step (both nets, buffer rows, reset draws)
 
 and, at the smaller size, the fused launch in each block shape (QUADENV_EPISODE_BLOCK x QUADENV_ROLLOUT_NT),
-which is what launch_policy_episode's choice rests on. The policy must fly its episodes to the limit (a policy
+which is what episode_block_shape's choice rests on. The policy must fly its episodes to the limit (a policy
 that loses them ends the launch early and measures nothing): pass one with --model, or the tool trains the
 HPO-pin configuration first (tests/hpo_repro.py's, 500k steps). Survival is reported.
 

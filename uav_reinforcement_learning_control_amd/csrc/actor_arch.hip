@@ -10,8 +10,8 @@
 //                                       episode_body<.., NT = 1, EB = 64, ..> (64-env blocks of two one-tile
 //                                       waves), the handle's constant block read from memory (no SPEC form)
 //
-// This file is compiled once without AA_KIND (the C entry points, the pack kernel, k_actor_act, the launch
-// dispatch) and once per (AA_KIND, AA_MB): AA_KIND = 0 hover / 1 trajectory / 2 hover waypoint laps, AA_MB =
+// This file is compiled once without AA_KIND (every quad_actor_* entry point, the pack kernel, k_actor_act, the
+// launch dispatch) and once per (AA_KIND, AA_MB): AA_KIND = 0 hover / 1 trajectory / 2 hover waypoint laps, AA_MB =
 // H2 / 32 = 2 / 4 / 8 -- nine objects of four kernels each that build in parallel.
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,7 @@
 #include "actor_arch.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "policy_episode.h"
 #include "policy_episode_body.h"
 
@@ -137,22 +138,10 @@ __global__ __launch_bounds__(actor::ACT_BLK) void k_actor_act(const float* __res
   });
 }
 
-}  // namespace
-
+// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
 int actor_net_of(const QuadActorArch* a, ActorNet* out) { return actor::net_of(a, "actor arch", false, out); }
 
-hipError_t launch_actor_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, int obs_mode,
-                                const ActorNet& net, const float* packed, const EpisodeArgs& a, hipStream_t s) {
-  return env_kind == QUAD_ENV_TRAJ ? launch_by_mb<1>(kc, kp, ctbr, obs_mode, net, packed, a, nullptr, s)
-                                   : launch_by_mb<0>(kc, kp, ctbr, obs_mode, net, packed, a, nullptr, s);
-}
-
-hipError_t launch_actor_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, int obs_mode,
-                                  const ActorNet& net, const float* packed, const EpisodeArgs& a,
-                                  const QuadWaypointRun& wr, hipStream_t s) {
-  return launch_by_mb<2>(kc, kp, ctbr, obs_mode, net, packed, a, &wr, s);
-}
-
+}  // namespace
 }  // namespace quadenv
 
 using namespace quadenv;
@@ -193,6 +182,33 @@ int quad_actor_act(const QuadActorArch* a, const float* packed, const float* obs
     return hipGetLastError();
   });
   return e == hipSuccess ? QUAD_OK : afail(QUAD_EHIP, "k_actor_act launch failed");
+}
+
+// ---- the episode and the laps: quad_policy_episode's / quad_policy_waypoints' checks and arguments
+int quad_actor_episode(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                       void* stream) {
+  ActorNet net;
+  if (int rc = actor_net_of(arch, &net)) return rc;
+  EpisodeArgs a{};
+  if (int rc = pop::episode_args(h, packed, r, &a, "quad_actor_episode")) return rc;
+  DeviceGuard g(h->device);
+  const bool ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h->cfg.env_kind == QUAD_ENV_TRAJ ? launch_by_mb<1>(h->kdev, h->kp, ctbr, r->obs_mode, net, packed, a, nullptr, s)
+                                           : launch_by_mb<0>(h->kdev, h->kp, ctbr, r->obs_mode, net, packed, a, nullptr, s));
+  return QUAD_OK;
+}
+
+int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
+                         const QuadWaypointRun* wr, void* stream) {
+  ActorNet net;
+  if (int rc = actor_net_of(arch, &net)) return rc;
+  EpisodeArgs a{};
+  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_actor_waypoints")) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_by_mb<2>(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net, packed, a, wr,
+                          static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // brax_actor.hip -- the Brax-profile policy (brax_actor.h: 21 -> H1 -> H2 -> 8, ReLU / tanh / SiLU, the running
 // statistics' normaliser in front) behind quad_brax_actor_pack / quad_brax_actor_act / quad_brax_actor_sample, and the
 // fused episode kernel of the brax env kinds that flies it (quad_brax_episode). The learner's unroll kernel
-// (quad_brax_unroll) is brax_unroll.hip.
+// (quad_brax_unroll: the entry point is here, beside quad_brax_episode) is brax_unroll.hip.
 //
 // Kernels
 //   actor::k_pack<brax::Layout, ..>
@@ -17,7 +17,7 @@
 // built with quadenv.o's floating-point flags (-ffp-contract=on, no SLP vectorizer), so brax_step has k_step_brax's
 // bits.
 //
-// This file is compiled once without BA_KIND (the C entry points, the pack kernel, k_brax_act, the launch dispatch) and
+// This file is compiled once without BA_KIND (every quad_brax_* entry point, the pack kernel, k_brax_act, the launch dispatch) and
 // once per (BA_KIND, BA_MB): BA_KIND = 0 brax hover / 1 brax trajectory, BA_MB = H2 / 32 = 2 / 4 / 8.
 #include <hip/hip_runtime.h>
 
@@ -27,19 +27,10 @@
 #include "brax_actor.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "quad_physics.h"
 
 namespace quadenv {
-
-// one (kind, MB) object's instantiation, defined and explicitly instantiated in that object
-template <int BKIND, int MB>
-hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
-                            const BraxEpisodeArgs& a, hipStream_t s);
-
-// brax_unroll.hip's, one per (kind, MB) object of its own
-template <int BKIND, int MB>
-hipError_t launch_brax_unroll_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
-                                   const BraxUnrollArgs& a, hipStream_t s);
 
 #if defined(BA_KIND)
 namespace {
@@ -235,28 +226,10 @@ hipError_t launch_brax_act(const ActorNet& net, const float* packed, const float
   });
 }
 
-}  // namespace
-
+// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
 int brax_net_of(const QuadBraxActorArch* a, ActorNet* out) { return actor::net_of(a, "brax actor arch", true, out); }
 
-hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
-                               const float* packed, const BraxEpisodeArgs& a, hipStream_t s) {
-  return with_mb(net.mb, [&](auto mb) {
-    constexpr int MB = decltype(mb)::value;
-    return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_inst<1, MB>(kc, kp, net, packed, a, s)
-                                          : launch_brax_inst<0, MB>(kc, kp, net, packed, a, s);
-  });
-}
-
-hipError_t launch_brax_unroll(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
-                              const float* packed, const BraxUnrollArgs& a, hipStream_t s) {
-  return with_mb(net.mb, [&](auto mb) {
-    constexpr int MB = decltype(mb)::value;
-    return env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_unroll_inst<1, MB>(kc, kp, net, packed, a, s)
-                                          : launch_brax_unroll_inst<0, MB>(kc, kp, net, packed, a, s);
-  });
-}
-
+}  // namespace
 }  // namespace quadenv
 
 using namespace quadenv;
@@ -313,6 +286,74 @@ int quad_brax_actor_sample(const QuadBraxActorArch* a, const float* packed, cons
   const hipError_t e = launch_brax_act<true>(net, packed, obs, logits, raw, log_prob, actions_env, n, 0, seed,
                                             env_id_base, noise_step, stream);
   return e == hipSuccess ? QUAD_OK : bfail(QUAD_EHIP, "k_brax_act launch failed");
+}
+
+// ---- whole episodes on the brax kinds (k_brax_episode)
+int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
+                      void* stream) {
+  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_episode: ") + m); };
+  ActorNet net;
+  if (int rc = brax_net_of(arch, &net)) return rc;
+  if (!h || !packed || !r) return bad("handle/packed/run is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
+    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
+  if (r->max_steps < 1) return bad("max_steps must be >= 1");
+  const QuadBraxMetrics& m = r->metrics;
+  if (!m.ret || !m.steps || !m.err_sum || !m.err_sq_sum || !m.err_count || !m.status)
+    return bad("every metrics array is required");
+  if (r->trace_envs < 0 || r->trace_envs > h->n) return bad("trace_envs must be in [0, N]");
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
+  const bool any_trace = r->trace_actions || r->trace_obs || r->trace_pos || r->trace_target;
+  if (any_trace && r->trace_envs > 0) {
+    if (int64_t(r->max_steps) * r->trace_envs * 84 > int64_t(UINT32_MAX))
+      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if (reinterpret_cast<uintptr_t>(r->trace_actions) & 15u) return bad("the action trace must be 16-byte aligned");
+  }
+  const BraxEpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0, r->deterministic, r->noise_step0, r->seed,
+                          r->metrics, r->trace_actions, r->trace_obs, r->trace_pos, r->trace_target};
+  DeviceGuard g(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_inst<1, MB>(h->kdev, h->kp, net, packed, a, s)
+                                                 : launch_brax_inst<0, MB>(h->kdev, h->kp, net, packed, a, s);
+  }));
+  return QUAD_OK;
+}
+
+// ---- the Brax learner's unrolls on the brax kinds (k_brax_unroll, brax_unroll.hip)
+int quad_brax_unroll(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxUnroll* u,
+                     void* stream) {
+  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_unroll: ") + m); };
+  ActorNet net;
+  if (int rc = brax_net_of(arch, &net)) return rc;
+  if (!h || !packed || !u) return bad("handle/packed/unroll is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
+    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
+  if (!h->cfg.auto_reset) return bad("the handle must have auto_reset = 1");
+  if (u->steps < 1 || u->unroll_length < 1) return bad("steps and unroll_length must be >= 1");
+  if (u->steps % u->unroll_length) return bad("steps must be a multiple of unroll_length");
+  if (!u->obs || !u->raw || !u->log_prob || !u->reward || !u->discount || !u->truncation || !u->next_obs ||
+      !u->ep_ret || !u->stats)
+    return bad("every buffer is required");
+  const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if ((at(packed) | at(u->raw)) & 15u) return bad("packed and raw must be 16-byte aligned");
+  if ((at(u->obs) | at(u->log_prob) | at(u->reward) | at(u->discount) | at(u->truncation) | at(u->next_obs) |
+       at(u->ep_ret)) & 3u)
+    return bad("the float buffers must be 4-byte aligned");
+  if (at(u->stats) & 7u) return bad("stats must be 8-byte aligned");
+  if (int64_t(u->steps) * h->n * 84 > int64_t(UINT32_MAX))
+    return bad("steps * N too large (rows use 32-bit byte offsets)");
+  const BraxUnrollArgs a{u->obs, u->raw, u->log_prob, u->reward, u->discount, u->truncation, u->next_obs, u->ep_ret,
+                         u->stats, u->steps, u->unroll_length, u->noise_step0, u->seed};
+  DeviceGuard g(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return h->cfg.env_kind == QUAD_ENV_BRAX_TRAJ ? launch_brax_unroll_inst<1, MB>(h->kdev, h->kp, net, packed, a, s)
+                                                 : launch_brax_unroll_inst<0, MB>(h->kdev, h->kp, net, packed, a, s);
+  }));
+  return QUAD_OK;
 }
 
 }  // extern "C"

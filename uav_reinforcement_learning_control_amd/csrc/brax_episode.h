@@ -1,5 +1,5 @@
-// brax_episode.h -- host-side entries of the Brax-profile policy's launches (brax_actor.hip), called by
-// quad_brax_episode and quad_brax_unroll (quadenv.hip).
+// brax_episode.h -- the flattened arguments of the Brax-profile policy's fused launches and the launchers their
+// per-(kind, MB) objects export to quad_brax_episode / quad_brax_unroll (brax_actor.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,8 +11,6 @@
 
 namespace quadenv {
 
-// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
-int brax_net_of(const QuadBraxActorArch* a, ActorNet* out);
 struct BraxEpisodeArgs {  // QuadBraxRun, flattened (trace_envs 0 when no trace is requested)
   int32_t max_steps, trace_envs, deterministic;
   uint32_t noise_step0;
@@ -20,10 +18,6 @@ struct BraxEpisodeArgs {  // QuadBraxRun, flattened (trace_envs 0 when no trace 
   QuadBraxMetrics metrics;
   float *trace_actions, *trace_obs, *trace_pos, *trace_target;
 };
-// k_brax_episode<env_kind, mb> over all envs of kp, 64-env blocks of two one-tile waves
-hipError_t launch_brax_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
-                               const float* packed, const BraxEpisodeArgs& a, hipStream_t s);
-
 struct BraxUnrollArgs {  // QuadBraxUnroll, flattened
   float *obs, *raw, *log_prob, *reward, *discount, *truncation, *next_obs, *ep_ret;
   double* stats;
@@ -31,8 +25,14 @@ struct BraxUnrollArgs {  // QuadBraxUnroll, flattened
   uint32_t noise_step0;
   uint64_t seed;
 };
-// k_brax_unroll<env_kind, mb> (brax_unroll.hip) over all envs of kp, the episode kernel's block shape
-hipError_t launch_brax_unroll(const KConsts<float>* kc, const KParams& kp, int env_kind, const ActorNet& net,
-                              const float* packed, const BraxUnrollArgs& a, hipStream_t s);
+
+// one (kind, MB) object's instantiation, defined and explicitly instantiated in that object: k_brax_episode
+// (brax_actor.hip) and k_brax_unroll (brax_unroll.hip) over all envs of kp, 64-env blocks of two one-tile waves
+template <int BKIND, int MB>
+hipError_t launch_brax_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
+                            const BraxEpisodeArgs& a, hipStream_t s);
+template <int BKIND, int MB>
+hipError_t launch_brax_unroll_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
+                                   const BraxUnrollArgs& a, hipStream_t s);
 
 }  // namespace quadenv

@@ -14,7 +14,7 @@
 // vectorizer), so brax_step and the reset have k_step_brax's bits.
 //
 // Compiled once per (BU_KIND, BU_MB): BU_KIND = 0 brax hover / 1 brax trajectory, BU_MB = H2 / 32 = 2 / 4 / 8. The
-// launch dispatch over the six objects is brax_actor.hip's (launch_brax_unroll).
+// launch dispatch over the six objects is quad_brax_unroll's (brax_actor.hip).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -29,10 +29,6 @@
 #endif
 
 namespace quadenv {
-
-template <int BKIND, int MB>
-hipError_t launch_brax_unroll_inst(const KConsts<float>* kc, const KParams& kp, const ActorNet& net, const float* packed,
-                                   const BraxUnrollArgs& a, hipStream_t s);
 
 namespace {
 

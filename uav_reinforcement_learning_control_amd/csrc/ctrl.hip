@@ -1,5 +1,5 @@
-// ctrl.hip -- the controller kernels on gfx950: the cascaded PID baseline (quad_pid_*) and the controller
-// family (quad_ctrl_*) are one kernel family (the laws: quad_pid.h, quad_ctrl.h).
+// ctrl.hip -- the controller kernels on gfx950 and their C entry points: the cascaded PID baseline (quad_pid_*)
+// and the controller family (quad_ctrl_*) are one kernel family (the laws: quad_pid.h, quad_ctrl.h); quad_target_info.
 //
 // Kernels
 //   k_ctrl_act<ROW, LAW>                 the law alone over [n,12] states and [n,9] targets, caller-owned state block
@@ -27,9 +27,9 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/quadenv.h"
-#include "ctrl.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "kconsts_default.h"
 #include "quad_ctrl.h"
 #include "quad_physics.h"
@@ -292,50 +292,118 @@ hipError_t launch_episode(const KConsts<float>* kc, const KParams& kp, int env_k
 
 }  // namespace
 
-namespace quadenv {
+constexpr LawIds PID_MODES{QUAD_PID_YAW_FRAME, QUAD_PID_WORLD_FRAME, "mode", "gains"};
+constexpr LawIds CTRL_LAWS{QUAD_CTRL_PID_YAW, QUAD_CTRL_LQR, "law", "params"};
 
-hipError_t launch_pid_act(const PidPlant& plant, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of,
-                          int32_t mode, const float* state12, const float* target9, int32_t n, double* integ,
-                          float* actions, double* diag, hipStream_t s) {
-  return launch_act(plant, gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag, s);
+extern "C" {
+
+// ---- cascaded PID baseline (QuadPidGains rows)
+int quad_pid_default_gains(QuadPidGains* g) {
+  if (!g) return fail(QUAD_EINVAL, "gains is NULL");
+  pid_default_gains_fill(g);
+  return QUAD_OK;
 }
 
-hipError_t launch_ctrl_act(const PidPlant& plant, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of,
-                           int32_t law, const float* state12, const float* target9, int32_t n, double* state,
-                           float* actions, double* diag, hipStream_t s) {
-  return launch_act(plant, params, n_sets, set_of, law, state12, target9, n, state, actions, diag, s);
+int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of, int32_t mode,
+                 const float* state12, const float* target9, int32_t n, double* integ, float* actions,
+                 double* diag, void* stream) {
+  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
+  if (int rc = check_law_table(h, "quad_pid_act", PID_MODES, mode, n_sets, gains)) return rc;
+  if (int rc = check_act_rows("quad_pid_act", state12, target9, integ, "integ", actions, n)) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_act(make_pid_plant(h->cfg), gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag,
+                     static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
 }
 
-hipError_t launch_pid_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec,
-                              const PidPlant& plant, const QuadPidRun& r, hipStream_t s) {
-  return launch_episode(kc, kp, env_kind, spec, plant, run_of(r), s);
+// ---- controller family (QuadCtrlParams rows); quad_pid_*'s rules with a law id in place of the mode
+int quad_ctrl_default_params(QuadCtrlParams* p) {
+  if (!p) return fail(QUAD_EINVAL, "params is NULL");
+  ctrl_default_params_fill(p);
+  return QUAD_OK;
 }
 
-hipError_t launch_ctrl_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool spec,
-                               const PidPlant& plant, const QuadCtrlRun& r, hipStream_t s) {
-  return launch_episode(kc, kp, env_kind, spec, plant, run_of(r), s);
+int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of, int32_t law,
+                  const float* state12, const float* target9, int32_t n, double* state, float* actions,
+                  double* diag, void* stream) {
+  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
+  if (int rc = check_law_table(h, "quad_ctrl_act", CTRL_LAWS, law, n_sets, params)) return rc;
+  if (int rc = check_act_rows("quad_ctrl_act", state12, target9, state, "state", actions, n)) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_act(make_pid_plant(h->cfg), params, n_sets, set_of, law, state12, target9, n, state, actions, diag,
+                     static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
 }
 
-hipError_t launch_ctrl_waypoints(const KConsts<float>* kc, const KParams& kp, bool spec, const PidPlant& plant,
-                                 const QuadCtrlRun& r, const QuadWaypointRun& wr, hipStream_t s) {
-  const dim3 grid((kp.n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
-  with_law<QuadCtrlParams>(r.law, [&](auto lw) {
-    with_bool(spec, [&](auto sp) {
-      hipLaunchKernelGGL((k_ctrl_waypoints<decltype(lw)::value, decltype(sp)::value>), grid, blk, 0, s, kc, kp, plant,
-                         run_of(r), wr);
+// ---- the fused episodes of both row types (k_ctrl_episode)
+int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream) {
+  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
+  if (int rc = check_law_table(h, "quad_pid_episode", PID_MODES, r->mode, r->n_sets, r->gains)) return rc;
+  const bool any_trace = r->trace_actions || r->trace_state12;
+  if (int rc = check_run("quad_pid_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
+  DeviceGuard g(h->device);
+  QuadPidRun run = *r;
+  if (!any_trace) run.trace_envs = 0;
+  HIP_TRY(launch_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run_of(run),
+                         static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream) {
+  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
+  if (int rc = check_law_table(h, "quad_ctrl_episode", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
+  const bool any_trace = r->trace_actions || r->trace_state12;
+  if (int rc = check_run("quad_ctrl_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
+  DeviceGuard g(h->device);
+  QuadCtrlRun run = *r;
+  if (!any_trace) run.trace_envs = 0;
+  HIP_TRY(launch_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run_of(run),
+                         static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+// ---- waypoint laps in one launch (k_ctrl_waypoints)
+int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointRun* wr, void* stream) {
+  if (!h || !r || !wr) return fail(QUAD_EINVAL, "handle/run/waypoints is NULL");
+  if (int rc = check_waypoint_run(h, "quad_ctrl_waypoints", wr)) return rc;
+  if (int rc = check_law_table(h, "quad_ctrl_waypoints", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
+  const bool any_trace = r->trace_actions || r->trace_state12 || wr->trace_reward || wr->trace_wp_idx;
+  if (int rc = check_run("quad_ctrl_waypoints", h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
+                         any_trace, "traces"))
+    return rc;
+  DeviceGuard g(h->device);
+  Run<QuadCtrlParams> run = run_of(*r);
+  if (!any_trace) run.trace_envs = 0;
+  const dim3 grid((h->n + EP_BLOCK - 1) / EP_BLOCK), blk(EP_BLOCK);
+  with_law<QuadCtrlParams>(run.law, [&](auto lw) {
+    with_bool(h->spec, [&](auto sp) {
+      hipLaunchKernelGGL((k_ctrl_waypoints<decltype(lw)::value, decltype(sp)::value>), grid, blk, 0,
+                         static_cast<hipStream_t>(stream), h->kdev, h->kp, make_pid_plant(h->cfg), run, *wr);
     });
   });
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return QUAD_OK;
 }
 
-hipError_t launch_target_info(const KConsts<float>* kc, const KParams& kp, int env_kind, float* target_info,
-                              hipStream_t s) {
-  const dim3 grid((kp.n + ACT_BLOCK - 1) / ACT_BLOCK), blk(ACT_BLOCK);
-  with_bool(env_kind == QUAD_ENV_TRAJ, [&](auto tr) {
+int quad_target_info(QuadHandle* h, float* target_info, void* stream) {
+  if (!h || !target_info) return fail(QUAD_EINVAL, "handle/target_info is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_target_info: env_kind must be HOVER or TRAJ");
+  DeviceGuard g(h->device);
+  const dim3 grid((h->n + ACT_BLOCK - 1) / ACT_BLOCK), blk(ACT_BLOCK);
+  with_bool(h->cfg.env_kind == QUAD_ENV_TRAJ, [&](auto tr) {
     constexpr int KIND = decltype(tr)::value ? QUAD_ENV_TRAJ : QUAD_ENV_HOVER;
-    hipLaunchKernelGGL(k_target_info<KIND>, grid, blk, 0, s, kc, kp, target_info);
+    hipLaunchKernelGGL(k_target_info<KIND>, grid, blk, 0, static_cast<hipStream_t>(stream), h->kdev, h->kp, target_info);
   });
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return QUAD_OK;
 }
 
-}  // namespace quadenv
+}  // extern "C"

@@ -312,17 +312,5 @@ __device__ __forceinline__ void store_row_sums(float* P, const float (&v)[NOUT +
   for (int k = 0; k < 3; k++) P[P_STATS + k] = v[NOUT + ACT + k];
 }
 
-// Host: opt kernels k0 and k1 into `bytes` of dynamic LDS on the current device, once per device
-// (`once`: the current device's entry of the call site's table). False: hipFuncSetAttribute failed.
-template <class K0, class K1>
-bool opt_in_dynamic_lds(bool& once, K0* k0, K1* k1, int bytes) {
-  constexpr hipFuncAttribute attr = hipFuncAttributeMaxDynamicSharedMemorySize;
-  if (once) return true;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k0), attr, bytes) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(k1), attr, bytes) != hipSuccess)
-    return false;
-  return once = true;
-}
-
 }  // namespace lrn
 }  // namespace quadenv

@@ -34,6 +34,7 @@
 #include <cstring>
 
 #include "../../include/quadenv.h"
+#include "dispatch.h"
 #include "learner.h"
 #include "policy_net.h"
 #include "population.h"
@@ -644,12 +645,7 @@ int ppo_grad_impl(const QuadPolicyParams* p, const QuadPPOBatch* b, const QuadPo
   if (dump && int64_t(b->batch) * 2 * 256 * 4 > (int64_t(1) << 40)) return lfail(QUAD_EINVAL, "batch too large to dump");
   if (workspace_bytes < l.adv_bytes + l.part_bytes + (x3 ? l.wimg_bytes : 0))
     return lfail(QUAD_EINVAL, "workspace too small");
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return lfail(QUAD_EHIP, "hipGetDevice failed");
   const int lds_bytes = L_TOTAL * int(sizeof(float));
-  if (!x3 && !opt_in_dynamic_lds(opted[dev], &k_ppo_grad, &k_ppo_grad_dump, lds_bytes))
-    return lfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   hipStream_t s = static_cast<hipStream_t>(stream);
   double* adv_part = static_cast<double*>(workspace);
   float* part = reinterpret_cast<float*>(static_cast<char*>(workspace) + l.adv_bytes);
@@ -680,11 +676,10 @@ int ppo_grad_impl(const QuadPolicyParams* p, const QuadPPOBatch* b, const QuadPo
     if (int rc = dump ? launch_ppo_grad_x3_dump(g, s, st, b->advantages) : launch_ppo_grad_x3(g, s, st, b->advantages))
       return rc;
   } else if (dump) {
-    hipLaunchKernelGGL(k_ppo_grad_dump, dim3(l.nb + l.nbc), dim3(LB), lds_bytes, s, g);
-    if (hipGetLastError() != hipSuccess) return lfail(QUAD_EHIP, "k_ppo_grad_dump launch failed");
-  } else {
-    hipLaunchKernelGGL(k_ppo_grad, dim3(l.nb + l.nbc), dim3(LB), lds_bytes, s, g);
-    if (hipGetLastError() != hipSuccess) return lfail(QUAD_EHIP, "k_ppo_grad launch failed");
+    if (launch_lds<&k_ppo_grad_dump>(dim3(l.nb + l.nbc), dim3(LB), lds_bytes, s, g) != hipSuccess)
+      return lfail(QUAD_EHIP, "k_ppo_grad_dump launch failed");
+  } else if (launch_lds<&k_ppo_grad>(dim3(l.nb + l.nbc), dim3(LB), lds_bytes, s, g) != hipSuccess) {
+    return lfail(QUAD_EHIP, "k_ppo_grad launch failed");
   }
   RArgs r{};
   r.gr = *gr; r.part = part; r.log_std = p->log_std; r.stats = b->stats; r.nb = l.nb; r.nbc = l.nbc;

@@ -33,6 +33,7 @@
 #include <cstdlib>
 
 #include "../../include/quadenv.h"
+#include "dispatch.h"
 #include "learner.h"
 #include "learner_x3_common.h"
 #include "population.h"
@@ -678,19 +679,17 @@ int launch_prep(const GArgs& g, hipStream_t s, double* adv_stats, const float* a
 }
 
 int launch_ppo_grad_x3(const GArgs& g, hipStream_t s, double* adv_stats, const float* adv) {
-  static bool opted[64] = {}, opted_net[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(QUAD_EHIP, "hipGetDevice failed");
-  if (!opt_in_dynamic_lds(opted[dev], &k_ppo_grad_x3, &k_ppo_grad_x3_sep, B_TOTAL))
-    return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   if (int rc = launch_prep(g, s, adv_stats, adv)) return rc;
   const char* sp = std::getenv("QUADENV_LEARNER_SPLIT");
   if (sp && std::atoi(sp) != 0) {
     static hipStream_t s2[64] = {};
     static hipEvent_t ev[64][2] = {};
     static bool ready[64] = {};
+    int dev = 0;  // the second stream and the events are kept per device
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(QUAD_EHIP, "hipGetDevice failed");
     if (!ready[dev]) {
-      if (!opt_in_dynamic_lds(opted_net[dev], &k_ppo_grad_x3_net<ACT>, &k_ppo_grad_x3_net<1>, B_TOTAL) ||
+      if (lds_opt_in<&k_ppo_grad_x3_net<ACT>>(B_TOTAL) != hipSuccess ||
+          lds_opt_in<&k_ppo_grad_x3_net<1>>(B_TOTAL) != hipSuccess ||
           hipStreamCreateWithFlags(&s2[dev], hipStreamNonBlocking) != hipSuccess ||
           hipEventCreateWithFlags(&ev[dev][0], hipEventDisableTiming) != hipSuccess ||
           hipEventCreateWithFlags(&ev[dev][1], hipEventDisableTiming) != hipSuccess)
@@ -709,38 +708,24 @@ int launch_ppo_grad_x3(const GArgs& g, hipStream_t s, double* adv_stats, const f
       return set_error(QUAD_EHIP, "learner split: join failed");
     return QUAD_OK;
   }
-  if (2 * g.nb <= X3_BLOCKS && g.nbc == g.nb)
-    hipLaunchKernelGGL(k_ppo_grad_x3_sep, dim3(2 * g.nb), dim3(LB), B_TOTAL, s, g);
-  else
-    hipLaunchKernelGGL(k_ppo_grad_x3, dim3(g.nb), dim3(LB), B_TOTAL, s, g);
-  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_ppo_grad_x3 launch failed");
-  return QUAD_OK;
+  const hipError_t e = 2 * g.nb <= X3_BLOCKS && g.nbc == g.nb
+                           ? launch_lds<&k_ppo_grad_x3_sep>(dim3(2 * g.nb), dim3(LB), B_TOTAL, s, g)
+                           : launch_lds<&k_ppo_grad_x3>(dim3(g.nb), dim3(LB), B_TOTAL, s, g);
+  return e == hipSuccess ? QUAD_OK : set_error(QUAD_EHIP, "k_ppo_grad_x3 launch failed");
 }
 
 int launch_pop_grad_x3(const GArgs* tab, const int32_t* active, int count, int slot, int nb, hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return set_error(QUAD_EHIP, "hipGetDevice failed");
-  if (!opted[dev]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_ppo_grad_x3_sep),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, B_TOTAL) != hipSuccess)
-      return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    opted[dev] = true;
-  }
   hipLaunchKernelGGL(k_pop_x3_prep, dim3(SPLIT_BLOCKS, count), dim3(256), 0, s, tab, active);
   if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_x3_prep launch failed");
-  hipLaunchKernelGGL(k_pop_ppo_grad_x3_sep, dim3(2 * nb, count), dim3(LB), B_TOTAL, s, tab, active, slot);
-  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_ppo_grad_x3_sep launch failed");
+  if (launch_lds<&k_pop_ppo_grad_x3_sep>(dim3(2 * nb, count), dim3(LB), B_TOTAL, s, tab, active, slot) != hipSuccess)
+    return set_error(QUAD_EHIP, "k_pop_ppo_grad_x3_sep launch failed");
   return QUAD_OK;
 }
 
 int launch_ppo_grad_x3_dump(const GArgs& g, hipStream_t s, double* adv_stats, const float* adv) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_ppo_grad_x3_dump), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          B_TOTAL) != hipSuccess)
-    return set_error(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   if (int rc = launch_prep(g, s, adv_stats, adv)) return rc;
-  hipLaunchKernelGGL(k_ppo_grad_x3_dump, dim3(g.nb), dim3(LB), B_TOTAL, s, g);
-  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_ppo_grad_x3_dump launch failed");
+  if (launch_lds<&k_ppo_grad_x3_dump>(dim3(g.nb), dim3(LB), B_TOTAL, s, g) != hipSuccess)
+    return set_error(QUAD_EHIP, "k_ppo_grad_x3_dump launch failed");
   return QUAD_OK;
 }
 

@@ -21,6 +21,7 @@
 #include <cstdint>
 
 #include "../../include/quadenv.h"
+#include "dispatch.h"
 #include "quad_physics.h"
 #include "policy_net.h"
 #include "population.h"
@@ -371,23 +372,13 @@ __global__ __launch_bounds__(PBLOCK) void k_rollout_post(const float* __restrict
 
 int pfail(int code, const char* m) { return set_error(code, m); }
 
-// the kernels take 152 KB of dynamic LDS (gfx950 has 160 KB per CU): opt in once per device
-int lds_opt_in() {
-  static bool done[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return pfail(QUAD_EHIP, "hipGetDevice failed");
-  if (done[dev]) return QUAD_OK;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_act<2, 256>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_policy_value<2, 256>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess ||
-      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rollout_post),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess)
-    return pfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-  done[dev] = true;
-  return QUAD_OK;
+// the kernels take 152 KB of dynamic LDS (gfx950 has 160 KB per CU): every entry point opts all three in, once per
+// device (dispatch.h), so packing an image is enough for the launches captured into a graph later
+int opt_in() {
+  return lds_opt_in<&k_policy_act<2, 256>, &k_pop_policy_value<2, 256>, &k_rollout_post>(LDS_F * int(sizeof(float))) ==
+                 hipSuccess
+             ? QUAD_OK
+             : pfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
 }
 
 int grid_for(int n, int nt, int waves) {
@@ -425,7 +416,7 @@ int quadenv::pop::launch_pop_pack(const PackEntry* tab, const int32_t* active, i
 }
 
 int quadenv::pop::launch_pop_value(const ValueEntry* tab, const int32_t* active, int count, int n, hipStream_t s) {
-  if (int rc = lds_opt_in()) return rc;
+  if (int rc = opt_in()) return rc;
   hipLaunchKernelGGL((k_pop_policy_value<2, 256>), dim3(grid_for(n, 2, 4), count), dim3(256), LDS_F * sizeof(float),
                      s, tab, active, n);
   return hipGetLastError() == hipSuccess ? QUAD_OK : pfail(QUAD_EHIP, "k_pop_policy_value launch failed");
@@ -441,7 +432,7 @@ int quad_policy_pack(const QuadPolicyParams* p, float* packed, void* stream) {
       !p->vf_b0 || !p->vf_w1 || !p->vf_b1 || !p->val_w || !p->val_b || !p->log_std)
     return pfail(QUAD_EINVAL, "a policy parameter pointer is NULL");
   if (reinterpret_cast<uintptr_t>(packed) & 15u) return pfail(QUAD_EINVAL, "packed must be 16-byte aligned");
-  if (int rc = lds_opt_in()) return rc;
+  if (int rc = opt_in()) return rc;
   NetPtrs actor{p->pi_w0, p->pi_b0, p->pi_w1, p->pi_b1, p->act_w, p->act_b};
   NetPtrs critic{p->vf_w0, p->vf_b0, p->vf_w1, p->vf_b1, p->val_w, p->val_b};
   hipLaunchKernelGGL(k_policy_pack, dim3((PACKED_F + 2 * 32 * 64 + 2 * 4 * 64 + 255) / 256), dim3(256), 0,
@@ -463,7 +454,7 @@ int quad_policy_act(const float* packed, const QuadPolicyAct* s, int32_t n, void
     if (s->epilogue->rows != s->rows) return pfail(QUAD_EINVAL, "epilogue rows != rows");
     e = epi_args(s->epilogue);
   }
-  if (int rc = lds_opt_in()) return rc;
+  if (int rc = opt_in()) return rc;
   ActArgs a{s->obs, s->actions_env, s->actions, s->log_prob, s->value, s->obs_copy, s->last_start,
             s->episode_starts, s->cursor, s->rows, s->deterministic, s->seed, s->env_id_base, n,
             s->epilogue ? 1 : 0};
@@ -480,7 +471,7 @@ int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* c
   if (n <= 0) return pfail(QUAD_EINVAL, "n must be > 0");
   if (reinterpret_cast<uintptr_t>(packed) & 15u) return pfail(QUAD_EINVAL, "packed must be 16-byte aligned");
   if (int rc = check_epi(p)) return rc;
-  if (int rc = lds_opt_in()) return rc;
+  if (int rc = opt_in()) return rc;
   hipLaunchKernelGGL(k_rollout_post, dim3(grid_for(n, 1, 4)), dim3(PBLOCK), LDS_F * sizeof(float),
                      static_cast<hipStream_t>(stream), packed, epi_args(p), cursor, n);
   return hipGetLastError() == hipSuccess ? QUAD_OK : pfail(QUAD_EHIP, "k_rollout_post launch failed");

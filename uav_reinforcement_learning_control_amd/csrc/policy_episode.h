@@ -1,5 +1,5 @@
-// policy_episode.h -- host-side entries of the deployed-observation law and the fused policy episode
-// (policy_episode.hip), called by quad_deploy_obs and quad_policy_episode.
+// policy_episode.h -- the fused policy episode's arguments (policy_episode.hip) and what crosses between its
+// three objects, to the general actor's entry points (actor_arch.hip) and to the population (population.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -25,14 +25,6 @@ struct EpisodeArgs {  // QuadPolicyRun, flattened
   double* vel_err_sq;
 };
 
-// k_deploy_obs over n rows (the observation bounds are the handle's constant block kc)
-hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const float* state12, const float* target3,
-                             double timestamp, int32_t n, float* obs, float* vel_est, hipStream_t s);
-
-// k_policy_episode<env_kind, ctbr, ., spec, obs_mode> over all envs of kp; the block shape is chosen here
-hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
-                                 int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s);
-
 // The population form (population.h, quad_pop_episode): k_policy_episode's arguments per member, env-observation
 // mode; block (b, k) is block b of member active[k]'s episodes. kc: the constant block every member shares.
 struct PopEpisodeEntry {
@@ -51,17 +43,9 @@ hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, 
                                    const float* packed, const EpisodeArgs& a, const QuadWaypointRun& wr,
                                    hipStream_t s);
 
-// ---- the general actor's forms (actor_arch.hip; quad_actor_episode / quad_actor_waypoints): the same closed loop
-// with actor_arch.h's forward, in 64-env blocks of two one-tile waves, the constant block read from memory
-struct ActorNet {  // a checked QuadActorArch or QuadBraxActorArch: H1 / 32, H2 / 32 (2, 4 or 8), QUAD_ACTFN_*
+// a checked QuadActorArch or QuadBraxActorArch (actor_core.h net_of): H1 / 32, H2 / 32 (2, 4 or 8), QUAD_ACTFN_*
+struct ActorNet {
   int nb1, mb, actfn;
 };
-// QUAD_OK and *out, or QUAD_EINVAL with a message for an arch outside the family
-int actor_net_of(const QuadActorArch* a, ActorNet* out);
-hipError_t launch_actor_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, int obs_mode,
-                                const ActorNet& net, const float* packed, const EpisodeArgs& a, hipStream_t s);
-hipError_t launch_actor_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, int obs_mode,
-                                  const ActorNet& net, const float* packed, const EpisodeArgs& a,
-                                  const QuadWaypointRun& wr, hipStream_t s);
 
 }  // namespace quadenv

@@ -31,15 +31,18 @@
 //
 // This file is compiled once per env kind (-DPE_KIND=0 hover / 1 trajectory) and once more for the hover
 // kind's waypoint instantiations (-DPE_KIND=2): the three objects build in parallel, each with its own
-// instantiations.
+// instantiations. The hover object (PE_KIND=0) also holds the family's host code: the block-shape rule, the
+// argument checks and the C entry points quad_deploy_obs, quad_policy_episode and quad_policy_waypoints.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
+#include <string>
 
 #include "../../include/quadenv.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "kconsts_default.h"
 #include "policy_episode.h"
 #include "policy_episode_body.h"
@@ -156,19 +159,8 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_pop_policy_episode(const KConst
 template <int KIND, bool CTBR, int NT, bool SPEC, int EB>
 hipError_t launch_pop(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count, int n,
                       hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (!opted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_policy_episode<KIND, CTBR, NT, SPEC, EB>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
-  hipLaunchKernelGGL((k_pop_policy_episode<KIND, CTBR, NT, SPEC, EB>), dim3((n + EB - 1) / EB, count),
-                     dim3(EB * 2 / NT), bytes, s, kc, tab, active);
-  return hipGetLastError();
+  return launch_lds<&k_pop_policy_episode<KIND, CTBR, NT, SPEC, EB>>(dim3((n + EB - 1) / EB, count), dim3(EB * 2 / NT),
+                                                                     LDS_F * int(sizeof(float)), s, kc, tab, active);
 }
 #endif
 
@@ -192,38 +184,15 @@ __global__ __launch_bounds__(EB * 2 / NT) void k_policy_waypoints(const KConsts<
 template <bool CTBR, int NT, bool SPEC, int MODE, int EB>
 hipError_t launch_wp(const KConsts<float>* kc, const KParams& kp, const float* packed, const EpisodeArgs& a,
                      const QuadWaypointRun& wr, hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (!opted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_policy_waypoints<CTBR, NT, SPEC, MODE, EB>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
-  hipLaunchKernelGGL((k_policy_waypoints<CTBR, NT, SPEC, MODE, EB>), dim3((kp.n + EB - 1) / EB), dim3(EB * 2 / NT),
-                     bytes, s, kc, kp, packed, a, wr);
-  return hipGetLastError();
+  return launch_lds<&k_policy_waypoints<CTBR, NT, SPEC, MODE, EB>>(dim3((kp.n + EB - 1) / EB), dim3(EB * 2 / NT),
+                                                                   LDS_F * int(sizeof(float)), s, kc, kp, packed, a, wr);
 }
 #else
 template <int KIND, bool CTBR, int NT, bool SPEC, int MODE, int EB>
 hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* packed, const EpisodeArgs& a,
                   hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (!opted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&k_policy_episode<KIND, CTBR, NT, SPEC, MODE, EB>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
-  hipLaunchKernelGGL((k_policy_episode<KIND, CTBR, NT, SPEC, MODE, EB>), dim3((kp.n + EB - 1) / EB),
-                     dim3(EB * 2 / NT), bytes, s, kc, kp, packed, a);
-  return hipGetLastError();
+  return launch_lds<&k_policy_episode<KIND, CTBR, NT, SPEC, MODE, EB>>(dim3((kp.n + EB - 1) / EB), dim3(EB * 2 / NT),
+                                                                       LDS_F * int(sizeof(float)), s, kc, kp, packed, a);
 }
 #endif
 
@@ -262,7 +231,7 @@ __global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float
 }  // namespace
 
 #if PE_WP
-// quad_policy_waypoints' launch: launch_policy_episode's block-shape rule (below, in the hover object)
+// quad_policy_waypoints' launch: quad_policy_episode's block-shape rule (below, in the hover object)
 hipError_t launch_policy_waypoints(const KConsts<float>* kc, const KParams& kp, bool ctbr, bool spec, int obs_mode,
                                    const float* packed, const EpisodeArgs& a, const QuadWaypointRun& wr,
                                    hipStream_t s) {
@@ -318,13 +287,6 @@ hipError_t launch_pop_episode_kind<PE_KIND>(const KConsts<float>* kc, const PopE
 #endif
 
 #if PE_KIND == 0
-hipError_t launch_deploy_obs(const KConsts<float>* kc, const EstArgs& est, const float* state12, const float* target3,
-                             double timestamp, int32_t n, float* obs, float* vel_est, hipStream_t s) {
-  hipLaunchKernelGGL(k_deploy_obs, dim3((n + DEPLOY_BLOCK - 1) / DEPLOY_BLOCK), dim3(DEPLOY_BLOCK), 0, s, kc, est,
-                     state12, target3, timestamp, n, obs, vel_est);
-  return hipGetLastError();
-}
-
 // The block shape: an evaluation batch (5 .. ~1,000 envs) in 64-env blocks of two one-tile waves (NT = 1),
 // so it spreads over 4x the CUs of k_rollout's shape and each wave's MFMA chain is one tile long; from
 // EPISODE_WIDE_N envs k_rollout's 256-env blocks of two-tile waves (the measurements: DESIGN 16). Every form
@@ -338,14 +300,6 @@ void episode_block_shape(int32_t n, int& nt, int& eb) {
   const char* b = std::getenv("QUADENV_EPISODE_BLOCK");
   eb = b && std::atoi(b) == 64 ? 64 : (b && std::atoi(b) == 256 ? 256 : (wide ? 256 : 64));
 }
-hipError_t launch_policy_episode(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
-                                 int obs_mode, const float* packed, const EpisodeArgs& a, hipStream_t s) {
-  int nt, eb;
-  episode_block_shape(kp.n, nt, eb);
-  return env_kind == QUAD_ENV_TRAJ
-             ? launch_episode_kind<QUAD_ENV_TRAJ>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s)
-             : launch_episode_kind<QUAD_ENV_HOVER>(kc, kp, ctbr, spec, obs_mode, nt, eb, packed, a, s);
-}
 hipError_t launch_pop_policy_episode(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active,
                                      int count, int n, int env_kind, bool ctbr, bool spec, hipStream_t s) {
   int nt, eb;
@@ -354,6 +308,73 @@ hipError_t launch_pop_policy_episode(const KConsts<float>* kc, const PopEpisodeE
              ? launch_pop_episode_kind<QUAD_ENV_TRAJ>(kc, tab, active, count, n, ctbr, spec, nt, eb, s)
              : launch_pop_episode_kind<QUAD_ENV_HOVER>(kc, tab, active, count, n, ctbr, spec, nt, eb, s);
 }
+
+// quad_policy_episode's argument checks and its flattened arguments (also quad_actor_episode's and
+// quad_pop_attach_eval's)
+int pop::episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out,
+                      const char* who) {
+  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, std::string(who) + ": env_kind must be HOVER or TRAJ");
+  return policy_run_args(h, packed, r, false, out, who);
+}
+
+// quad_policy_waypoints' argument checks and its flattened arguments (also quad_actor_waypoints')
+int waypoints_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
+                   EpisodeArgs* out, const char* who) {
+  if (!h || !packed || !r || !wr) return fail(QUAD_EINVAL, "handle/packed/run/waypoints is NULL");
+  if (int rc = check_waypoint_run(h, who, wr)) return rc;
+  return policy_run_args(h, packed, r, wr->trace_reward || wr->trace_wp_idx, out, who);
+}
 #endif
 
 }  // namespace quadenv
+
+#if PE_KIND == 0
+using namespace quadenv;
+
+extern "C" {
+
+int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
+  if (!h || !est) return fail(QUAD_EINVAL, "handle/est is NULL");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_deploy_obs: env_kind must be HOVER or TRAJ");
+  if (int rc = check_est(est, "quad_deploy_obs")) return rc;
+  if (!est->state) return fail(QUAD_EINVAL, "quad_deploy_obs: the estimator state block is required");
+  if (!state12 || !target3 || !obs) return fail(QUAD_EINVAL, "quad_deploy_obs: state12, target3 and obs are required");
+  if (n < 1) return fail(QUAD_EINVAL, "quad_deploy_obs: n must be >= 1");
+  DeviceGuard g(h->device);
+  hipLaunchKernelGGL(k_deploy_obs, dim3((n + DEPLOY_BLOCK - 1) / DEPLOY_BLOCK), dim3(DEPLOY_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), h->kdev, EstArgs{est->alpha, est->alpha_all, est->max_dt, est->state},
+                     state12, target3, timestamp, n, obs, vel_est);
+  HIP_TRY(hipGetLastError());
+  return QUAD_OK;
+}
+
+int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream) {
+  EpisodeArgs a{};
+  if (int rc = pop::episode_args(h, packed, r, &a)) return rc;
+  DeviceGuard g(h->device);
+  int nt, eb;
+  episode_block_shape(h->n, nt, eb);
+  const bool ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h->cfg.env_kind == QUAD_ENV_TRAJ
+              ? launch_episode_kind<QUAD_ENV_TRAJ>(h->kdev, h->kp, ctbr, h->spec, r->obs_mode, nt, eb, packed, a, s)
+              : launch_episode_kind<QUAD_ENV_HOVER>(h->kdev, h->kp, ctbr, h->spec, r->obs_mode, nt, eb, packed, a, s));
+  return QUAD_OK;
+}
+
+int quad_policy_waypoints(QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
+                          void* stream) {
+  EpisodeArgs a{};
+  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_policy_waypoints")) return rc;
+  DeviceGuard g(h->device);
+  HIP_TRY(launch_policy_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode, packed, a, *wr,
+                                  static_cast<hipStream_t>(stream)));
+  return QUAD_OK;
+}
+
+}  // extern "C"
+#endif

@@ -16,20 +16,6 @@
 namespace quadenv {
 namespace pop {
 
-// what the population needs of an env handle (QuadHandle is quadenv.hip's)
-struct EnvView {
-  const KConsts<float>* kdev;   // the handle's constant block on the device
-  const KConsts<float>* khost;  // and its host copy (members must agree on it, bit for bit)
-  KParams kp;
-  int32_t env_kind, wrapper, auto_reset, device, n;
-  bool spec;
-};
-void env_view(const QuadHandle* h, EnvView* v);  // quadenv.hip
-// quad_policy_episode's argument checks (QUAD_EINVAL + message) and its flattened arguments; quadenv.hip
-// (who: the entry point the messages name)
-int episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out,
-                 const char* who = "quad_policy_episode");
-
 // A table entry seen through the constant address space (device code only). A population table is written by
 // the host before any launch and never while one runs, so its entries are invariant for a kernel, exactly as
 // its kernel arguments are; the constant address space tells the compiler so, and it may then re-issue an

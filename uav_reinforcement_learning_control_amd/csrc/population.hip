@@ -13,11 +13,8 @@
 #include <vector>
 
 #include "../../include/quadenv.h"
+#include "handle.h"
 #include "population.h"
-
-namespace quadenv {
-int set_error(int code, const char* msg);  // quadenv.hip
-}
 
 using namespace quadenv;
 using namespace quadenv::pop;
@@ -58,16 +55,11 @@ int hfail(const char* what, hipError_t e) {
   return set_error(QUAD_EHIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
 }
 
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
+// two handles agree on what a population shares: kind, wrapper, constants (bit for bit), env count and device
+bool same_envs(const QuadHandle* a, const QuadHandle* b) {
+  return a->cfg.env_kind == b->cfg.env_kind && a->cfg.wrapper == b->cfg.wrapper && a->n == b->n &&
+         a->device == b->device && a->spec == b->spec && std::memcmp(&a->kh, &b->kh, sizeof(KConsts<float>)) == 0;
+}
 
 template <class T>
 hipError_t upload(T** dev, const void* host, size_t bytes) {
@@ -148,7 +140,7 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   std::vector<lrn::GArgs> gt(static_cast<size_t>(P));
   std::vector<lrn::RArgs> rt(static_cast<size_t>(P));
   std::vector<lrn::AdamArgs> at(static_cast<size_t>(P));
-  EnvView v0{};
+  const QuadHandle* v0 = nullptr;
   for (int32_t i = 0; i < P; i++) {
     const QuadPopMember& m = members[i];
     const QuadRollout& r = m.rollout;
@@ -162,21 +154,19 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
          reinterpret_cast<uintptr_t>(r.obs_copy) | reinterpret_cast<uintptr_t>(r.last_obs) |
          reinterpret_cast<uintptr_t>(m.scratch_actions)) & 15u)
       return pfail(who + "packed, actions, obs_copy, last_obs and scratch_actions must be 16-byte aligned");
-    EnvView v{};
-    env_view(m.env, &v);
-    if (v.env_kind != QUAD_ENV_HOVER && v.env_kind != QUAD_ENV_TRAJ) return pfail(who + "env_kind must be HOVER or TRAJ");
-    if (v.wrapper != QUAD_WRAP_NONE && v.wrapper != QUAD_WRAP_CTBR)
+    const QuadHandle* v = m.env;
+    if (v->cfg.env_kind != QUAD_ENV_HOVER && v->cfg.env_kind != QUAD_ENV_TRAJ)
+      return pfail(who + "env_kind must be HOVER or TRAJ");
+    if (v->cfg.wrapper != QUAD_WRAP_NONE && v->cfg.wrapper != QUAD_WRAP_CTBR)
       return pfail(who + "the policy takes 12-D obs (wrapper NONE or CTBR)");
-    if (!v.auto_reset) return pfail(who + "the handle needs auto_reset = 1");
+    if (!v->cfg.auto_reset) return pfail(who + "the handle needs auto_reset = 1");
     if (i == 0) v0 = v;
-    if (v.env_kind != v0.env_kind || v.wrapper != v0.wrapper || v.n != v0.n || v.device != v0.device ||
-        v.spec != v0.spec || std::memcmp(v.khost, v0.khost, sizeof(KConsts<float>)) != 0)
-      return pfail(who + "env kind, wrapper, constants, env count or device differ from member 0's");
+    if (!same_envs(v, v0)) return pfail(who + "env kind, wrapper, constants, env count or device differ from member 0's");
     if (r.rows != members[0].rollout.rows) return pfail(who + "rows differ from member 0's");
-    const int64_t total = int64_t(r.rows) * v.n;
+    const int64_t total = int64_t(r.rows) * v->n;
     if (total % batch != 0) return pfail(who + "rows x envs is not a multiple of the minibatch");
     if (total / batch > 65535) return pfail(who + "more than 65,535 minibatches per epoch");
-    roll[size_t(i)] = RollEntry{v.kp, m.packed,
+    roll[size_t(i)] = RollEntry{v->kp, m.packed,
                                 RollArgs{r.obs_copy, r.actions, r.log_prob, r.value, r.episode_starts, r.rewards,
                                          r.last_obs, r.last_start, r.ep_ret, r.ep_len, r.stats, uint32_t(r.rows), 0u, 0,
                                          r.deterministic, r.seed, r.gamma}};
@@ -191,11 +181,11 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   }
   QuadPop* p = new (std::nothrow) QuadPop();
   if (!p) return set_error(QUAD_ENOMEM, "quad_pop_create: out of host memory");
-  p->P = P; p->n = v0.n; p->rows = members[0].rollout.rows; p->batch = batch;
+  p->P = P; p->n = v0->n; p->rows = members[0].rollout.rows; p->batch = batch;
   p->nmb = int32_t(int64_t(p->rows) * p->n / batch);
   p->normalize = (normalize_advantage && batch > 1) ? 1 : 0;
-  p->device = v0.device; p->env_kind = v0.env_kind; p->ctbr = v0.wrapper == QUAD_WRAP_CTBR; p->spec = v0.spec;
-  p->kc = v0.kdev;
+  p->device = v0->device; p->env_kind = v0->cfg.env_kind; p->ctbr = v0->cfg.wrapper == QUAD_WRAP_CTBR;
+  p->spec = v0->spec; p->kc = v0->kdev;
   p->nb = lrn::layout_both(batch).nb;
   p->adam_nblocks = at[0].nblocks;
   for (int32_t i = 0; i < P; i++) p->packed.push_back(members[i].packed);
@@ -300,7 +290,7 @@ int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals) {
   if (!pop || !evals) return pfail("quad_pop_attach_eval: pop / evals is NULL");
   std::vector<PopEpisodeEntry> tab(static_cast<size_t>(pop->P));
   std::vector<char> ok(static_cast<size_t>(pop->P), 0);
-  EnvView v0{};
+  const QuadHandle* v0 = nullptr;
   int32_t first = -1;
   for (int32_t i = 0; i < pop->P; i++) {
     if (!evals[i].env) continue;  // a member that is not evaluated: no entry, quad_pop_episode rejects it
@@ -308,16 +298,14 @@ int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals) {
     EpisodeArgs a{};
     if (int rc = episode_args(evals[i].env, pop->packed[size_t(i)], &evals[i].run, &a)) return rc;
     if (evals[i].run.obs_mode != QUAD_OBS_ENV) return pfail(who + "obs_mode must be QUAD_OBS_ENV");
-    EnvView v{};
-    env_view(evals[i].env, &v);
+    const QuadHandle* v = evals[i].env;
     if (first < 0) { first = i; v0 = v; }
-    if (v.env_kind != v0.env_kind || v.wrapper != v0.wrapper || v.n != v0.n || v.device != v0.device ||
-        v.spec != v0.spec || std::memcmp(v.khost, v0.khost, sizeof(KConsts<float>)) != 0)
+    if (!same_envs(v, v0))
       return pfail(who + "env kind, wrapper, constants, env count or device differ from the first evaluated member's");
     if (evals[i].run.max_steps != evals[first].run.max_steps)
       return pfail(who + "max_steps differ from the first evaluated member's");
-    if (v.device != pop->device) return pfail(who + "the evaluation handle is on another device");
-    tab[size_t(i)] = PopEpisodeEntry{v.kp, pop->packed[size_t(i)], a};
+    if (v->device != pop->device) return pfail(who + "the evaluation handle is on another device");
+    tab[size_t(i)] = PopEpisodeEntry{v->kp, pop->packed[size_t(i)], a};
     ok[size_t(i)] = 1;
   }
   if (first < 0) return pfail("quad_pop_attach_eval: no member has an evaluation handle");
@@ -330,8 +318,8 @@ int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals) {
   (void)hipFree(pop->eval);
   pop->eval = dev;
   pop->eval_ok = ok;
-  pop->eval_kc = v0.kdev; pop->eval_n = v0.n; pop->eval_kind = v0.env_kind;
-  pop->eval_ctbr = v0.wrapper == QUAD_WRAP_CTBR; pop->eval_spec = v0.spec;
+  pop->eval_kc = v0->kdev; pop->eval_n = v0->n; pop->eval_kind = v0->cfg.env_kind;
+  pop->eval_ctbr = v0->cfg.wrapper == QUAD_WRAP_CTBR; pop->eval_spec = v0->spec;
   return QUAD_OK;
 }
 

@@ -1,4 +1,7 @@
-// quadenv.hip -- gfx950 kernels + the extern "C" ABI declared in include/quadenv.h.
+// quadenv.hip -- the env kernels on gfx950, the handle's lifecycle, the step / reset / observe / state / waypoint-tracker /
+// GAE entry points of include/quadenv.h, and the definitions of the argument checks the other kernel families' entry
+// points share (handle.h). Every other family's entry points are beside its kernels (ctrl.hip, rollout.hip,
+// policy_episode.hip, actor_arch.hip, brax_actor.hip, policy.hip, learner.hip, population.hip).
 //
 // Data layout in HBM (one allocation per handle): tiles of 64 envs, each NFT fields x 64 lanes of 4 B -- qpos,
 // qvel, voltage, target, CTBR integral, previous action, step count, episode counter (table: env_tiles.h).
@@ -22,8 +25,6 @@
 //   k_mem_floor          the step's loads and stores alone (bench.py's DRAM floor)
 //   k_random_actions     action_space.sample() stand-in (Philox), config 2
 //   k_gae                SB3 GAE(lambda) reverse scan, one thread per env
-// The kernels of the cascaded PID baseline and of the controller family (k_ctrl_act, k_ctrl_episode,
-// k_ctrl_waypoints, k_target_info) are in ctrl.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -37,13 +38,10 @@
 #include "quad_physics.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "kconsts_default.h"
-#include "brax_episode.h"
-#include "ctrl.h"
-#include "policy_episode.h"
 #include "population.h"
 #include "quad_waypoints.h"
-#include "rollout.h"
 
 using namespace quadenv;
 
@@ -56,15 +54,11 @@ thread_local std::string g_err;
 }  // namespace
 
 namespace quadenv {
-// shared with policy.hip: one last-error slot per thread for the whole library
+// one last-error slot per thread for the whole library (handle.h)
 int set_error(int code, const char* msg) {
   g_err = msg;
   return code;
 }
-}  // namespace quadenv
-
-namespace {
-
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
@@ -72,15 +66,9 @@ int fail(int code, const std::string& msg) {
 int hip_fail(hipError_t e, const char* what) {
   return fail(QUAD_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-// wrapper kinds: the RelPosActWrapper output stage (obs7) and the CTBR action path
-inline bool wrap_relpos(int32_t w) { return w == QUAD_WRAP_RELPOS || w == QUAD_WRAP_CTBR_RELPOS; }
-inline bool wrap_ctbr(int32_t w) { return w == QUAD_WRAP_CTBR || w == QUAD_WRAP_CTBR_RELPOS; }
+}  // namespace quadenv
 
-#define HIP_TRY(expr)                                  \
-  do {                                                 \
-    hipError_t e__ = (expr);                           \
-    if (e__ != hipSuccess) return hip_fail(e__, #expr); \
-  } while (0)
+namespace {
 
 // The reset draw of episode `ep` (the env's counter, loaded by the caller with the state; the
 // caller stores ep + 1).
@@ -979,28 +967,7 @@ __global__ __launch_bounds__(BLOCK) void k_pop_gae(const pop::GaeEntry* __restri
 
 }  // namespace
 
-struct QuadHandle {
-  QuadCfg cfg;
-  PhysConstsD pd;
-  KParams kp;
-  int device;
-  int n;
-  float* tiles = nullptr;     // env state (layout at the top of this file)
-  size_t tile_bytes = 0;
-  uint32_t* stage = nullptr;  // [NFT][n] staging for host-side get/set_state, allocated on first use
-  KConsts<float> kh;                 // host copy of the constant block
-  KConsts<float>* kdev = nullptr;    // device copy the kernels read (scalar loads, K$-resident)
-  bool spec = false;                 // kh == a reference default block: k_step_h's SPEC form
-  int hblock = 0;                    // envs per k_step_h block: 0 = by size (h_wide: 256 between H_SMALL and 2M, else 64)
-  int hd = -1;                       // k_step_hd for the 64-env nt launches: -1 = by size (hd_form), 0 / 1
-  int nt = -1;                       // k_step_h's state cache policy: -1 = by size (nt_state), 0 / 1
-};
-
 // ---- what the population launches (population.hip) need from this file
-void quadenv::pop::env_view(const QuadHandle* h, EnvView* v) {
-  *v = EnvView{h->kdev, &h->kh, h->kp, h->cfg.env_kind, h->cfg.wrapper, h->cfg.auto_reset, h->device, h->n, h->spec};
-}
-
 hipError_t quadenv::pop::launch_pop_gae(const GaeEntry* tab, const int32_t* active, int count, int T, int n,
                                         hipStream_t s) {
   hipLaunchKernelGGL(k_pop_gae, dim3((n + BLOCK - 1) / BLOCK, count), dim3(BLOCK), 0, s, tab, active, T, n);
@@ -1010,17 +977,6 @@ hipError_t quadenv::pop::launch_pop_gae(const GaeEntry* tab, const int32_t* acti
 namespace {
 
 int grid_of(int n) { return (n + BLOCK - 1) / BLOCK; }
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 // k_step_h's state cache policy for a launch of `count` envs (env_tiles.h): nt where it measured
 // faster -- one step wave per SIMD (65,536 envs) and the DRAM-bound sizes from 2M envs -- and the
@@ -1074,6 +1030,92 @@ int check_step_out(const QuadStepOut* out, const void* other, const char* pair =
 }
 
 }  // namespace
+
+// ---- the checks the families' entry points share (handle.h says what each asks)
+namespace quadenv {
+
+int check_est(const QuadVelEst* e, const char* who) {
+  const std::string w(who);
+  if (!e->alpha && !std::isfinite(e->alpha_all)) return fail(QUAD_EINVAL, w + ": alpha_all must be finite");
+  if (!(e->max_dt > 0.0)) return fail(QUAD_EINVAL, w + ": max_dt must be > 0");
+  return QUAD_OK;
+}
+
+int check_run(const char* who, int32_t n, int32_t max_steps, int32_t trace_envs, const QuadPidMetrics& m,
+              uintptr_t aligned, bool any_trace, const char* align_what, const QuadVelEst* est, double est_dt) {
+  const auto bad = [who](const std::string& msg) { return fail(QUAD_EINVAL, std::string(who) + ": " + msg); };
+  if (max_steps < 1) return bad("max_steps must be >= 1");
+  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
+      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
+      !m.yaw_rate_delta_sum)
+    return bad("every metrics array is required");
+  if (trace_envs < 0 || trace_envs > n) return bad("trace_envs must be in [0, N]");
+  if (est) {
+    if (int rc = check_est(est, who)) return rc;
+    if (!(est_dt > 0.0)) return bad("est_dt must be > 0");
+  }
+  if (any_trace && trace_envs > 0) {
+    if (int64_t(max_steps) * trace_envs * 48 > int64_t(UINT32_MAX))
+      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
+    if (aligned & 15u) return bad(std::string(align_what) + " must be 16-byte aligned");
+  }
+  return QUAD_OK;
+}
+
+int check_law_table(const QuadHandle* h, const char* who, const LawIds& ids, int32_t id, int32_t n_sets,
+                    const void* table) {
+  const std::string w(who);
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
+  if (h->cfg.wrapper != QUAD_WRAP_NONE)
+    return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
+  if (id < ids.lo || id > ids.hi) return fail(QUAD_EINVAL, w + ": unknown " + ids.what);
+  if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
+  if (!table) return fail(QUAD_EINVAL, w + ": " + ids.table + " is NULL");
+  return QUAD_OK;
+}
+
+int check_act_rows(const char* who, const float* state12, const float* target9, const double* state,
+                   const char* state_name, const float* actions, int32_t n) {
+  const std::string w(who);
+  if (!state12 || !target9 || !state || !actions)
+    return fail(QUAD_EINVAL, w + ": state12, target9, " + state_name + " and actions are required");
+  if (n < 1) return fail(QUAD_EINVAL, w + ": n must be >= 1");
+  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, w + ": actions must be 16-byte aligned");
+  return QUAD_OK;
+}
+
+int check_waypoint_run(const QuadHandle* h, const char* who, const QuadWaypointRun* wr) {
+  const std::string w(who);
+  if (h->cfg.env_kind != QUAD_ENV_HOVER)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER (a switch overwrites the target register)");
+  if (!wr->w.points || !wr->w.counts || wr->w.max_points < 1) return fail(QUAD_EINVAL, w + ": waypoint table is empty");
+  if (!(wr->w.reach_radius >= 0.f)) return fail(QUAD_EINVAL, w + ": reach_radius must be >= 0");
+  const QuadWaypointState& s = wr->s;
+  if (!s.wp_idx || !s.reached || !s.laps || !s.steps || !s.status || !s.total_reward)
+    return fail(QUAD_EINVAL, w + ": waypoint tracker arrays are required");
+  return QUAD_OK;
+}
+
+int policy_run_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, bool lap_traces,
+                    EpisodeArgs* out, const char* who) {
+  const auto bad = [who](const char* m) { return fail(QUAD_EINVAL, std::string(who) + ": " + m); };
+  if (wrap_relpos(h->cfg.wrapper)) return bad("the policy takes 12-D obs (no RELPOS)");
+  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED) return bad("unknown obs_mode");
+  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || lap_traces;
+  if (int rc = check_run(who, h->n, r->max_steps, r->trace_envs, r->metrics,
+                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
+                             reinterpret_cast<uintptr_t>(r->trace_obs),
+                         any_trace, "the action, state12 and obs traces", &r->est, r->est_dt))
+    return rc;
+  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
+  *out = EpisodeArgs{r->max_steps, any_trace ? r->trace_envs : 0,
+                     EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
+                     r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
+  return QUAD_OK;
+}
+
+}  // namespace quadenv
 
 extern "C" {
 
@@ -1255,363 +1297,6 @@ int quad_step_range(QuadHandle* h, int32_t first, int32_t count, const float* ac
     });
   }
   HIP_TRY(hipGetLastError());
-  return QUAD_OK;
-}
-
-int quad_rollout(QuadHandle* h, const float* packed, const QuadRollout* r, void* stream) {
-  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/rollout is NULL");
-  if (!r->obs_copy || !r->actions || !r->log_prob || !r->value || !r->episode_starts || !r->rewards ||
-      !r->last_obs || !r->last_start || !r->ep_ret || !r->ep_len || !r->stats)
-    return fail(QUAD_EINVAL, "quad_rollout: NULL buffer");
-  if (r->rows < 1 || r->steps < 1 || r->t0 < 0) return fail(QUAD_EINVAL, "quad_rollout: rows, steps >= 1, t0 >= 0");
-  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(r->actions) |
-       reinterpret_cast<uintptr_t>(r->obs_copy) | reinterpret_cast<uintptr_t>(r->last_obs)) & 15u)
-    return fail(QUAD_EINVAL, "quad_rollout: packed, actions, obs_copy and last_obs must be 16-byte aligned");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_rollout: env_kind must be HOVER or TRAJ");
-  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_rollout: the policy takes 12-D obs (no RELPOS)");
-  if (!h->cfg.auto_reset) return fail(QUAD_EINVAL, "quad_rollout: the handle needs auto_reset = 1");
-  DeviceGuard g(h->device);
-  RollArgs a{r->obs_copy, r->actions, r->log_prob, r->value, r->episode_starts, r->rewards, r->last_obs,
-             r->last_start, r->ep_ret, r->ep_len, r->stats, uint32_t(r->rows), uint32_t(r->t0), r->steps,
-             r->deterministic, r->seed, r->gamma};
-  HIP_TRY(launch_rollout(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, packed, a,
-                         static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- what the fused runs and the controller calls check alike; who: the entry point the messages name
-static int check_est(const QuadVelEst* e, const char* who) {
-  const std::string w(who);
-  if (!e->alpha && !std::isfinite(e->alpha_all)) return fail(QUAD_EINVAL, w + ": alpha_all must be finite");
-  if (!(e->max_dt > 0.0)) return fail(QUAD_EINVAL, w + ": max_dt must be > 0");
-  return QUAD_OK;
-}
-
-// The common fields of a run (QuadPidRun, QuadCtrlRun, QuadPolicyRun), in this order: max_steps, the twelve
-// metrics arrays, trace_envs' range, a policy run's estimator (est and est_dt; NULL for a controller run) and,
-// with a trace requested, the 32-bit bound on the trace rows' byte offsets and the 16-byte alignment of
-// `aligned`: the OR of the pointers the kernels store 16 bytes at a time, which align_what names.
-static int check_run(const char* who, int32_t n, int32_t max_steps, int32_t trace_envs, const QuadPidMetrics& m,
-                     uintptr_t aligned, bool any_trace, const char* align_what, const QuadVelEst* est = nullptr,
-                     double est_dt = 1.0) {
-  const auto bad = [who](const std::string& msg) { return fail(QUAD_EINVAL, std::string(who) + ": " + msg); };
-  if (max_steps < 1) return bad("max_steps must be >= 1");
-  if (!m.steps || !m.status || !m.total_reward || !m.pos_err_sum || !m.pos_err_sq || !m.pos_err_max ||
-      !m.yaw_rate_abs_sum || !m.yaw_rate_sum || !m.yaw_rate_sq || !m.yaw_rate_abs_max || !m.yaw_rate_sign_changes ||
-      !m.yaw_rate_delta_sum)
-    return bad("every metrics array is required");
-  if (trace_envs < 0 || trace_envs > n) return bad("trace_envs must be in [0, N]");
-  if (est) {
-    if (int rc = check_est(est, who)) return rc;
-    if (!(est_dt > 0.0)) return bad("est_dt must be > 0");
-  }
-  if (any_trace && trace_envs > 0) {
-    if (int64_t(max_steps) * trace_envs * 48 > int64_t(UINT32_MAX))
-      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if (aligned & 15u) return bad(std::string(align_what) + " must be 16-byte aligned");
-  }
-  return QUAD_OK;
-}
-
-// what quad_pid_* (ids: the modes) and quad_ctrl_* (ids: the laws) ask of the handle and of the table
-struct LawIds {
-  int32_t lo, hi;            // the valid ids
-  const char *what, *table;  // the words the messages print
-};
-constexpr LawIds PID_MODES{QUAD_PID_YAW_FRAME, QUAD_PID_WORLD_FRAME, "mode", "gains"};
-constexpr LawIds CTRL_LAWS{QUAD_CTRL_PID_YAW, QUAD_CTRL_LQR, "law", "params"};
-static int check_law_table(const QuadHandle* h, const char* who, const LawIds& ids, int32_t id, int32_t n_sets,
-                           const void* table) {
-  const std::string w(who);
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
-  if (h->cfg.wrapper != QUAD_WRAP_NONE)
-    return fail(QUAD_EINVAL, w + ": the law emits thrust / torque actions (wrapper NONE)");
-  if (id < ids.lo || id > ids.hi) return fail(QUAD_EINVAL, w + ": unknown " + ids.what);
-  if (n_sets < 1) return fail(QUAD_EINVAL, w + ": n_sets must be >= 1");
-  if (!table) return fail(QUAD_EINVAL, w + ": " + ids.table + " is NULL");
-  return QUAD_OK;
-}
-
-// the rows of quad_pid_act / quad_ctrl_act; state_name: "integ" / "state"
-static int check_act_rows(const char* who, const float* state12, const float* target9, const double* state,
-                          const char* state_name, const float* actions, int32_t n) {
-  const std::string w(who);
-  if (!state12 || !target9 || !state || !actions)
-    return fail(QUAD_EINVAL, w + ": state12, target9, " + state_name + " and actions are required");
-  if (n < 1) return fail(QUAD_EINVAL, w + ": n must be >= 1");
-  if (reinterpret_cast<uintptr_t>(actions) & 15u) return fail(QUAD_EINVAL, w + ": actions must be 16-byte aligned");
-  return QUAD_OK;
-}
-
-// ---- cascaded PID baseline (kernels: ctrl.hip, on QuadPidGains rows)
-int quad_pid_default_gains(QuadPidGains* g) {
-  if (!g) return fail(QUAD_EINVAL, "gains is NULL");
-  pid_default_gains_fill(g);
-  return QUAD_OK;
-}
-
-int quad_pid_act(QuadHandle* h, const QuadPidGains* gains, int32_t n_sets, const int32_t* set_of, int32_t mode,
-                 const float* state12, const float* target9, int32_t n, double* integ, float* actions,
-                 double* diag, void* stream) {
-  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
-  if (int rc = check_law_table(h, "quad_pid_act", PID_MODES, mode, n_sets, gains)) return rc;
-  if (int rc = check_act_rows("quad_pid_act", state12, target9, integ, "integ", actions, n)) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_pid_act(make_pid_plant(h->cfg), gains, n_sets, set_of, mode, state12, target9, n, integ, actions, diag,
-                         static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-int quad_pid_episode(QuadHandle* h, const QuadPidRun* r, void* stream) {
-  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
-  if (int rc = check_law_table(h, "quad_pid_episode", PID_MODES, r->mode, r->n_sets, r->gains)) return rc;
-  const bool any_trace = r->trace_actions || r->trace_state12;
-  if (int rc = check_run("quad_pid_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
-                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
-                         any_trace, "traces"))
-    return rc;
-  DeviceGuard g(h->device);
-  QuadPidRun run = *r;
-  if (!any_trace) run.trace_envs = 0;
-  HIP_TRY(launch_pid_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
-                             static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- controller family (kernels: ctrl.hip); quad_pid_*'s rules with a law id in place of the mode
-int quad_ctrl_default_params(QuadCtrlParams* p) {
-  if (!p) return fail(QUAD_EINVAL, "params is NULL");
-  ctrl_default_params_fill(p);
-  return QUAD_OK;
-}
-
-int quad_ctrl_act(QuadHandle* h, const QuadCtrlParams* params, int32_t n_sets, const int32_t* set_of, int32_t law,
-                  const float* state12, const float* target9, int32_t n, double* state, float* actions,
-                  double* diag, void* stream) {
-  if (!h) return fail(QUAD_EINVAL, "handle is NULL");
-  if (int rc = check_law_table(h, "quad_ctrl_act", CTRL_LAWS, law, n_sets, params)) return rc;
-  if (int rc = check_act_rows("quad_ctrl_act", state12, target9, state, "state", actions, n)) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_ctrl_act(make_pid_plant(h->cfg), params, n_sets, set_of, law, state12, target9, n, state, actions, diag,
-                          static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-int quad_ctrl_episode(QuadHandle* h, const QuadCtrlRun* r, void* stream) {
-  if (!h || !r) return fail(QUAD_EINVAL, "handle/run is NULL");
-  if (int rc = check_law_table(h, "quad_ctrl_episode", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
-  const bool any_trace = r->trace_actions || r->trace_state12;
-  if (int rc = check_run("quad_ctrl_episode", h->n, r->max_steps, r->trace_envs, r->metrics,
-                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
-                         any_trace, "traces"))
-    return rc;
-  DeviceGuard g(h->device);
-  QuadCtrlRun run = *r;
-  if (!any_trace) run.trace_envs = 0;
-  HIP_TRY(launch_ctrl_episode(h->kdev, h->kp, h->cfg.env_kind, h->spec, make_pid_plant(h->cfg), run,
-                              static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- the deployed observation path and the policy's fused episode (kernels: policy_episode.hip)
-int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
-                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
-  if (!h || !est) return fail(QUAD_EINVAL, "handle/est is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_deploy_obs: env_kind must be HOVER or TRAJ");
-  if (int rc = check_est(est, "quad_deploy_obs")) return rc;
-  if (!est->state) return fail(QUAD_EINVAL, "quad_deploy_obs: the estimator state block is required");
-  if (!state12 || !target3 || !obs) return fail(QUAD_EINVAL, "quad_deploy_obs: state12, target3 and obs are required");
-  if (n < 1) return fail(QUAD_EINVAL, "quad_deploy_obs: n must be >= 1");
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_deploy_obs(h->kdev, EstArgs{est->alpha, est->alpha_all, est->max_dt, est->state}, state12, target3,
-                            timestamp, n, obs, vel_est, static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-}  // extern "C"
-
-// What quad_policy_episode / quad_policy_waypoints and their quad_actor_* forms ask of the wrapper, the run and
-// the image, after the entry point's own handle checks, and the flattened arguments. who: the entry point the
-// messages name (the message is built only on failure); lap_traces: the lap call's own traces are requested.
-static int policy_run_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, bool lap_traces,
-                           EpisodeArgs* out, const char* who) {
-  const auto bad = [who](const char* m) { return fail(QUAD_EINVAL, std::string(who) + ": " + m); };
-  if (wrap_relpos(h->cfg.wrapper)) return bad("the policy takes 12-D obs (no RELPOS)");
-  if (r->obs_mode != QUAD_OBS_ENV && r->obs_mode != QUAD_OBS_DEPLOYED) return bad("unknown obs_mode");
-  const bool any_trace = r->trace_actions || r->trace_state12 || r->trace_obs || r->trace_vel_est || lap_traces;
-  if (int rc = check_run(who, h->n, r->max_steps, r->trace_envs, r->metrics,
-                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12) |
-                             reinterpret_cast<uintptr_t>(r->trace_obs),
-                         any_trace, "the action, state12 and obs traces", &r->est, r->est_dt))
-    return rc;
-  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
-  *out = EpisodeArgs{r->max_steps, any_trace ? r->trace_envs : 0,
-                     EstArgs{r->est.alpha, r->est.alpha_all, r->est.max_dt, r->est.state}, r->est_dt,
-                     r->trace_actions, r->trace_state12, r->trace_obs, r->trace_vel_est, r->metrics, r->vel_err_sq};
-  return QUAD_OK;
-}
-
-// quad_policy_episode's argument checks and its flattened arguments (also quad_pop_attach_eval's, population.hip)
-int quadenv::pop::episode_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, EpisodeArgs* out,
-                               const char* who) {
-  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/run is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, std::string(who) + ": env_kind must be HOVER or TRAJ");
-  return policy_run_args(h, packed, r, false, out, who);
-}
-
-extern "C" {
-
-int quad_policy_episode(QuadHandle* h, const float* packed, const QuadPolicyRun* r, void* stream) {
-  EpisodeArgs a{};
-  if (int rc = quadenv::pop::episode_args(h, packed, r, &a)) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_policy_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode,
-                                packed, a, static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- waypoint laps in one launch (kernels: k_ctrl_waypoints, k_policy_waypoints)
-// what both lap calls ask of the handle and of the tracker; the wrapper is the caller's to check
-static int check_waypoint_run(const QuadHandle* h, const char* who, const QuadWaypointRun* wr) {
-  const std::string w(who);
-  if (h->cfg.env_kind != QUAD_ENV_HOVER)
-    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER (a switch overwrites the target register)");
-  if (!wr->w.points || !wr->w.counts || wr->w.max_points < 1) return fail(QUAD_EINVAL, w + ": waypoint table is empty");
-  if (!(wr->w.reach_radius >= 0.f)) return fail(QUAD_EINVAL, w + ": reach_radius must be >= 0");
-  const QuadWaypointState& s = wr->s;
-  if (!s.wp_idx || !s.reached || !s.laps || !s.steps || !s.status || !s.total_reward)
-    return fail(QUAD_EINVAL, w + ": waypoint tracker arrays are required");
-  return QUAD_OK;
-}
-
-int quad_ctrl_waypoints(QuadHandle* h, const QuadCtrlRun* r, const QuadWaypointRun* wr, void* stream) {
-  if (!h || !r || !wr) return fail(QUAD_EINVAL, "handle/run/waypoints is NULL");
-  if (int rc = check_waypoint_run(h, "quad_ctrl_waypoints", wr)) return rc;
-  if (int rc = check_law_table(h, "quad_ctrl_waypoints", CTRL_LAWS, r->law, r->n_sets, r->params)) return rc;
-  const bool any_trace = r->trace_actions || r->trace_state12 || wr->trace_reward || wr->trace_wp_idx;
-  if (int rc = check_run("quad_ctrl_waypoints", h->n, r->max_steps, r->trace_envs, r->metrics,
-                         reinterpret_cast<uintptr_t>(r->trace_actions) | reinterpret_cast<uintptr_t>(r->trace_state12),
-                         any_trace, "traces"))
-    return rc;
-  DeviceGuard g(h->device);
-  QuadCtrlRun run = *r;
-  if (!any_trace) run.trace_envs = 0;
-  HIP_TRY(launch_ctrl_waypoints(h->kdev, h->kp, h->spec, make_pid_plant(h->cfg), run, *wr,
-                                static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// quad_policy_waypoints' argument checks and its flattened arguments (who: the entry point the messages name)
-static int waypoints_args(const QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
-                          EpisodeArgs* out, const char* who) {
-  if (!h || !packed || !r || !wr) return fail(QUAD_EINVAL, "handle/packed/run/waypoints is NULL");
-  if (int rc = check_waypoint_run(h, who, wr)) return rc;
-  return policy_run_args(h, packed, r, wr->trace_reward || wr->trace_wp_idx, out, who);
-}
-
-int quad_policy_waypoints(QuadHandle* h, const float* packed, const QuadPolicyRun* r, const QuadWaypointRun* wr,
-                          void* stream) {
-  EpisodeArgs a{};
-  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_policy_waypoints")) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_policy_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, h->spec, r->obs_mode, packed, a, *wr,
-                                  static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- the general actor's episode and laps (kernels: actor_arch.hip): the same checks, the same arguments
-int quad_actor_episode(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
-                       void* stream) {
-  ActorNet net;
-  if (int rc = actor_net_of(arch, &net)) return rc;
-  EpisodeArgs a{};
-  if (int rc = quadenv::pop::episode_args(h, packed, r, &a, "quad_actor_episode")) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_actor_episode(h->kdev, h->kp, h->cfg.env_kind, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net,
-                               packed, a, static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-int quad_actor_waypoints(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadPolicyRun* r,
-                         const QuadWaypointRun* wr, void* stream) {
-  ActorNet net;
-  if (int rc = actor_net_of(arch, &net)) return rc;
-  EpisodeArgs a{};
-  if (int rc = waypoints_args(h, packed, r, wr, &a, "quad_actor_waypoints")) return rc;
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_actor_waypoints(h->kdev, h->kp, h->cfg.wrapper == QUAD_WRAP_CTBR, r->obs_mode, net, packed, a, *wr,
-                                 static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- the Brax-profile policy's episodes on the brax kinds (kernels: brax_actor.hip)
-int quad_brax_episode(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxRun* r,
-                      void* stream) {
-  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_episode: ") + m); };
-  ActorNet net;
-  if (int rc = brax_net_of(arch, &net)) return rc;
-  if (!h || !packed || !r) return bad("handle/packed/run is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
-    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
-  if (r->max_steps < 1) return bad("max_steps must be >= 1");
-  const QuadBraxMetrics& m = r->metrics;
-  if (!m.ret || !m.steps || !m.err_sum || !m.err_sq_sum || !m.err_count || !m.status)
-    return bad("every metrics array is required");
-  if (r->trace_envs < 0 || r->trace_envs > h->n) return bad("trace_envs must be in [0, N]");
-  if (reinterpret_cast<uintptr_t>(packed) & 15u) return bad("packed must be 16-byte aligned");
-  const bool any_trace = r->trace_actions || r->trace_obs || r->trace_pos || r->trace_target;
-  if (any_trace && r->trace_envs > 0) {
-    if (int64_t(r->max_steps) * r->trace_envs * 84 > int64_t(UINT32_MAX))
-      return bad("max_steps * trace_envs too large (trace rows use 32-bit byte offsets)");
-    if (reinterpret_cast<uintptr_t>(r->trace_actions) & 15u) return bad("the action trace must be 16-byte aligned");
-  }
-  const BraxEpisodeArgs a{r->max_steps, any_trace ? r->trace_envs : 0, r->deterministic, r->noise_step0, r->seed,
-                          r->metrics, r->trace_actions, r->trace_obs, r->trace_pos, r->trace_target};
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_brax_episode(h->kdev, h->kp, h->cfg.env_kind, net, packed, a, static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-// ---- the Brax learner's unrolls on the brax kinds (kernel: brax_unroll.hip)
-int quad_brax_unroll(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxUnroll* u,
-                     void* stream) {
-  const auto bad = [](const char* m) { return fail(QUAD_EINVAL, std::string("quad_brax_unroll: ") + m); };
-  ActorNet net;
-  if (int rc = brax_net_of(arch, &net)) return rc;
-  if (!h || !packed || !u) return bad("handle/packed/unroll is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_BRAX_HOVER && h->cfg.env_kind != QUAD_ENV_BRAX_TRAJ)
-    return bad("env_kind must be BRAX_HOVER or BRAX_TRAJ");
-  if (!h->cfg.auto_reset) return bad("the handle must have auto_reset = 1");
-  if (u->steps < 1 || u->unroll_length < 1) return bad("steps and unroll_length must be >= 1");
-  if (u->steps % u->unroll_length) return bad("steps must be a multiple of unroll_length");
-  if (!u->obs || !u->raw || !u->log_prob || !u->reward || !u->discount || !u->truncation || !u->next_obs ||
-      !u->ep_ret || !u->stats)
-    return bad("every buffer is required");
-  const auto at = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if ((at(packed) | at(u->raw)) & 15u) return bad("packed and raw must be 16-byte aligned");
-  if ((at(u->obs) | at(u->log_prob) | at(u->reward) | at(u->discount) | at(u->truncation) | at(u->next_obs) |
-       at(u->ep_ret)) & 3u)
-    return bad("the float buffers must be 4-byte aligned");
-  if (at(u->stats) & 7u) return bad("stats must be 8-byte aligned");
-  if (int64_t(u->steps) * h->n * 84 > int64_t(UINT32_MAX))
-    return bad("steps * N too large (rows use 32-bit byte offsets)");
-  const BraxUnrollArgs a{u->obs, u->raw, u->log_prob, u->reward, u->discount, u->truncation, u->next_obs, u->ep_ret,
-                         u->stats, u->steps, u->unroll_length, u->noise_step0, u->seed};
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_brax_unroll(h->kdev, h->kp, h->cfg.env_kind, net, packed, a, static_cast<hipStream_t>(stream)));
-  return QUAD_OK;
-}
-
-int quad_target_info(QuadHandle* h, float* target_info, void* stream) {
-  if (!h || !target_info) return fail(QUAD_EINVAL, "handle/target_info is NULL");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_target_info: env_kind must be HOVER or TRAJ");
-  DeviceGuard g(h->device);
-  HIP_TRY(launch_target_info(h->kdev, h->kp, h->cfg.env_kind, target_info, static_cast<hipStream_t>(stream)));
   return QUAD_OK;
 }
 

@@ -1,4 +1,4 @@
-// rollout.h -- host-side entry of the fused rollout kernel (rollout.hip), called by quad_rollout.
+// rollout.h -- the fused rollout kernel's arguments (rollout.hip), shared with the population tables (population.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -27,9 +27,5 @@ struct RollArgs {  // QuadRollout, flattened
   uint64_t seed;
   float gamma;
 };
-
-// k_rollout<env_kind, ctbr> over all envs of kp (one 256-env block per CU-resident slot)
-hipError_t launch_rollout(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
-                          const float* packed, const RollArgs& a, hipStream_t s);
 
 }  // namespace quadenv

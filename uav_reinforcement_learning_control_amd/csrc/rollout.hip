@@ -1,5 +1,5 @@
 // rollout.hip -- the fused PPO rollout: policy (MFMA) + env step + SB3 bookkeeping for many steps
-// in ONE launch (quad_rollout, include/quadenv.h).
+// in ONE launch (quad_rollout, include/quadenv.h: the entry point is at the end of this file).
 //
 // Reference loop (SB3 OnPolicyAlgorithm.collect_rollouts as train.py:50-68 configures it, with
 // HoverEnv.step / TrajectoryFollowEnv.step (+ RateControlWrapper) as the env and DummyVecEnv's
@@ -29,6 +29,7 @@
 #include "../../include/quadenv.h"
 #include "dispatch.h"
 #include "env_tiles.h"
+#include "handle.h"
 #include "kconsts_default.h"
 #include "policy_net.h"
 #include "population.h"
@@ -270,19 +271,8 @@ __global__ __launch_bounds__(512 / NT) void k_rollout(const KConsts<float>* __re
 template <int KIND, bool CTBR, int NT, bool SPEC>
 hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* packed, const RollArgs& a,
                   hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (!opted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rollout<KIND, CTBR, NT, SPEC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
-  hipLaunchKernelGGL((k_rollout<KIND, CTBR, NT, SPEC>), dim3((kp.n + RBLOCK - 1) / RBLOCK), dim3(512 / NT), bytes,
-                     s, kc, kp, packed, a);
-  return hipGetLastError();
+  return launch_lds<&k_rollout<KIND, CTBR, NT, SPEC>>(dim3((kp.n + RBLOCK - 1) / RBLOCK), dim3(512 / NT),
+                                                      LDS_F * int(sizeof(float)), s, kc, kp, packed, a);
 }
 
 // The population form (population.h): block (b, k) is block b of member active[k]'s rollout. The member's
@@ -313,19 +303,8 @@ __global__ __launch_bounds__(512 / NT) void k_pop_rollout(const KConsts<float>* 
 template <int KIND, bool CTBR, int NT, bool SPEC>
 hipError_t launch_pop(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active, int count, int n,
                       uint32_t t0, int32_t steps, hipStream_t s) {
-  static bool opted[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  const int bytes = LDS_F * int(sizeof(float));
-  if (!opted[dev]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pop_rollout<KIND, CTBR, NT, SPEC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return e;
-    opted[dev] = true;
-  }
-  hipLaunchKernelGGL((k_pop_rollout<KIND, CTBR, NT, SPEC>), dim3((n + RBLOCK - 1) / RBLOCK, count), dim3(512 / NT),
-                     bytes, s, kc, tab, active, t0, steps);
-  return hipGetLastError();
+  return launch_lds<&k_pop_rollout<KIND, CTBR, NT, SPEC>>(dim3((n + RBLOCK - 1) / RBLOCK, count), dim3(512 / NT),
+                                                          LDS_F * int(sizeof(float)), s, kc, tab, active, t0, steps);
 }
 
 int rollout_nt() {
@@ -349,17 +328,35 @@ hipError_t pop::launch_pop_rollout(const KConsts<float>* kc, const RollEntry* ta
   });
 }
 
-hipError_t launch_rollout(const KConsts<float>* kc, const KParams& kp, int env_kind, bool ctbr, bool spec,
-                          const float* packed, const RollArgs& a, hipStream_t s) {
+}  // namespace quadenv
+
+using namespace quadenv;
+
+extern "C" int quad_rollout(QuadHandle* h, const float* packed, const QuadRollout* r, void* stream) {
+  if (!h || !packed || !r) return fail(QUAD_EINVAL, "handle/packed/rollout is NULL");
+  if (!r->obs_copy || !r->actions || !r->log_prob || !r->value || !r->episode_starts || !r->rewards ||
+      !r->last_obs || !r->last_start || !r->ep_ret || !r->ep_len || !r->stats)
+    return fail(QUAD_EINVAL, "quad_rollout: NULL buffer");
+  if (r->rows < 1 || r->steps < 1 || r->t0 < 0) return fail(QUAD_EINVAL, "quad_rollout: rows, steps >= 1, t0 >= 0");
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(r->actions) |
+       reinterpret_cast<uintptr_t>(r->obs_copy) | reinterpret_cast<uintptr_t>(r->last_obs)) & 15u)
+    return fail(QUAD_EINVAL, "quad_rollout: packed, actions, obs_copy and last_obs must be 16-byte aligned");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, "quad_rollout: env_kind must be HOVER or TRAJ");
+  if (wrap_relpos(h->cfg.wrapper)) return fail(QUAD_EINVAL, "quad_rollout: the policy takes 12-D obs (no RELPOS)");
+  if (!h->cfg.auto_reset) return fail(QUAD_EINVAL, "quad_rollout: the handle needs auto_reset = 1");
+  DeviceGuard g(h->device);
+  const RollArgs a{r->obs_copy, r->actions, r->log_prob, r->value, r->episode_starts, r->rewards, r->last_obs,
+                   r->last_start, r->ep_ret, r->ep_len, r->stats, uint32_t(r->rows), uint32_t(r->t0), r->steps,
+                   r->deterministic, r->seed, r->gamma};
   const int nt = rollout_nt();
-  return with_kind(env_kind == QUAD_ENV_TRAJ, ctbr, [&](auto kind, auto cb) {
+  const hipError_t e = with_kind(h->cfg.env_kind == QUAD_ENV_TRAJ, h->cfg.wrapper == QUAD_WRAP_CTBR, [&](auto kind, auto cb) {
     return with_bool(nt == 1, [&](auto one) {
-      return with_bool(spec, [&](auto sp) {
+      return with_bool(h->spec, [&](auto sp) {
         return launch<decltype(kind)::value, decltype(cb)::value, decltype(one)::value ? 1 : 2, decltype(sp)::value>(
-            kc, kp, packed, a, s);
+            h->kdev, h->kp, packed, a, static_cast<hipStream_t>(stream));
       });
     });
   });
+  return e == hipSuccess ? QUAD_OK : hip_fail(e, "k_rollout launch");
 }
-
-}  // namespace quadenv
