@@ -655,6 +655,68 @@ typedef struct QuadBraxUnroll {
 int quad_brax_unroll(QuadHandle* h, const QuadBraxActorArch* arch, const float* packed, const QuadBraxUnroll* u,
                      void* stream);
 
+/* ---- The Brax learner's minibatch gradient: the gradient of ppo/brax_ppo.py brax_ppo_loss (brax's
+ * compute_ppo_loss) with respect to the twelve tensors of the policy net 21 -> h1 -> h2 -> 8 and the value net
+ * 21 -> h1 -> h2 -> 1, in four launches on `stream` with no host synchronisation. Added within ABI v8.
+ *   total = -mean(min(rho A, clip(rho, 1 - eps, 1 + eps) A)) + 0.25 mean((vs - V)^2) - entropy_cost mean(entropy),
+ *   rho = exp(NormalTanh.log_prob(logits, raw) - log_prob); (vs, A) = brax's compute_gae of the minibatch's
+ *   trajectories on the value net's own baseline and bootstrap V(next_obs), with reward_scaling, discounting,
+ *   gae_lambda and the truncation / termination masks (termination = (1 - discount)(1 - truncation)), outside the
+ *   gradient; A = (A - mean) / (std(unbiased = False) + 1e-8) over the L mb rows unless normalize_advantage == 0;
+ *   entropy = sum of 1/2 + 1/2 log 2 pi + log scale + 2 (log 2 - x - softplus(-2 x)) at ONE sample
+ *   x = loc + scale z per row, differentiated through loc and scale.
+ * Ties of the min and the clip bounds follow torch's autograd (a tie's gradient is split in half; clamp passes it
+ * on the closed interval). Family: policy_h1 = policy_h2 = value_h1 = value_h2 = 128 and QUAD_ACTFN_RELU.
+ * Parameters and gradients are device f32 in flax's [in, out] layout (BraxMLP.kernels / biases); the gradients are
+ * OVERWRITTEN, not accumulated. mean / std [21]: observations are normalised (obs - mean) / std in f32 with the
+ * correctly rounded division (RunningStats.normalize).
+ * Batch: the time-major buffers quad_brax_unroll writes -- obs [U,L,N,21], next_obs [U,N,21], raw [U,L,N,4]
+ * (16-byte aligned), log_prob / reward / discount / truncation [U,L,N]. Trajectory m = u N + n; its step t is row
+ * (u L + t) N + n. index [mb] (int64) names the minibatch's trajectories: each entry must lie in [0, U N) -- this is
+ * the CALLER's responsibility, the launches do not check it. Rows are gathered through index; no minibatch copy is
+ * made. Row q = t mb + j of the minibatch-ordered arrays below is step t of trajectory index[j].
+ * entropy_noise [L,mb,4] (16-byte aligned) is z when given; when NULL z is the four Box-Muller normals of
+ * Philox(seed; index[j], noise_step * L + t, 0x500). noise_out [L,mb,4] (or NULL) receives the z used.
+ * Diagnostic outputs (NULL to skip): values [L+1,mb] (baseline rows, then the bootstrap row), vs [L,mb],
+ * advantages [L,mb] as they enter the surrogate; stats [3] = policy_loss, v_loss, entropy_loss.
+ * For equal arguments the results are bit-identical from call to call, and do not depend on where a trajectory's
+ * rows lie in the buffers.
+ * QUAD_EINVAL, with nothing launched: an arch outside the family; a NULL or misaligned parameter, gradient, unroll
+ * buffer or index; a misaligned optional buffer or workspace (16 bytes); mb < 1; L outside [1, 64]; U or N < 1;
+ * (L + 1) mb > 2^28; clipping_epsilon <= 0; workspace_bytes < quad_brax_ppo_workspace_bytes(mb, L). */
+typedef struct QuadBraxPPOParams {
+  const float *pi_w0, *pi_b0, *pi_w1, *pi_b1, *pi_w2, *pi_b2;  /* [21,h1] [h1] [h1,h2] [h2] [h2,8] [8] */
+  const float *vf_w0, *vf_b0, *vf_w1, *vf_b1, *vf_w2, *vf_b2;  /* [21,h1] [h1] [h1,h2] [h2] [h2,1] [1] */
+  const float *mean, *std;                                     /* [21] */
+  float min_std;
+  int32_t policy_h1, policy_h2, value_h1, value_h2, activation;
+} QuadBraxPPOParams;
+
+typedef struct QuadBraxPPOGrads {
+  float *pi_w0, *pi_b0, *pi_w1, *pi_b1, *pi_w2, *pi_b2;
+  float *vf_w0, *vf_b0, *vf_w1, *vf_b1, *vf_w2, *vf_b2;
+} QuadBraxPPOGrads;
+
+typedef struct QuadBraxPPOBatch {
+  const float *obs, *next_obs, *raw, *log_prob, *reward, *discount, *truncation;
+  const int64_t* index;        /* [mb] */
+  const float* entropy_noise;  /* [L,mb,4] or NULL */
+  float* noise_out;            /* [L,mb,4] or NULL */
+  float *values, *vs, *advantages;  /* diagnostics, or NULL */
+  float* stats;                /* [3] or NULL */
+  int32_t U, L, N, mb;
+  float clipping_epsilon, entropy_cost, discounting, gae_lambda, reward_scaling;
+  int32_t normalize_advantage;
+  uint32_t noise_step;
+  uint64_t seed;
+} QuadBraxPPOBatch;
+
+/* Device workspace (bytes, 16-byte aligned) quad_brax_ppo_grad needs; 0 for mb < 1, L outside [1, 64] or
+ * (L + 1) mb > 2^28. */
+int64_t quad_brax_ppo_workspace_bytes(int32_t mb, int32_t L);
+int quad_brax_ppo_grad(const QuadBraxPPOParams* p, const QuadBraxPPOBatch* b, const QuadBraxPPOGrads* gr,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Finish the pending step (end of a rollout): the epilogue for row (t-1) % rows if the cursor
  * marks one pending, then clears the mark. A no-op otherwise. */
 int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* cursor, int32_t n,

@@ -1,0 +1,282 @@
+"""The Brax learner's fused minibatch gradient (csrc/brax_learner.hip, quad_brax_ppo_grad; ppo/fused.py
+FusedBraxLearner; BraxPPOConfig.fused_update) on the GPU, on synthetic unroll buffers (tests/brax_learner_ref.py
+make_case): the gradient against float64 autograd of brax_ppo_loss at tests/test_gpu_learner.py's bar, the
+diagnostic outputs, the entropy noise, determinism and the gather, the argument checks, the Adam step, the Python
+layer, and a learning run with both flags on."""
+import copy
+import ctypes as C
+import functools
+import json
+import os
+import types
+
+import numpy as np
+import pytest
+import torch
+
+import brax_learner_ref as R
+from uav_reinforcement_learning_control_amd import _native as N
+from uav_reinforcement_learning_control_amd.envs import QuadVecEnv
+from uav_reinforcement_learning_control_amd.ppo.brax_ppo import BraxPPO, BraxPPOConfig, brax_gae
+from uav_reinforcement_learning_control_amd.ppo.fused import FusedBraxLearner
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+# (U, N, L, mb, seed, normalize_advantage): 65 loss rows = one full round + one row with a ragged bootstrap round;
+# exactly ten rounds; L = 1, mb = 1; several blocks per net; and the raw-advantage path
+CASES = {"ragged": (3, 11, 5, 13, 1, True), "rounds": (2, 40, 10, 64, 2, True), "single": (1, 7, 1, 1, 6, True),
+         "blocks": (4, 150, 10, 512, 4, True), "raw_adv": (3, 11, 5, 13, 5, False)}
+
+
+def _learner(case):
+    net = copy.deepcopy(case["net"]).float()
+    norm = types.SimpleNamespace(mean=case["mean"], std=case["std"])
+    opt = torch.optim.Adam(net.parameters(), lr=case["cfg"].learning_rate, eps=1e-8)
+    return FusedBraxLearner(net, norm, case["cfg"], opt=opt, seed=7)
+
+
+def _run(lrn, case, **kw):
+    """One grads() call from garbage-filled .grad tensors; returns (gradients, stats, diag) as clones."""
+    for p in lrn.params:
+        p.grad = torch.full_like(p, float("nan"))
+    stats = torch.full((3,), float("nan"), device=DEV)
+    diag = {}
+    kw.setdefault("entropy_noise", case["z"])
+    lrn.grads(kw.pop("buffers", case["buffers"]), kw.pop("index", case["index"]), stats=stats, diag=diag, **kw)
+    torch.cuda.synchronize()
+    return [p.grad.clone() for p in lrn.params], stats.clone(), {k: v.clone() for k, v in diag.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def built(name):
+    U, n, L, mb, seed, na = CASES[name]
+    case = R.make_case(U, n, L, mb, seed, device=DEV, normalize_advantage=na)
+    g64, st64 = R.autograd_reference(case, torch.float64)
+    g32, _ = R.autograd_reference(case, torch.float32)
+    lrn = _learner(case)
+    g, st, diag = _run(lrn, case)
+    return dict(case=case, g64=g64, g32=g32, st64=st64, lrn=lrn, g=g, st=st, diag=diag)
+
+
+NAMES = ["pi_k0", "pi_k1", "pi_k2", "pi_b0", "pi_b1", "pi_b2", "vf_k0", "vf_k1", "vf_k2", "vf_b0", "vf_b1", "vf_b2"]
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_gradient_matches_float64_autograd(name):
+    b = built(name)
+    assert b["case"]["dropped"] <= 0.2, b["case"]["dropped"]  # ReLU decisions: at most one candidate in five dropped
+    assert b["case"]["index"].numel() == CASES[name][3]
+    # a lone row's advantage normalises to 0; its trajectory terminates (not truncated), so the value loss is not 0
+    assert name != "single" or float(b["st64"][1]) > 0.0
+    for nm, g, g64, g32 in zip(NAMES, b["g"], b["g64"], b["g32"]):
+        assert bool(torch.isfinite(g).all()), nm  # the garbage was overwritten
+        err = float((g.double() - g64).abs().max())
+        e32 = float((g32 - g64).abs().max())
+        mx = float(g64.abs().max())
+        print(f"{name} {nm}: err {err:.3e} torch32 {e32:.3e} max {mx:.3e}")
+        assert err <= 1e-4 * mx + 4 * e32 + 1e-9, (name, nm, err, e32, mx)
+        assert err <= 4 * e32 + 1e-6 * mx + 1e-9, (name, nm, err, e32, mx)
+    print(name, "stats", b["st"].tolist(), b["st64"].tolist())
+    torch.testing.assert_close(b["st"].double(), b["st64"], rtol=1e-4, atol=1e-7)
+
+
+@pytest.mark.parametrize("name", ["ragged", "blocks", "raw_adv"])
+def test_diagnostics(name):
+    """values against the float64 forward; vs and advantages against float64 brax_gae on the kernel's own values:
+    each within 4x torch-fp32's error of the same expression on the same inputs + 1e-6 of the scale."""
+    b = built(name)
+    case, d = b["case"], b["diag"]
+    cfg = case["cfg"]
+
+    def values(dtype):
+        m = R.gather(case, dtype)
+        net = copy.deepcopy(case["net"]).to(dtype)
+        with torch.no_grad():
+            return torch.cat([net.value(m["norm_obs"]).squeeze(-1), net.value(m["norm_next"]).squeeze(-1)[None]], 0)
+
+    def gae(dtype):
+        m = R.gather(case, dtype)
+        v = d["values"].to(dtype)
+        term = (1.0 - m["discount"]) * (1.0 - m["truncation"])
+        vs, adv = brax_gae(m["truncation"], term, m["reward"] * cfg.reward_scaling, v[:-1], v[-1], cfg.gae_lambda,
+                           cfg.discounting)
+        if cfg.normalize_advantage:
+            adv = (adv - adv.mean()) / (adv.std(unbiased=False) + 1e-8)
+        return vs, adv
+
+    def check(what, got, ref64, ref32):
+        err, e32 = float((got.double() - ref64).abs().max()), float((ref32.double() - ref64).abs().max())
+        scale = float(ref64.abs().max())
+        print(f"{name} {what}: err {err:.3e} torch32 {e32:.3e} scale {scale:.3e}")
+        assert err <= 4 * e32 + 1e-6 * scale, (what, err, e32, scale)
+
+    check("values", d["values"], values(torch.float64), values(torch.float32))
+    (vs64, adv64), (vs32, adv32) = gae(torch.float64), gae(torch.float32)
+    check("vs", d["vs"], vs64, vs32)
+    check("advantages", d["advantages"], adv64, adv32)
+    assert torch.equal(d["noise"], case["z"])
+
+
+def test_philox_noise():
+    b = built("blocks")
+    case, lrn = b["case"], b["lrn"]
+    g0, _, d0 = _run(lrn, case, entropy_noise=None, noise_step=3)
+    g1, _, d1 = _run(lrn, case, entropy_noise=d0["noise"].contiguous())
+    assert all(torch.equal(a, c) for a, c in zip(g0, g1))        # noise_out fed back: the same bits
+    _, _, d2 = _run(lrn, case, entropy_noise=None, noise_step=3)
+    assert torch.equal(d0["noise"], d2["noise"])                  # equal keys, equal z
+    _, _, d3 = _run(lrn, case, entropy_noise=None, noise_step=4)
+    assert not torch.equal(d0["noise"], d3["noise"])
+    z = d0["noise"].double().flatten()
+    n = z.numel()
+    assert n == 4 * 10 * 512
+    assert abs(float(z.mean())) <= 5.0 / np.sqrt(n)
+    assert abs(float(z.var(unbiased=False)) - 1.0) <= 5.0 * np.sqrt(2.0 / n)
+
+
+@pytest.mark.parametrize("name", ["ragged", "rounds"])
+def test_determinism_and_gather(name):
+    b = built(name)
+    case, lrn = b["case"], b["lrn"]
+    g1, st1, _ = _run(lrn, case)
+    assert all(torch.equal(a, c) for a, c in zip(b["g"], g1)) and torch.equal(b["st"], st1)
+    # the minibatch's trajectories physically moved into minibatch order: U' = 1, N' = mb, identity index
+    U, n, L, mb = case["shape"]
+    idx = case["index"]
+    tm = lambda x: x.transpose(1, 2).reshape(U * n, L, *x.shape[3:])[idx].transpose(0, 1).contiguous()[None]
+    bu = case["buffers"]
+    moved = {k: tm(bu[k]) for k in ("obs", "raw", "logp", "rew", "disc", "trunc")}
+    moved["nxt"] = bu["nxt"].reshape(U * n, -1)[idx].contiguous()[None]
+    g2, st2, _ = _run(lrn, case, buffers=moved, index=torch.arange(mb, device=DEV))
+    assert all(torch.equal(a, c) for a, c in zip(b["g"], g2)) and torch.equal(b["st"], st2)
+
+
+def test_argument_checks_leave_everything_untouched():
+    b = built("ragged")
+    case, lrn = b["case"], b["lrn"]
+    L = N.lib()
+    for p in lrn.params:
+        p.grad = torch.full_like(p, 123.0)
+    stats = torch.full((3,), 123.0, device=DEV)
+    prm, bt, grd = lrn.describe(case["buffers"], case["index"], entropy_noise=case["z"], stats=stats)
+    ws = torch.full((lrn._ws.numel(),), 77, dtype=torch.uint8, device=DEV)
+    need = L.quad_brax_ppo_workspace_bytes(bt.mb, bt.L)
+    assert 0 < need <= ws.numel()
+    assert L.quad_brax_ppo_workspace_bytes(0, 5) == 0 and L.quad_brax_ppo_workspace_bytes(4, 65) == 0
+
+    def call(p=prm, bb=bt, g=grd, w=ws.data_ptr(), nbytes=None):
+        return L.quad_brax_ppo_grad(C.byref(p), C.byref(bb), C.byref(g), C.c_void_p(w),
+                                    C.c_int64(ws.numel() if nbytes is None else nbytes), None)
+
+    def changed(struct, **kw):
+        s = type(struct).from_buffer_copy(struct)
+        for k, v in kw.items():
+            setattr(s, k, v)
+        return s
+
+    bad = [call(p=changed(prm, policy_h1=64)), call(p=changed(prm, value_h2=256)),
+           call(p=changed(prm, activation=N.ACTFN_TANH)), call(p=changed(prm, pi_w1=None)),
+           call(p=changed(prm, mean=prm.mean + 2)), call(g=changed(grd, vf_b2=None)),
+           call(g=changed(grd, pi_w0=grd.pi_w0 + 1)), call(bb=changed(bt, obs=None)),
+           call(bb=changed(bt, raw=bt.raw + 4)), call(bb=changed(bt, index=bt.index + 4)),
+           call(bb=changed(bt, index=None)), call(bb=changed(bt, entropy_noise=bt.entropy_noise + 4)),
+           call(bb=changed(bt, mb=0)), call(bb=changed(bt, L=0)), call(bb=changed(bt, L=65)),
+           call(bb=changed(bt, U=0)), call(w=ws.data_ptr() + 4), call(nbytes=need - 1), call(w=None)]
+    torch.cuda.synchronize()
+    assert all(rc == N.QUAD_EINVAL for rc in bad), bad
+    assert all(bool((p.grad == 123.0).all()) for p in lrn.params) and bool((stats == 123.0).all())
+    assert bool((ws == 77).all())
+    assert call() == N.QUAD_OK  # and the unchanged descriptors launch
+    torch.cuda.synchronize()
+    assert all(torch.equal(p.grad, g) for p, g in zip(lrn.params, b["g"]))
+
+
+def test_adam_step_matches_torch_and_keeps_the_state_dict():
+    b = built("rounds")
+    case = b["case"]
+    lrn = _learner(case)
+    twin = copy.deepcopy(lrn.net)
+    topt = torch.optim.Adam(twin.parameters(), lr=case["cfg"].learning_rate, eps=1e-8)
+    for _ in range(2):
+        _run(lrn, case)
+        for p, q in zip(lrn.net.parameters(), twin.parameters()):
+            q.grad = p.grad.clone()
+        lrn.adam_step()
+        topt.step()
+    torch.cuda.synchronize()
+    sa, sb = lrn.opt.state_dict()["state"], topt.state_dict()["state"]
+    # absolute floors where the two steps' terms cancel: after two steps a moment is a sum of three f32-rounded terms
+    # of at most 0.19 max|g| (2e-3 max|g|^2), so two evaluations differ by at most 6 roundings of that: 2^-24 * 6 *
+    # 0.19 < 1e-7 (of max|g|), 2^-24 * 6 * 2e-3 < 1e-9 (of max|g|^2); a parameter moves by lr times a ratio of them
+    for i, (p, q) in enumerate(zip(lrn.net.parameters(), twin.parameters())):
+        gm = float(q.grad.abs().max())
+        torch.testing.assert_close(p, q, rtol=1e-5, atol=1e-9)
+        torch.testing.assert_close(sa[i]["exp_avg"], sb[i]["exp_avg"], rtol=1e-5, atol=1e-7 * gm)
+        torch.testing.assert_close(sa[i]["exp_avg_sq"], sb[i]["exp_avg_sq"], rtol=1e-5, atol=1e-9 * gm * gm)
+        assert float(sa[i]["step"]) == 2.0
+    # the state dict round-trips through a fresh optimizer
+    sd = copy.deepcopy(lrn.opt.state_dict())
+    fresh = torch.optim.Adam(lrn.net.parameters(), lr=1.0, eps=1e-8)
+    fresh.load_state_dict(sd)
+    assert fresh.param_groups[0]["lr"] == case["cfg"].learning_rate
+    for i in range(12):
+        assert torch.equal(fresh.state_dict()["state"][i]["exp_avg"], sa[i]["exp_avg"])
+
+
+@pytest.mark.parametrize("fused_unroll", [False, True], ids=["torch_unroll", "fused_unroll"])
+def test_training_step_runs_with_either_unroll_form(fused_unroll):
+    cfg = BraxPPOConfig(num_envs=64, batch_size=16, num_minibatches=4, unroll_length=5, episode_length=50,
+                        fused_unroll=fused_unroll, fused_update=True)
+    env = QuadVecEnv(64, env="brax_hover", device=DEV, seed=0, max_episode_steps=50)
+    m = BraxPPO(env, cfg, seed=0)
+    before = [p.detach().clone() for p in m.net.parameters()]
+    for _ in range(2):
+        st = m.training_step()
+        assert st.env_steps == 64 * 5 and all(np.isfinite(v) for v in st.losses.values())
+    assert m._update_t == 2 * cfg.num_updates_per_batch * cfg.num_minibatches
+    assert all(bool(torch.isfinite(p).all()) and not torch.equal(p, q) for p, q in zip(m.net.parameters(), before))
+    env.close()
+
+
+@pytest.mark.parametrize("bad", [dict(policy_hidden_sizes=(64, 64)), dict(value_hidden_sizes=(128, 128, 128))],
+                         ids=["narrow_policy", "three_layer_value"])
+def test_construction_outside_the_family_raises(bad):
+    cfg = BraxPPOConfig(num_envs=64, batch_size=16, num_minibatches=4, unroll_length=5, fused_update=True, **bad)
+    env = QuadVecEnv(64, env="brax_hover", device=DEV, seed=0, max_episode_steps=50)
+    with pytest.raises(ValueError, match=r"hidden sizes \(128, 128\) and relu"):
+        BraxPPO(env, cfg, seed=0)
+    env.close()
+
+
+def test_brax_profile_ppo_learns_with_both_flags_and_the_driver_records_them(tmp_path, capsys):
+    """test_brax_profile_ppo_learns_with_fused_unrolls_and_the_driver_records_the_flag's configuration and
+    criterion with fused_update on as well; then train_brax --fused-unroll --fused-update at that test's CLI shape."""
+    from uav_reinforcement_learning_control_amd import train_brax
+    from uav_reinforcement_learning_control_amd.export import load_brax_params
+    cfg = BraxPPOConfig(num_envs=2048, batch_size=512, num_minibatches=8, episode_length=200, fused_unroll=True,
+                        fused_update=True)
+    env = QuadVecEnv(2048, env="brax_jax_mjx", device=DEV, seed=0, max_episode_steps=200)
+    m = BraxPPO(env, cfg, seed=0)
+    curve = []
+    for it in range(40):
+        st = m.training_step()
+        assert st.env_steps == 512 * 10 * 8
+        assert all(np.isfinite(v) for v in st.losses.values())
+        curve.append(st.mean_episode_reward)
+    assert m._update_t == 40 * 4 * 8
+    fin = [c for c in curve if np.isfinite(c)]
+    print("brax-profile episode reward, fused unrolls and update", [round(c, 2) for c in fin][::4])
+    assert np.mean(fin[-5:]) > np.mean(fin[:5])
+    env.close()
+    capsys.readouterr()
+    train_brax.main(["--env", "jax_mjx_quad", "--num-envs", "1024", "--batch-size", "256", "--num-minibatches", "8",
+                     "--num-timesteps", "60000", "--checkpoint-interval", "20000", "--output-dir", str(tmp_path),
+                     "--fused-unroll", "--fused-update"])
+    text = capsys.readouterr().out
+    assert "update: fused minibatch gradient" in text
+    (run,) = os.listdir(tmp_path)
+    summ = json.load(open(tmp_path / run / "training_summary.json"))
+    assert summ["fused_update"] is True and summ["fused_unroll"] is True
+    norm, pol, val = load_brax_params(summ["params_path"])
+    assert norm["count"] > 0 and val["params"]["hidden_2"]["kernel"].shape == (128, 1)

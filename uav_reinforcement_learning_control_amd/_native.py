@@ -191,6 +191,31 @@ class QuadBraxRun(C.Structure):
                 ("trace_target", C.c_void_p)]
 
 
+class QuadBraxPPOParams(C.Structure):
+    """quad_brax_ppo_grad's nets: flax [in, out] kernels and biases, the normaliser, the checked arch."""
+    _fields_ = [(n, C.c_void_p) for n in ("pi_w0", "pi_b0", "pi_w1", "pi_b1", "pi_w2", "pi_b2",
+                                          "vf_w0", "vf_b0", "vf_w1", "vf_b1", "vf_w2", "vf_b2", "mean", "std")] + \
+               [("min_std", C.c_float)] + \
+               [(n, C.c_int32) for n in ("policy_h1", "policy_h2", "value_h1", "value_h2", "activation")]
+
+
+class QuadBraxPPOGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pi_w0", "pi_b0", "pi_w1", "pi_b1", "pi_w2", "pi_b2",
+                                          "vf_w0", "vf_b0", "vf_w1", "vf_b1", "vf_w2", "vf_b2")]
+
+
+class QuadBraxPPOBatch(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "next_obs", "raw", "log_prob", "reward", "discount", "truncation",
+                                          "index", "entropy_noise", "noise_out", "values", "vs", "advantages",
+                                          "stats")] + \
+               [(n, C.c_int32) for n in ("U", "L", "N", "mb")] + \
+               [(n, C.c_float) for n in ("clipping_epsilon", "entropy_cost", "discounting", "gae_lambda",
+                                         "reward_scaling")] + \
+               [("normalize_advantage", C.c_int32), ("noise_step", C.c_uint32), ("seed", C.c_uint64)]
+
+
+BRAX_PPO_HIDDEN, BRAX_PPO_MAX_L = (128, 128), 64  # quad_brax_ppo_grad's family
+
 POLICY_STAT_SLOTS = 1024
 
 
@@ -234,7 +259,7 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_actor_packed_floats", "quad_actor_pack", "quad_actor_act", "quad_actor_episode",
            "quad_actor_waypoints",
            "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode",
-           "quad_brax_actor_sample", "quad_brax_unroll")
+           "quad_brax_actor_sample", "quad_brax_unroll", "quad_brax_ppo_workspace_bytes", "quad_brax_ppo_grad")
 
 
 class QuadRollout(C.Structure):
@@ -383,6 +408,13 @@ def _declare(L):
     L.quad_brax_unroll.argtypes = [vp, barch, vp, C.POINTER(QuadBraxUnroll), vp]
     for n in ("quad_brax_actor_sample", "quad_brax_unroll"):
         getattr(L, n).restype = C.c_int
+    if not hasattr(L, "quad_brax_ppo_grad"):  # nor with the learner's gradient entry points
+        raise QuadError(f"{LIB_PATH} was built before the Brax gradient's entry points (quad_brax_ppo_grad); rebuild it")
+    L.quad_brax_ppo_workspace_bytes.argtypes = [i32, i32]
+    L.quad_brax_ppo_workspace_bytes.restype = C.c_int64
+    L.quad_brax_ppo_grad.argtypes = [C.POINTER(QuadBraxPPOParams), C.POINTER(QuadBraxPPOBatch),
+                                     C.POINTER(QuadBraxPPOGrads), vp, C.c_int64, vp]
+    L.quad_brax_ppo_grad.restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
     L.quad_pop_detach_eval.argtypes = [vp]

@@ -62,6 +62,9 @@ class BraxPPOConfig:
     # collect the unrolls in one launch per training step (FusedBraxActor.unroll: Philox noise) instead of the torch
     # per-step loop (torch.Generator noise): another sample path of the same algorithm
     fused_unroll: bool = False
+    # compute each minibatch gradient in fused launches (FusedBraxLearner: quad_brax_ppo_grad + quad_clip_adam, Philox
+    # entropy noise) instead of torch autograd (torch.Generator noise): another sample path of the same algorithm
+    fused_update: bool = False
 
 
 _ACT = {"relu": F.relu, "tanh": torch.tanh, "silu": F.silu}
@@ -266,6 +269,9 @@ class BraxPPO:
             if not brax_unroll_supported(c.policy_hidden_sizes, c.activation, env):
                 raise ValueError("fused_unroll=True needs a brax env kind (brax_hover / brax_jax_mjx) with auto-reset "
                                  "and a policy the one-launch unroll is chosen for (ppo.fused.brax_unroll_supported)")
+        if c.fused_update:
+            from .fused import brax_update_family
+            brax_update_family(c)  # ValueError naming the family
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)
         self.net = BraxActorCritic(env.obs_dim, 4, c).to(self.device)
@@ -280,6 +286,11 @@ class BraxPPO:
         self._flat = torch.zeros(sum(p.numel() for p in self.net.parameters()), device=self.device)
         from .ppo import bind_grad_bucket
         bind_grad_bucket(list(self.net.parameters()), self._flat)  # in-place all-reduce
+        self._learner = None     # FusedBraxLearner of self.net (fused_update)
+        self._update_t = 0       # noise step of the next fused minibatch step: advances once per step, never reset
+        if c.fused_update:
+            from .fused import FusedBraxLearner
+            self._learner = FusedBraxLearner(self.net, self.norm, c, opt=self.opt, seed=self.seed)
 
     @torch.no_grad()
     def _unrolls_fused(self):
@@ -344,6 +355,8 @@ class BraxPPO:
         obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum = self._unrolls()
         U, L, N = obs.shape[:3]
         self.norm.update(obs)  # acme running statistics, after the unrolls
+        if c.fused_update:
+            return self._update_fused(t0, obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum)
         # trajectories [M = U * N, L, ...] -> time-major per minibatch
         tr = lambda x: x.transpose(1, 2).reshape(U * N, L, *x.shape[3:])
         obs_m, raw_m, logp_m, rew_m, disc_m, trunc_m = map(tr, (obs, raw, logp, rew, disc, trunc))
@@ -368,8 +381,35 @@ class BraxPPO:
                 self.opt.step()
                 acc += torch.stack([pl.detach(), vl.detach(), el.detach()]).double()
                 nsteps += 1
+        return self._step_stats(t0, U * L * N, acc, nsteps, finished, ret_sum)
+
+    def _update_fused(self, t0, obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum) -> BraxStepStats:
+        """training_step's update with fused_update: the same statistics update and permutations; each minibatch
+        step is FusedBraxLearner.grads on a slice of the pass's permutation (gathered from the time-major buffers,
+        no transposed copies), the all-reduce when world > 1, and adam_step."""
+        c = self.cfg
+        U, L, N = obs.shape[:3]
+        M = U * N
+        mb = M // c.num_minibatches
+        bufs = dict(obs=obs, nxt=nxt, raw=raw, logp=logp, rew=rew, disc=disc, trunc=trunc)
+        acc = torch.zeros(3, dtype=torch.float64, device=self.device)
+        st = torch.zeros(3, dtype=torch.float32, device=self.device)
+        nsteps = 0
+        for _ in range(c.num_updates_per_batch):
+            perm = torch.randperm(M, device=self.device, generator=self.gen)
+            for k in range(c.num_minibatches):
+                self._learner.grads(bufs, perm[k * mb:(k + 1) * mb], noise_step=self._update_t, stats=st)
+                self._update_t += 1
+                if self.world > 1:
+                    from .ppo import allreduce_mean_
+                    allreduce_mean_(list(self.net.parameters()), self._flat, self.world)
+                self._learner.adam_step()
+                acc += st.double()
+                nsteps += 1
+        return self._step_stats(t0, U * L * N, acc, nsteps, finished, ret_sum)
+
+    def _step_stats(self, t0, steps, acc, nsteps, finished, ret_sum) -> BraxStepStats:
         torch.cuda.synchronize(self.device)
-        steps = U * L * N
         self.num_timesteps += steps * self.world
         a = (acc / max(nsteps, 1)).tolist()
         n_fin, r_sum = int(finished.item()), float(ret_sum.item())

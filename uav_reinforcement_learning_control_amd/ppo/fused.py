@@ -11,7 +11,8 @@ statistics) -- instead of ~25 torch kernels. The torch ActorCritic stays the tra
 other supported architecture (quad_actor_*: 12-H1-H2-4, ReLU or tanh) for evaluation episodes and waypoint laps;
 `fused_actor_for(policy)` picks between the two. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
 21-H1-H2-8 behind the running statistics, ReLU / tanh / SiLU, NormalTanh sampling) for evaluation episodes of the
-brax env kinds and for the learner's unrolls (sample, unroll).
+brax env kinds and for the learner's unrolls (sample, unroll). `FusedBraxLearner` is the Brax profile's minibatch
+gradient and Adam step (quad_brax_ppo_grad, quad_clip_adam) for (128, 128) ReLU policy and value nets.
 """
 from __future__ import annotations
 
@@ -531,3 +532,138 @@ class FusedBraxActor:
         v = lambda k, *tail: buf[k].view(U, L, n, *tail)
         return dict(obs=v("obs", N.BRAX_OBS), nxt=buf["next_obs"], raw=v("raw", 4), logp=v("log_prob"),
                     rew=v("reward"), disc=v("discount"), trunc=v("truncation"), finished=tot[1], ret_sum=tot[0])
+
+
+# (num_envs, num_minibatches, unroll_length) for which the fused update did not beat the torch update in
+# profiles/brax_update/bench.json (by 19's to 21's rule): it won every measured row
+BRAX_UPDATE_KEEP_TORCH = frozenset()
+
+_BRAX_UPDATE_FAMILY = ("the fused Brax update (quad_brax_ppo_grad) trains policy and value nets with hidden sizes "
+                       f"{N.BRAX_PPO_HIDDEN} and relu, unroll_length in [1, {N.BRAX_PPO_MAX_L}]")
+
+
+def brax_update_family(cfg) -> None:
+    """ValueError naming the family unless cfg's nets and unroll length are quad_brax_ppo_grad's."""
+    sizes = (tuple(int(x) for x in cfg.policy_hidden_sizes), tuple(int(x) for x in cfg.value_hidden_sizes))
+    if (sizes != (N.BRAX_PPO_HIDDEN, N.BRAX_PPO_HIDDEN) or cfg.activation != "relu"
+            or not 1 <= int(cfg.unroll_length) <= N.BRAX_PPO_MAX_L):
+        raise ValueError(f"{_BRAX_UPDATE_FAMILY}, got policy {sizes[0]}, value {sizes[1]}, {cfg.activation!r}, "
+                         f"unroll_length {cfg.unroll_length}")
+
+
+def brax_update_supported(cfg, env=None) -> bool:
+    """The fused update where its family holds and it did not lose to the torch update (BRAX_UPDATE_KEEP_TORCH)."""
+    try:
+        brax_update_family(cfg)
+    except (ValueError, TypeError, AttributeError):
+        return False
+    if env is not None and getattr(env, "device", torch.device("cpu")).type != "cuda":
+        return False
+    return (int(cfg.num_envs), int(cfg.num_minibatches), int(cfg.unroll_length)) not in BRAX_UPDATE_KEEP_TORCH
+
+
+class FusedBraxLearner:
+    """The gradient of ppo/brax_ppo.py brax_ppo_loss in four launches (csrc/brax_learner.hip, quad_brax_ppo_grad) and
+    the Adam step in two (quad_clip_adam), bound to a BraxActorCritic, its RunningStats and a BraxPPOConfig.
+
+    grads() gathers a minibatch of trajectories straight from the time-major unroll buffers and overwrites the
+    parameters' .grad tensors; adam_step() updates the parameters through the state tensors of `opt` (the learner's
+    own torch.optim.Adam), so opt.state_dict() and checkpoints stay what they are."""
+
+    def __init__(self, net, norm, cfg, opt: Optional[torch.optim.Adam] = None, seed: int = 0):
+        brax_update_family(cfg)
+        self.net, self.norm, self.cfg, self.opt, self.seed = net, norm, cfg, opt, int(seed)
+        self.params = [*net.policy.kernels, *net.policy.biases, *net.value.kernels, *net.value.biases]
+        shapes = [tuple(p.shape) for p in self.params]
+        h = N.BRAX_PPO_HIDDEN[0]
+        want = [(N.BRAX_OBS, h), (h, h), (h, N.BRAX_LOGITS), (h,), (h,), (N.BRAX_LOGITS,),
+                (N.BRAX_OBS, h), (h, h), (h, 1), (h,), (h,), (1,)]
+        if shapes != want:
+            raise ValueError(f"{_BRAX_UPDATE_FAMILY} on 21-D observations and 4-D actions, got {shapes}")
+        self.device = self.params[0].device
+        if self.device.type != "cuda":
+            raise N.QuadError("FusedBraxLearner needs the nets on a ROCm GPU")
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("parameters must be contiguous float32")
+        self._ws = None
+        self._adam = None
+
+    _stream = FusedPolicy._stream
+
+    def _ordered(self, ts):
+        """[k0, k1, k2, b0, b1, b2] of each net -> w0, b0, w1, b1, w2, b2 of the policy, then of the value net."""
+        return [ts[6 * n + 3 * j + i] for n in range(2) for i in range(3) for j in range(2)]
+
+    def grads(self, buffers: dict, index: torch.Tensor, *, entropy_noise: Optional[torch.Tensor] = None,
+              noise_step: int = 0, stats: Optional[torch.Tensor] = None, diag: Optional[dict] = None) -> None:
+        """quad_brax_ppo_grad on the minibatch of trajectories `index` ([mb] int64, each in [0, U * N)) of `buffers`:
+        obs [U, L, N, 21], nxt [U, N, 21], raw [U, L, N, 4], logp, rew, disc, trunc [U, L, N] (FusedBraxActor.unroll's
+        and BraxPPO._unrolls' tensors). entropy_noise [L, mb, 4] is the entropy sample's z; None draws it from
+        Philox(seed; trajectory, noise_step * L + t). stats [3] receives policy_loss, v_loss, entropy_loss. diag, a
+        dict, receives "values" [L + 1, mb], "vs", "advantages" [L, mb] and "noise" [L, mb, 4]. The gradients
+        overwrite the parameters' .grad (created when absent)."""
+        prm, b, grd = self.describe(buffers, index, entropy_noise=entropy_noise, noise_step=noise_step, stats=stats,
+                                    diag=diag)
+        N.check(N.lib().quad_brax_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), _p(self._ws),
+                                           C.c_int64(self._ws.numel()), self._stream()), "quad_brax_ppo_grad")
+
+    def describe(self, buffers: dict, index: torch.Tensor, *, entropy_noise=None, noise_step: int = 0, stats=None,
+                 diag: Optional[dict] = None):
+        """grads' checked arguments as (QuadBraxPPOParams, QuadBraxPPOBatch, QuadBraxPPOGrads); sizes self._ws."""
+        dev, f32, c = self.device, torch.float32, self.cfg
+        obs = buffers["obs"]
+        U, L, n = (int(x) for x in obs.shape[:3])
+        mb = int(index.shape[0])
+        for k, shp in (("obs", (U, L, n, N.BRAX_OBS)), ("nxt", (U, n, N.BRAX_OBS)), ("raw", (U, L, n, 4)),
+                       ("logp", (U, L, n)), ("rew", (U, L, n)), ("disc", (U, L, n)), ("trunc", (U, L, n))):
+            _need(buffers[k], shp, f32, dev, k)
+        _need(index, (mb,), torch.int64, dev, "index")
+        if entropy_noise is not None:
+            _need(entropy_noise, (L, mb, 4), f32, dev, "entropy_noise")
+        if stats is not None:
+            _need(stats, (3,), f32, dev, "stats")
+        out = {}
+        if diag is not None:
+            e = lambda *s: torch.empty(*s, dtype=f32, device=dev)
+            out = dict(values=e(L + 1, mb), vs=e(L, mb), advantages=e(L, mb), noise=e(L, mb, 4))
+            diag.update(out)
+        for p in self.params:
+            if p.grad is None:
+                p.grad = torch.empty_like(p)
+            elif not p.grad.is_contiguous():
+                raise ValueError("every parameter needs a contiguous .grad")
+        mean, std = self.norm.mean, self.norm.std
+        _need(mean, (N.BRAX_OBS,), f32, dev, "mean")
+        _need(std, (N.BRAX_OBS,), f32, dev, "std")
+        L_ = N.lib()
+        need = int(L_.quad_brax_ppo_workspace_bytes(mb, L))
+        if self._ws is None or self._ws.numel() < max(need, 16):
+            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        h = N.BRAX_PPO_HIDDEN
+        prm = N.QuadBraxPPOParams(*[p.data_ptr() for p in self._ordered(self.params)], mean.data_ptr(),
+                                  std.data_ptr(), float(self.net.dist.min_std), h[0], h[1], h[0], h[1],
+                                  N.BRAX_ACTFNS[c.activation])
+        grd = N.QuadBraxPPOGrads(*[p.grad.data_ptr() for p in self._ordered(self.params)])
+        b = N.QuadBraxPPOBatch(
+            obs=obs.data_ptr(), next_obs=buffers["nxt"].data_ptr(), raw=buffers["raw"].data_ptr(),
+            log_prob=buffers["logp"].data_ptr(), reward=buffers["rew"].data_ptr(),
+            discount=buffers["disc"].data_ptr(), truncation=buffers["trunc"].data_ptr(), index=index.data_ptr(),
+            entropy_noise=_p(entropy_noise), noise_out=_p(out.get("noise")), values=_p(out.get("values")),
+            vs=_p(out.get("vs")), advantages=_p(out.get("advantages")), stats=_p(stats), U=U, L=L, N=n, mb=mb,
+            clipping_epsilon=float(c.clipping_epsilon), entropy_cost=float(c.entropy_cost),
+            discounting=float(c.discounting), gae_lambda=float(c.gae_lambda), reward_scaling=float(c.reward_scaling),
+            normalize_advantage=int(bool(c.normalize_advantage)), noise_step=int(noise_step) & 0xFFFFFFFF,
+            seed=self.seed & (2**64 - 1))
+        b._keep = (mean, std, entropy_noise, stats, out)  # the launches read them: alive as long as the descriptor
+        return prm, b, grd
+
+    def adam_step(self) -> None:
+        """opt.step() of the learner's Adam (optax defaults: no clipping, eps 1e-8) as quad_clip_adam on the
+        optimizer's own state tensors."""
+        if self.opt is None:
+            raise ValueError("FusedBraxLearner.adam_step needs the optimizer (opt=...)")
+        if self._adam is None:
+            from .learner import FusedAdam
+            self._adam = FusedAdam(self.opt, 0.0)
+        self._adam.step()

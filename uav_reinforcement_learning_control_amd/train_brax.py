@@ -6,7 +6,8 @@ Same arguments and defaults as train_brax_ppo.py where they apply (the JAX/MJX-s
 --impl, --backend and Orbax checkpoints have no counterpart here). --num-evals K runs brax's in-training
 evaluation (K evaluations evenly spaced over the run on a separate eval env, BraxPPO.evaluate: one launch per
 evaluation); its default here is 0, so a run without the flag prints and writes what it always did. --fused-unroll
-collects each training step's unrolls in one launch (ppo/fused.py FusedBraxActor.unroll), off by default. Outputs mirror the
+collects each training step's unrolls in one launch (ppo/fused.py FusedBraxActor.unroll), off by default;
+--fused-update computes each minibatch gradient in fused launches (ppo/fused.py FusedBraxLearner), off by default. Outputs mirror the
 reference's run directory: <output-dir>/<timestamp>/ppo_params.msgpack (brax model.save_params
 format, ppo/brax_ppo.py + export.save_brax_params), checkpoints/params_step_<n>.msgpack every
 --checkpoint-interval steps, and training_summary.json.
@@ -93,6 +94,10 @@ def parse(argv=None):
                     help="collect each training step's unrolls in one launch (Philox action noise) instead of the\n"
                          "torch per-step loop; needs a two-hidden-layer policy of the MFMA family. Off by default:\n"
                          "the output of a run without the flag is unchanged")
+    ap.add_argument("--fused-update", action="store_true",
+                    help="compute each minibatch gradient in four fused launches (quad_brax_ppo_grad, Philox entropy\n"
+                         "noise) and step Adam with quad_clip_adam instead of torch autograd; needs (128, 128) ReLU\n"
+                         "policy and value nets. Off by default: the output of a run without the flag is unchanged")
     return ap.parse_args(argv)
 
 
@@ -110,7 +115,7 @@ def main(argv=None):
                         num_updates_per_batch=a.num_updates_per_batch, gae_lambda=a.gae_lambda,
                         reward_scaling=a.reward_scaling, policy_hidden_sizes=_sizes(a.policy_hidden_sizes),
                         value_hidden_sizes=_sizes(a.value_hidden_sizes), activation=a.activation,
-                        fused_unroll=a.fused_unroll)
+                        fused_unroll=a.fused_unroll, fused_update=a.fused_update)
     kind = {"hover": "brax_hover", "jax_mjx_quad": "brax_jax_mjx"}[a.env]
     env = QuadVecEnv(a.num_envs, env=kind, device=f"cuda:{local}", seed=a.seed, env_id_base=rank * a.num_envs,
                      max_episode_steps=a.episode_length, cfg_overrides={"traj_duration": a.traj_duration_seconds})
@@ -124,6 +129,9 @@ def main(argv=None):
     if a.fused_unroll and rank == 0:
         print(f"unrolls: one launch per training step ({model.num_unrolls} x {cfg.unroll_length} steps, "
               f"quad_brax_unroll)", flush=True)
+    if a.fused_update and rank == 0:
+        print(f"update: fused minibatch gradient ({cfg.num_updates_per_batch} x {cfg.num_minibatches} steps of "
+              f"quad_brax_ppo_grad + quad_clip_adam per training step)", flush=True)
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     run = os.path.abspath(os.path.join(a.output_dir, stamp))
     ckdir = os.path.join(run, "checkpoints")
@@ -177,6 +185,8 @@ def main(argv=None):
                    "params_path": params_path}
         if a.fused_unroll:
             summary["fused_unroll"] = True
+        if a.fused_update:
+            summary["fused_update"] = True
         if a.num_evals > 0:
             summary["num_evals"] = a.num_evals
             summary["final_metrics"]["eval/episode_reward"] = eval_reward
