@@ -160,7 +160,7 @@ def test_argument_checks_leave_everything_untouched():
         p.grad = torch.full_like(p, 123.0)
     stats = torch.full((3,), 123.0, device=DEV)
     prm, bt, grd = lrn.describe(case["buffers"], case["index"], entropy_noise=case["z"], stats=stats)
-    ws = torch.full((lrn._ws.numel(),), 77, dtype=torch.uint8, device=DEV)
+    ws = torch.full((lrn._ws.nbytes,), 77, dtype=torch.uint8, device=DEV)
     need = L.quad_brax_ppo_workspace_bytes(bt.mb, bt.L)
     assert 0 < need <= ws.numel()
     assert L.quad_brax_ppo_workspace_bytes(0, 5) == 0 and L.quad_brax_ppo_workspace_bytes(4, 65) == 0

@@ -406,6 +406,90 @@ def test_graph_update_recaptures_on_resumed_state_and_new_lr():
         assert torch.equal(a, b)
 
 
+def _graph_twins(monkeypatch, between=None, iters=3):
+    """Two PPO twins (graph_update True, then False; 8 hover envs with RateControlWrapper, 64 steps in
+    minibatches of 128, 2 epochs: 4 optimizer steps per epoch) run `iters` iterations from the same seeds,
+    with between(algo) called on both after iteration 1. Asserts that the parameters and Adam's exp_avg /
+    exp_avg_sq / step end as the same bits and returns the graph twin's captured hipGraph object after each
+    iteration (the objects, so that identity is not confused by a reused id)."""
+    from uav_reinforcement_learning_control_amd.envs import QuadVecEnv
+    from uav_reinforcement_learning_control_amd.ppo.ppo import PPO, PPOConfig
+    outs, graphs = [], []
+    for graph in (True, False):
+        for var in ("QUADENV_LEARNER", "QUADENV_LEARNER_SPLIT"):
+            monkeypatch.delenv(var, raising=False)
+        env = QuadVecEnv(8, env="hover", wrapper="RateControlWrapper", device="cuda:0", seed=3)
+        algo = PPO(env, PPOConfig(n_steps=64, batch_size=128, n_epochs=2, graph_update=graph), seed=11)
+        assert algo.n_minibatches_per_epoch() == 4
+        torch.manual_seed(5)
+        for it in range(iters):
+            algo.collect_rollouts()
+            assert algo.train()["n"] == 8
+            assert (algo._epoch_graph is not None) == graph
+            if graph:
+                graphs.append(algo._epoch_graph.graph)
+            if it == 0 and between is not None:
+                between(algo)
+        st = algo.opt.state
+        outs.append([p.detach().clone() for p in algo.policy.parameters()] +
+                    [st[p][k].clone() for p in algo.policy.parameters() for k in ("exp_avg", "exp_avg_sq", "step")])
+        env.close()
+    for a, b in zip(*outs):
+        assert torch.equal(a, b)
+    return graphs
+
+
+def test_graph_update_keeps_its_graph_in_steady_state(monkeypatch):
+    """Nothing changes between three iterations: the graph captured in iteration 1 is replayed in 2 and 3 (the
+    workspaces are reserved before the key is taken, so the first eager epoch does not invalidate it)."""
+    g = _graph_twins(monkeypatch)
+    assert g[0] is g[1] is g[2]
+
+
+def test_graph_update_recaptures_when_the_workspace_moved(monkeypatch):
+    """The captured launches hold the gradient workspace's pointer. A grads() call on a larger minibatch between
+    two train() calls replaces the workspace (here: 1,024 rows of other buffers); the graph must be recaptured,
+    not replayed into the freed allocation, and the update stays the eager loop's bits."""
+    from uav_reinforcement_learning_control_amd import _native as N
+    big = 1024
+    assert N.lib().quad_ppo_workspace_bytes(big) > N.lib().quad_ppo_workspace_bytes(128)
+    pol = _policy(31)
+    bufs = _buffers(pol, 2048, 31, 0.2)
+    idx = torch.randperm(2048, generator=torch.Generator().manual_seed(1)).cuda()[:big].contiguous()
+
+    def between(algo):
+        ws = algo._learner._ws
+        before = (ws.ptr, ws.nbytes)
+        algo._learner.grads(*bufs, idx)
+        assert ws.ptr != before[0] and ws.nbytes > before[1]  # the precondition: the workspace moved
+    g = _graph_twins(monkeypatch, between)
+    assert g[1] is not g[0] and g[2] is g[1]
+
+
+def test_graph_update_recaptures_on_new_loss_coefficients(monkeypatch):
+    """clip_range, ent_coef and vf_coef are kernel arguments of the captured quad_ppo_grad launches."""
+    def between(algo):
+        algo._learner.clip_range *= 0.5
+        algo._learner.ent_coef = 0.01
+    g = _graph_twins(monkeypatch, between)
+    assert g[1] is not g[0] and g[2] is g[1]
+
+
+@pytest.mark.parametrize("var,value", [("QUADENV_LEARNER", "f32"), ("QUADENV_LEARNER_SPLIT", "1")])
+def test_graph_update_recaptures_on_new_gradient_form(monkeypatch, var, value):
+    """The library reads QUADENV_LEARNER and QUADENV_LEARNER_SPLIT on every call, so the eager loop follows a
+    change between two train() calls; the graph path must recapture to follow it too."""
+    from uav_reinforcement_learning_control_amd import _native as N
+    forms = []
+
+    def between(algo):
+        monkeypatch.setenv(var, value)
+        forms.append(N.lib().quad_ppo_grad_form())
+    g = _graph_twins(monkeypatch, between)
+    assert forms == [0 if var == "QUADENV_LEARNER" else 1] * 2
+    assert g[1] is not g[0] and g[2] is g[1]
+
+
 @pytest.mark.parametrize("max_norm", [0.5, 1e9, 0.0])
 def test_fused_clip_adam_matches_torch(max_norm):
     """quad_clip_adam (clip_grad_norm_ + Adam.step) vs torch's on identical gradients, 4 steps, on

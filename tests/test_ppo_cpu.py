@@ -183,3 +183,86 @@ def test_minibatch_partition_is_sb3s():
         assert n_minibatches(total, batch) == len(starts), (total, batch)
         sizes = [min(total, s + batch) - s for s in starts]
         assert sum(sizes) == total
+
+
+class _RecLearner:
+    """A stand-in for FusedLearner that records what fused_epoch asks of it."""
+
+    def __init__(self, normalize_advantage, log):
+        self.normalize_advantage, self.log = normalize_advantage, log
+
+    def adv_stats_epoch(self, adv, perm, batch, n, out=None):
+        assert self.normalize_advantage
+        sums = torch.arange(n * 4, dtype=torch.float64).reshape(n, 4) + 100.0 * len(self.log)
+        self.log.append(("stats", adv, perm, batch, n, out, sums))
+        return sums
+
+    def grads(self, obs, act, logp_old, adv, ret, idx, stats, adv_sums=None):
+        self.log.append(("grads", (obs, act, logp_old, adv, ret), idx.clone(), stats, adv_sums))
+
+
+class _RecAdam:
+    def __init__(self, log):
+        self.log = log
+
+    def step(self):
+        self.log.append(("step",))
+
+
+@pytest.mark.parametrize("normalize", [True, False])
+@pytest.mark.parametrize("epochs", [2, 3])
+def test_fused_update_issues_the_epoch_sequence(monkeypatch, normalize, epochs):
+    """fused_update / fused_epoch on recording stand-ins: 320 rows in minibatches of 128 are two full
+    minibatches and a short one of 64 rows per epoch; max_minibatches = 5 ends the update after the
+    second minibatch of epoch 1. Each epoch that runs draws one permutation (a third epoch draws none);
+    with normalization its two full minibatches' statistics come from one adv_stats_epoch call and
+    minibatch m gets row m, the short one None (grads' own pre-pass); without it there is no such call
+    and no row anywhere. Every grads is followed by `reduce` and one adam.step, five steps in all."""
+    from uav_reinforcement_learning_control_amd.ppo import ppo as P
+    total, B, max_minibatches = 320, 128, 5
+    nmb = P.n_minibatches(total, B)
+    assert nmb == 3
+    steps = min(epochs * nmb, max_minibatches)
+    bufs = tuple(torch.randn(total, w).squeeze(-1) for w in (12, 4, 1, 1, 1))
+    perms, log = [], []
+
+    def draw(n, device):
+        perms.append(torch.randperm(n, generator=torch.Generator().manual_seed(len(perms))))
+        return perms[-1]
+    monkeypatch.setattr(P, "epoch_permutation", draw)
+    mstats = torch.zeros(steps, 4)
+    P.fused_update(_RecLearner(normalize, log), _RecAdam(log), bufs, B, steps, mstats, lambda: log.append(("reduce",)))
+    assert len(perms) == 2
+    want = []
+    k = 0
+    for e in range(2):
+        left = steps - e * nmb
+        if normalize:
+            want.append("stats")
+        want += ["grads", "reduce", "step"] * min(nmb, left)
+    assert [r[0] for r in log] == want
+    assert sum(r[0] == "step" for r in log) == 5
+    sums = None
+    for r in log:
+        if r[0] == "stats":
+            e = k // nmb
+            _, adv, perm, batch, n, out, sums = r
+            assert adv is bufs[3] and perm is perms[e] and (batch, n, out) == (B, 2, None)
+        elif r[0] == "grads":
+            e, m = divmod(k, nmb)
+            _, got, idx, st, row = r
+            assert all(a is b for a, b in zip(got, bufs))
+            assert torch.equal(idx, perms[e][m * B:min(total, (m + 1) * B)]) and idx.numel() == (128, 128, 64)[m]
+            assert st.data_ptr() == mstats[k].data_ptr() and st.shape == (4,)
+            if normalize and m < 2:
+                assert row.data_ptr() == sums[m].data_ptr() and torch.equal(row, sums[m])
+            else:
+                assert row is None
+            k += 1
+    assert k == 5
+    # one captured epoch (a persistent sums buffer, no limit, no all-reduce): the buffer is handed through
+    log.clear()
+    buf = torch.zeros(2, 4, dtype=torch.float64)
+    P.fused_epoch(_RecLearner(normalize, log), _RecAdam(log), bufs, B, perms[0], buf, torch.zeros(nmb, 4))
+    assert [r[0] for r in log] == (["stats"] if normalize else []) + ["grads", "step"] * nmb
+    assert not normalize or log[0][5] is buf

@@ -350,61 +350,51 @@ class BraxPPO:
         return obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum
 
     def training_step(self) -> BraxStepStats:
+        """Unrolls, the statistics update, then num_updates_per_batch passes over a fresh permutation of the
+        trajectories in num_minibatches minibatches. A minibatch step is the gradient (autograd of brax_ppo_loss, or
+        with fused_update FusedBraxLearner.grads: no transposed copies), the all-reduce when world > 1, Adam's step."""
         c = self.cfg
         t0 = time.perf_counter()
         obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum = self._unrolls()
         U, L, N = obs.shape[:3]
         self.norm.update(obs)  # acme running statistics, after the unrolls
-        if c.fused_update:
-            return self._update_fused(t0, obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum)
-        # trajectories [M = U * N, L, ...] -> time-major per minibatch
-        tr = lambda x: x.transpose(1, 2).reshape(U * N, L, *x.shape[3:])
-        obs_m, raw_m, logp_m, rew_m, disc_m, trunc_m = map(tr, (obs, raw, logp, rew, disc, trunc))
-        nxt_m = nxt.reshape(U * N, -1)
         M = U * N
         mb = M // c.num_minibatches
-        acc = torch.zeros(3, dtype=torch.float64, device=self.device)
-        nsteps = 0
-        for _ in range(c.num_updates_per_batch):
-            perm = torch.randperm(M, device=self.device, generator=self.gen)
-            for k in range(c.num_minibatches):
-                idx = perm[k * mb:(k + 1) * mb]
+        if c.fused_update:
+            bufs = dict(obs=obs, nxt=nxt, raw=raw, logp=logp, rew=rew, disc=disc, trunc=trunc)
+            st = torch.zeros(3, dtype=torch.float32, device=self.device)
+            apply = self._learner.adam_step
+
+            def grad(idx):
+                self._learner.grads(bufs, idx, noise_step=self._update_t, stats=st)
+                self._update_t += 1
+                return st
+        else:
+            # trajectories [M = U * N, L, ...] -> time-major per minibatch
+            tr = lambda x: x.transpose(1, 2).reshape(M, L, *x.shape[3:])
+            obs_m, raw_m, logp_m, rew_m, disc_m, trunc_m = map(tr, (obs, raw, logp, rew, disc, trunc))
+            nxt_m = nxt.reshape(M, -1)
+            apply = self.opt.step
+
+            def grad(idx):
                 T = lambda x: x[idx].transpose(0, 1)
-                loss, pl, vl, el = brax_ppo_loss(
+                loss, *parts = brax_ppo_loss(
                     self.net, self.norm.normalize(T(obs_m)), self.norm.normalize(nxt_m[idx]), T(raw_m),
                     T(logp_m), T(rew_m), T(disc_m), T(trunc_m), c, self.gen)
                 self.opt.zero_grad(set_to_none=False)
                 loss.backward()
-                if self.world > 1:
-                    from .ppo import allreduce_mean_
-                    allreduce_mean_(list(self.net.parameters()), self._flat, self.world)
-                self.opt.step()
-                acc += torch.stack([pl.detach(), vl.detach(), el.detach()]).double()
-                nsteps += 1
-        return self._step_stats(t0, U * L * N, acc, nsteps, finished, ret_sum)
-
-    def _update_fused(self, t0, obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum) -> BraxStepStats:
-        """training_step's update with fused_update: the same statistics update and permutations; each minibatch
-        step is FusedBraxLearner.grads on a slice of the pass's permutation (gathered from the time-major buffers,
-        no transposed copies), the all-reduce when world > 1, and adam_step."""
-        c = self.cfg
-        U, L, N = obs.shape[:3]
-        M = U * N
-        mb = M // c.num_minibatches
-        bufs = dict(obs=obs, nxt=nxt, raw=raw, logp=logp, rew=rew, disc=disc, trunc=trunc)
+                return torch.stack([x.detach() for x in parts])
         acc = torch.zeros(3, dtype=torch.float64, device=self.device)
-        st = torch.zeros(3, dtype=torch.float32, device=self.device)
         nsteps = 0
         for _ in range(c.num_updates_per_batch):
             perm = torch.randperm(M, device=self.device, generator=self.gen)
             for k in range(c.num_minibatches):
-                self._learner.grads(bufs, perm[k * mb:(k + 1) * mb], noise_step=self._update_t, stats=st)
-                self._update_t += 1
+                losses = grad(perm[k * mb:(k + 1) * mb])
                 if self.world > 1:
                     from .ppo import allreduce_mean_
                     allreduce_mean_(list(self.net.parameters()), self._flat, self.world)
-                self._learner.adam_step()
-                acc += st.double()
+                apply()
+                acc += losses.double()
                 nsteps += 1
         return self._step_stats(t0, U * L * N, acc, nsteps, finished, ret_sum)
 

@@ -35,6 +35,33 @@ def _need(t: torch.Tensor, shape, dtype, dev, name):
                          f"{t.dtype} {tuple(t.shape)} on {t.device}")
 
 
+def _ordered(policy: ActorCritic):
+    """The parameters in QuadPolicyParams' (and QuadPolicyGrads') field order."""
+    ex = policy.mlp_extractor
+    return [ex.policy_net[0].weight, ex.policy_net[0].bias, ex.policy_net[2].weight, ex.policy_net[2].bias,
+            policy.action_net.weight, policy.action_net.bias,
+            ex.value_net[0].weight, ex.value_net[0].bias, ex.value_net[2].weight, ex.value_net[2].bias,
+            policy.value_net.weight, policy.value_net.bias, policy.log_std]
+
+
+def current_stream(device) -> C.c_void_p:
+    """torch's current stream of `device`, as the entry points take it."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+class Workspace:
+    """A grow-only uint8 device buffer for a kernel family's scratch. reserve() replaces the allocation when more
+    bytes are needed, so a hipGraph that captured a launch is keyed on (ptr, nbytes), which the launch took."""
+
+    def __init__(self, device):
+        self.device, self.buf, self.ptr, self.nbytes = device, None, 0, 0
+
+    def reserve(self, nbytes: int) -> None:
+        if self.nbytes < nbytes:
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            self.ptr, self.nbytes = self.buf.data_ptr(), int(nbytes)
+
+
 def _episode_run(env, dev, T: int, M: int, obs_mode, alpha, alpha_all, max_dt, est_state, laps: bool):
     """The result tensors and the QuadPolicyRun of one fused episode / lap launch (FusedPolicy.episode's rules)."""
     n = env.num_envs
@@ -85,21 +112,15 @@ class FusedPolicy:
         L = N.lib()
         self.packed = torch.empty(L.quad_policy_packed_floats(), dtype=torch.float32, device=self.device)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     @torch.no_grad()
     def pack(self) -> None:
-        pol, ex = self.policy, self.policy.mlp_extractor
-        ts = [ex.policy_net[0].weight, ex.policy_net[0].bias, ex.policy_net[2].weight, ex.policy_net[2].bias,
-              pol.action_net.weight, pol.action_net.bias,
-              ex.value_net[0].weight, ex.value_net[0].bias, ex.value_net[2].weight, ex.value_net[2].bias,
-              pol.value_net.weight, pol.value_net.bias, pol.log_std]
+        ts = _ordered(self.policy)
         for t in ts:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise ValueError("policy parameters must be contiguous float32")
         prm = N.QuadPolicyParams(*[t.data_ptr() for t in ts])
-        N.check(N.lib().quad_policy_pack(C.byref(prm), _p(self.packed), self._stream()), "quad_policy_pack")
+        N.check(N.lib().quad_policy_pack(C.byref(prm), _p(self.packed), current_stream(self.device)),
+                "quad_policy_pack")
 
     def act(self, obs: torch.Tensor, actions_env: torch.Tensor, *, actions=None, log_prob=None,
             value=None, obs_copy=None, last_start=None, episode_starts=None,
@@ -126,7 +147,7 @@ class FusedPolicy:
                             deterministic=int(bool(deterministic)), seed=int(seed) & (2**64 - 1),
                             env_id_base=int(env_id_base),
                             epilogue=C.pointer(epilogue) if epilogue is not None else None)
-        N.check(N.lib().quad_policy_act(_p(self.packed), C.byref(a), n, self._stream()), "quad_policy_act")
+        N.check(N.lib().quad_policy_act(_p(self.packed), C.byref(a), n, current_stream(self.device)), "quad_policy_act")
 
     def value(self, obs: torch.Tensor, out: torch.Tensor, scratch: torch.Tensor) -> torch.Tensor:
         """V(obs) [N] into out ([1, N]) on the MFMA kernel: per-row results do not depend on the
@@ -159,7 +180,7 @@ class FusedPolicy:
         """quad_rollout_post: finish the pending step (end of a rollout)."""
         _need(cursor, (4,), torch.int32, self.device, "cursor")
         N.check(N.lib().quad_rollout_post(_p(self.packed), C.byref(epilogue), _p(cursor), epilogue._n,
-                                          self._stream()), "quad_rollout_post")
+                                          current_stream(self.device)), "quad_rollout_post")
 
     def rollout(self, env, *, obs_copy, actions, log_prob, value, episode_starts, rewards, last_obs,
                 last_start, ep_ret, ep_len, stats, t0: int, steps: int, seed: int, gamma: float,
@@ -184,7 +205,7 @@ class FusedPolicy:
                           rows=int(rows), t0=int(t0), steps=int(steps),
                           deterministic=int(bool(deterministic)), seed=int(seed) & (2**64 - 1),
                           gamma=float(gamma))
-        N.check(N.lib().quad_rollout(env._h, _p(self.packed), C.byref(r), self._stream()), "quad_rollout")
+        N.check(N.lib().quad_rollout(env._h, _p(self.packed), C.byref(r), current_stream(self.device)), "quad_rollout")
 
     def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
                 max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
@@ -199,7 +220,7 @@ class FusedPolicy:
         stay zero)."""
         res, run = _episode_run(env, self.device, int(env.max_episode_steps if max_steps is None else max_steps),
                                 int(trace_envs), obs_mode, alpha, alpha_all, max_dt, est_state, laps=False)
-        N.check(N.lib().quad_policy_episode(env._h, _p(self.packed), C.byref(run), self._stream()),
+        N.check(N.lib().quad_policy_episode(env._h, _p(self.packed), C.byref(run), current_stream(self.device)),
                 "quad_policy_episode")
         return res
 
@@ -216,8 +237,8 @@ class FusedPolicy:
         res, run = _episode_run(env, self.device, int(max_steps), int(trace_envs), obs_mode, alpha, alpha_all, max_dt,
                                 est_state, laps=True)
         wr = course.run(res.get("rewards"), res.get("flown_wp"))
-        N.check(N.lib().quad_policy_waypoints(env._h, _p(self.packed), C.byref(run), C.byref(wr), self._stream()),
-                "quad_policy_waypoints")
+        N.check(N.lib().quad_policy_waypoints(env._h, _p(self.packed), C.byref(run), C.byref(wr),
+                      current_stream(self.device)), "quad_policy_waypoints")
         return res
 
 
@@ -252,8 +273,6 @@ class FusedActor:
             raise N.QuadError("quad_actor_packed_floats rejected the architecture")
         self.packed = torch.empty(nf, dtype=torch.float32, device=self.device)
 
-    _stream = FusedPolicy._stream
-
     @torch.no_grad()
     def pack(self) -> None:
         pol, net = self.policy, self.policy.mlp_extractor.policy_net
@@ -262,7 +281,7 @@ class FusedActor:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise ValueError("policy parameters must be contiguous float32")
         prm = N.QuadActorParams(*[t.data_ptr() for t in ts])
-        N.check(N.lib().quad_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed), self._stream()),
+        N.check(N.lib().quad_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed), current_stream(self.device)),
                 "quad_actor_pack")
 
     def act(self, obs: torch.Tensor, actions_env: torch.Tensor, mean: Optional[torch.Tensor] = None, *,
@@ -276,15 +295,15 @@ class FusedActor:
         if mean is not None:
             _need(mean, (n, 4), f32, dev, "mean")
         N.check(N.lib().quad_actor_act(C.byref(self.arch), _p(self.packed), _p(obs), _p(mean), _p(actions_env), n,
-                                       self._stream()), "quad_actor_act")
+                                       current_stream(self.device)), "quad_actor_act")
 
     def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
                 max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
         """quad_actor_episode: FusedPolicy.episode with this actor (the same arguments, the same tensors)."""
         res, run = _episode_run(env, self.device, int(env.max_episode_steps if max_steps is None else max_steps),
                                 int(trace_envs), obs_mode, alpha, alpha_all, max_dt, est_state, laps=False)
-        N.check(N.lib().quad_actor_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), self._stream()),
-                "quad_actor_episode")
+        N.check(N.lib().quad_actor_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run),
+                      current_stream(self.device)), "quad_actor_episode")
         return res
 
     def waypoints(self, env, course, *, max_steps: int = 5000, obs_mode="env", alpha=None, alpha_all: float = 0.8,
@@ -294,7 +313,7 @@ class FusedActor:
                                 est_state, laps=True)
         wr = course.run(res.get("rewards"), res.get("flown_wp"))
         N.check(N.lib().quad_actor_waypoints(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), C.byref(wr),
-                                             self._stream()), "quad_actor_waypoints")
+                                             current_stream(self.device)), "quad_actor_waypoints")
         return res
 
 
@@ -435,8 +454,6 @@ class FusedBraxActor:
         self.packed = torch.empty(nf, dtype=torch.float32, device=self.device)
         self._noise_step = 0
 
-    _stream = FusedPolicy._stream
-
     def _mean_std(self):
         g = (lambda k: self.norm[k]) if isinstance(self.norm, dict) else (lambda k: getattr(self.norm, k))
         return g("mean"), g("std")
@@ -447,8 +464,8 @@ class FusedBraxActor:
         ts = _brax_parts(self.source)[0] + list(self._mean_std())
         ts = [torch.as_tensor(t).to(device=self.device, dtype=torch.float32).contiguous() for t in ts]
         prm = N.QuadBraxActorParams(*[t.data_ptr() for t in ts], min_std=self.min_std)
-        N.check(N.lib().quad_brax_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed), self._stream()),
-                "quad_brax_actor_pack")
+        N.check(N.lib().quad_brax_actor_pack(C.byref(self.arch), C.byref(prm), _p(self.packed),
+                      current_stream(self.device)), "quad_brax_actor_pack")
         self._packed_from = ts  # the launch reads them: alive until the next pack
 
     def act(self, obs: torch.Tensor, actions_env: torch.Tensor, logits: Optional[torch.Tensor] = None, *,
@@ -462,7 +479,7 @@ class FusedBraxActor:
         N.check(N.lib().quad_brax_actor_act(C.byref(self.arch), _p(self.packed), _p(obs), _p(logits), _p(actions_env),
                                             n, int(bool(deterministic)), int(seed) & (2**64 - 1),
                                             int(env_id_base) & (2**64 - 1), int(noise_step) & 0xFFFFFFFF,
-                                            self._stream()), "quad_brax_actor_act")
+                                            current_stream(self.device)), "quad_brax_actor_act")
 
     def episode(self, env, *, max_steps: Optional[int] = None, deterministic: bool = False, seed: int = 0,
                 trace_envs: int = 0, noise_step0: int = 0) -> dict:
@@ -483,8 +500,8 @@ class FusedBraxActor:
                             metrics=N.QuadBraxMetrics(**{k: res[k].data_ptr() for k, _ in N.BRAX_METRIC_FIELDS}),
                             trace_actions=tr("actions"), trace_obs=tr("obs"), trace_pos=tr("pos"),
                             trace_target=tr("target"))
-        N.check(N.lib().quad_brax_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), self._stream()),
-                "quad_brax_episode")
+        N.check(N.lib().quad_brax_episode(env._h, C.byref(self.arch), _p(self.packed), C.byref(run),
+                      current_stream(self.device)), "quad_brax_episode")
         return res
 
     def sample(self, obs: torch.Tensor, actions_env: torch.Tensor, raw: torch.Tensor, log_prob: torch.Tensor,
@@ -502,7 +519,7 @@ class FusedBraxActor:
         N.check(N.lib().quad_brax_actor_sample(C.byref(self.arch), _p(self.packed), _p(obs), _p(logits), _p(raw),
                                                _p(log_prob), _p(actions_env), n, int(seed) & (2**64 - 1),
                                                int(env_id_base) & (2**64 - 1), int(noise_step) & 0xFFFFFFFF,
-                                               self._stream()), "quad_brax_actor_sample")
+                                               current_stream(self.device)), "quad_brax_actor_sample")
 
     def unroll(self, env, *, num_unrolls: int, unroll_length: int, seed: int = 0, noise_step0: int = 0,
                ep_ret: torch.Tensor, stats: Optional[torch.Tensor] = None) -> dict:
@@ -526,8 +543,8 @@ class FusedBraxActor:
         u = N.QuadBraxUnroll(**{k: t.data_ptr() for k, t in buf.items()}, ep_ret=ep_ret.data_ptr(),
                              stats=stats.data_ptr(), steps=T, unroll_length=L,
                              noise_step0=int(noise_step0) & 0xFFFFFFFF, seed=int(seed) & (2**64 - 1))
-        N.check(N.lib().quad_brax_unroll(env._h, C.byref(self.arch), _p(self.packed), C.byref(u), self._stream()),
-                "quad_brax_unroll")
+        N.check(N.lib().quad_brax_unroll(env._h, C.byref(self.arch), _p(self.packed), C.byref(u),
+                      current_stream(self.device)), "quad_brax_unroll")
         tot = stats.sum(0) - before
         v = lambda k, *tail: buf[k].view(U, L, n, *tail)
         return dict(obs=v("obs", N.BRAX_OBS), nxt=buf["next_obs"], raw=v("raw", 4), logp=v("log_prob"),
@@ -586,10 +603,8 @@ class FusedBraxLearner:
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError("parameters must be contiguous float32")
-        self._ws = None
+        self._ws = Workspace(self.device)
         self._adam = None
-
-    _stream = FusedPolicy._stream
 
     def _ordered(self, ts):
         """[k0, k1, k2, b0, b1, b2] of each net -> w0, b0, w1, b1, w2, b2 of the policy, then of the value net."""
@@ -605,8 +620,8 @@ class FusedBraxLearner:
         overwrite the parameters' .grad (created when absent)."""
         prm, b, grd = self.describe(buffers, index, entropy_noise=entropy_noise, noise_step=noise_step, stats=stats,
                                     diag=diag)
-        N.check(N.lib().quad_brax_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), _p(self._ws),
-                                           C.c_int64(self._ws.numel()), self._stream()), "quad_brax_ppo_grad")
+        N.check(N.lib().quad_brax_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), self._ws.ptr, self._ws.nbytes,
+                                           current_stream(self.device)), "quad_brax_ppo_grad")
 
     def describe(self, buffers: dict, index: torch.Tensor, *, entropy_noise=None, noise_step: int = 0, stats=None,
                  diag: Optional[dict] = None):
@@ -636,10 +651,7 @@ class FusedBraxLearner:
         mean, std = self.norm.mean, self.norm.std
         _need(mean, (N.BRAX_OBS,), f32, dev, "mean")
         _need(std, (N.BRAX_OBS,), f32, dev, "std")
-        L_ = N.lib()
-        need = int(L_.quad_brax_ppo_workspace_bytes(mb, L))
-        if self._ws is None or self._ws.numel() < max(need, 16):
-            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        self._ws.reserve(max(int(N.lib().quad_brax_ppo_workspace_bytes(mb, L)), 16))
         h = N.BRAX_PPO_HIDDEN
         prm = N.QuadBraxPPOParams(*[p.data_ptr() for p in self._ordered(self.params)], mean.data_ptr(),
                                   std.data_ptr(), float(self.net.dist.min_std), h[0], h[1], h[0], h[1],

@@ -13,21 +13,14 @@ on torch's own optimizer state.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional
 
 import torch
 
 from .. import _native as N
-from .fused import FusedPolicy, _need
+from .fused import FusedPolicy, Workspace, _need, _ordered, current_stream  # noqa: F401 (_ordered: re-exported)
 from .policy import ActorCritic
-
-
-def _ordered(policy: ActorCritic):
-    ex = policy.mlp_extractor
-    return [ex.policy_net[0].weight, ex.policy_net[0].bias, ex.policy_net[2].weight, ex.policy_net[2].bias,
-            policy.action_net.weight, policy.action_net.bias,
-            ex.value_net[0].weight, ex.value_net[0].bias, ex.value_net[2].weight, ex.value_net[2].bias,
-            policy.value_net.weight, policy.value_net.bias, policy.log_std]
 
 
 class FusedLearner:
@@ -42,7 +35,7 @@ class FusedLearner:
             raise N.QuadError("FusedLearner needs the policy on a ROCm GPU")
         self.clip_range, self.ent_coef, self.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
         self.normalize_advantage = bool(normalize_advantage)
-        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._ws = Workspace(self.device)
         self._lib = N.lib()
 
     def _structs(self):
@@ -57,10 +50,18 @@ class FusedLearner:
         return (N.QuadPolicyParams(*[p.data_ptr() for p in ps]),
                 N.QuadPolicyGrads(*[p.grad.data_ptr() for p in ps]))
 
-    def _workspace(self, B: int) -> None:
-        need = int(self._lib.quad_ppo_workspace_bytes(B))
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+    def reserve(self, B: int) -> None:
+        """Size the workspace for minibatches of B rows (quad_ppo_workspace_bytes) without launching anything."""
+        self._ws.reserve(int(self._lib.quad_ppo_workspace_bytes(B)))
+
+    def signature(self) -> tuple:
+        """Everything a quad_ppo_grad / quad_ppo_adv_stats_epoch launch takes by value besides the batch: the 13
+        parameter and 13 gradient pointers, the workspace, the loss coefficients and the gradient form the library
+        reads from the environment per call. A hipGraph that captured grads() is valid while this is unchanged."""
+        prm, grd = self._structs()
+        return (bytes(prm), bytes(grd), self._ws.ptr, self._ws.nbytes,
+                self.clip_range, self.ent_coef, self.vf_coef, self.normalize_advantage,
+                self._lib.quad_ppo_grad_form(), os.environ.get("QUADENV_LEARNER_SPLIT"))
 
     def adv_stats(self, advantages: torch.Tensor, index: torch.Tensor) -> None:
         """Enqueue the advantage statistics of minibatch `index` (quad_ppo_adv_stats) into the
@@ -68,11 +69,10 @@ class FusedLearner:
         if not self.normalize_advantage:
             return
         B = int(index.numel())
-        self._workspace(B)
+        self.reserve(B)
         b = N.QuadPPOBatch(0, 0, 0, advantages.data_ptr(), 0, index.data_ptr(), B, 1, 0.2, 0.0, 0.0, None)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        N.check(self._lib.quad_ppo_adv_stats(C.byref(b), C.c_void_p(self._ws.data_ptr()), C.c_int64(self._ws.numel()),
-                                             stream), "quad_ppo_adv_stats")
+        N.check(self._lib.quad_ppo_adv_stats(C.byref(b), self._ws.ptr, self._ws.nbytes, current_stream(self.device)),
+                "quad_ppo_adv_stats")
 
     def adv_stats_epoch(self, advantages: torch.Tensor, perm: torch.Tensor, batch: int, n_minibatches: int,
                         out: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -86,9 +86,8 @@ class FusedLearner:
             raise ValueError("perm: a contiguous int64 vector of at least batch * n_minibatches rows")
         if out is None or tuple(out.shape) != (n_minibatches, N.ADV_SUM_DOUBLES):
             out = torch.empty(n_minibatches, N.ADV_SUM_DOUBLES, dtype=torch.float64, device=self.device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        N.check(self._lib.quad_ppo_adv_stats_epoch(C.c_void_p(advantages.data_ptr()), C.c_void_p(perm.data_ptr()),
-                                                   int(batch), int(n_minibatches), C.c_void_p(out.data_ptr()), stream),
+        N.check(self._lib.quad_ppo_adv_stats_epoch(advantages.data_ptr(), perm.data_ptr(), int(batch),
+                                                   int(n_minibatches), out.data_ptr(), current_stream(self.device)),
                 "quad_ppo_adv_stats_epoch")
         return out
 
@@ -117,7 +116,7 @@ class FusedLearner:
             raise ValueError("empty minibatch")
         if stats is not None:
             _need(stats, (4,), torch.float32, dev, "stats")
-        self._workspace(B)
+        self.reserve(B)
         prm, grd = self._structs()
         norm = int(self.normalize_advantage)
         if norm and adv_sums is not None:
@@ -131,15 +130,14 @@ class FusedLearner:
                            self.clip_range, self.ent_coef, self.vf_coef,
                            None if stats is None else stats.data_ptr(),
                            adv_sums.data_ptr() if norm == N.QUAD_ADV_GIVEN else None)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        ws, stream = self._ws, current_stream(dev)
         if hidden is not None:
             _need(hidden, (2, B, 256), torch.float32, dev, "hidden")
-            N.check(self._lib.quad_ppo_hidden(C.byref(prm), C.byref(b), C.byref(grd), C.c_void_p(hidden.data_ptr()),
-                                              C.c_void_p(self._ws.data_ptr()), C.c_int64(self._ws.numel()), stream),
-                    "quad_ppo_hidden")
+            N.check(self._lib.quad_ppo_hidden(C.byref(prm), C.byref(b), C.byref(grd), hidden.data_ptr(), ws.ptr,
+                                              ws.nbytes, stream), "quad_ppo_hidden")
             return
-        N.check(self._lib.quad_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), C.c_void_p(self._ws.data_ptr()),
-                                        C.c_int64(self._ws.numel()), stream), "quad_ppo_grad")
+        N.check(self._lib.quad_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), ws.ptr, ws.nbytes, stream),
+                "quad_ppo_grad")
 
 
 def adam_state(opt: torch.optim.Adam, params) -> list:
@@ -176,7 +174,7 @@ class FusedAdam:
                 raise ValueError("parameters must be contiguous float32 on a ROCm GPU")
         self.max_grad_norm = float(max_grad_norm)
         self._lib = N.lib()
-        self._ws = None
+        self._ws = Workspace(self.params[0].device)
 
     def _build(self):
         grp = self.opt.param_groups[0]
@@ -196,18 +194,19 @@ class FusedAdam:
 
     def signature(self) -> tuple:
         """Everything a quad_clip_adam launch takes by value: the parameter, gradient and Adam-state
-        pointers and the hyperparameters. A hipGraph that captured step() replays correctly only
-        while this is unchanged (Optimizer.load_state_dict replaces the state tensors; a changed
-        lr is a new kernel argument)."""
+        pointers, the hyperparameters and the workspace. A hipGraph that captured step() replays correctly
+        only while this is unchanged (Optimizer.load_state_dict replaces the state tensors; a changed lr is a new
+        kernel argument; reserve() first: the workspace is allocated on first use)."""
         a = self._build()
         return tuple((a.params[i], a.grads[i], a.exp_avg[i], a.exp_avg_sq[i], a.step[i]) for i in range(a.count)) + \
-            (a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm)
+            (a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm, self._ws.ptr, self._ws.nbytes)
+
+    def reserve(self) -> None:
+        """Size the workspace (quad_adam_workspace_bytes; the tensors are fixed, so once) without launching anything."""
+        if not self._ws.nbytes:
+            self._ws.reserve(max(int(self._lib.quad_adam_workspace_bytes(C.byref(self._build()))), 4))
 
     def step(self) -> None:
-        a = self._build()
-        if self._ws is None:
-            self._ws = torch.empty(max(int(self._lib.quad_adam_workspace_bytes(C.byref(a))), 4), dtype=torch.uint8,
-                                   device=self.params[0].device)
-        stream = C.c_void_p(torch.cuda.current_stream(self.params[0].device).cuda_stream)
-        N.check(self._lib.quad_clip_adam(C.byref(a), C.c_void_p(self._ws.data_ptr()), C.c_int64(self._ws.numel()),
-                                         stream), "quad_clip_adam")
+        self.reserve()
+        N.check(self._lib.quad_clip_adam(C.byref(self._build()), self._ws.ptr, self._ws.nbytes,
+                                         current_stream(self._ws.device)), "quad_clip_adam")

@@ -24,7 +24,7 @@ import torch
 
 from .. import _native as N
 from ..envs import QuadVecEnv
-from .learner import adam_state
+from .fused import current_stream
 from .ppo import PPO, PPOConfig, RolloutStats
 
 
@@ -88,7 +88,7 @@ class PopulationPPO:
         self.active = list(range(P))
         dev = self.device
         m0 = self.members[0]
-        a0 = self._adam_struct(m0)
+        a0 = m0._adam._build()
         ws = int(self._lib.quad_pop_workspace_bytes(C.byref(a0), batch))
         if ws <= 0:
             raise N.QuadError("quad_pop_workspace_bytes failed: " + self._lib.quad_last_error().decode(errors="replace"))
@@ -108,16 +108,11 @@ class PopulationPPO:
         self._started = False
 
     # ------------------------------------------------------------------------------------
-    @staticmethod
-    def _adam_struct(m: PPO) -> N.QuadAdam:
-        adam_state(m.opt, m._adam.params)
-        return m._adam._build()
-
     def _fill(self, e: N.QuadPopMember, m: PPO, i: int, ws: int) -> None:
         prm, grd = m._learner._structs()
         cfg = m.cfg
         e.env = m.env._h.value
-        e.params, e.grads, e.adam = prm, grd, self._adam_struct(m)
+        e.params, e.grads, e.adam = prm, grd, m._adam._build()
         e.packed = _p(m._fp.packed)
         e.rollout = N.QuadRollout(obs_copy=_p(m.buf_obs), actions=_p(m.buf_act), log_prob=_p(m.buf_logp),
                                   value=_p(m.buf_val), episode_starts=_p(m.buf_start), rewards=_p(m.buf_rew),
@@ -141,9 +136,6 @@ class PopulationPPO:
             self.close()
         except Exception:
             pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _subset(self, members: Sequence[int]) -> int:
         """The id of the launch subset `members` (registered with the library once: one small upload)."""
@@ -180,7 +172,7 @@ class PopulationPPO:
         out: List[Optional[RolloutStats]] = [None] * self.P
         if not act:
             return out
-        L, st, h = self._lib, self._stream(), self._h
+        L, st, h = self._lib, current_stream(self.device), self._h
         t0 = time.perf_counter()
         sid = self._subset(act)
         N.check(L.quad_pop_pack(h, sid, st), "quad_pop_pack")
@@ -227,7 +219,7 @@ class PopulationPPO:
         out: List[Optional[dict]] = [None] * self.P
         if not act:
             return out
-        L, st, h = self._lib, self._stream(), self._h
+        L, st, h = self._lib, current_stream(self.device), self._h
         epochs = {i: int(self.members[i].cfg.n_epochs) for i in act}
         max_e = max(epochs.values())
         # every epoch's keys, drawn per member in epoch order, uploaded once for the whole update
@@ -265,7 +257,7 @@ class PopulationPPO:
         seeds = list(range(self.P)) if seeds is None else [int(s) for s in seeds]
         if len(seeds) != self.P:
             raise ValueError("seeds: one per member")
-        L, st, h, dev, n = self._lib, self._stream(), self._h, self.device, int(num_episodes)
+        L, st, h, dev, n = self._lib, current_stream(self.device), self._h, self.device, int(num_episodes)
         # fresh evaluation handles for the ACTIVE members only (a deactivated member costs nothing), seeded as
         # evaluate_episodes seeds its env; the table takes each handle's seed as it is when attached
         envs = {i: QuadVecEnv(n, env=self._env_kind, wrapper=self._wrapper, device=dev, seed=seeds[i],

@@ -86,6 +86,49 @@ def epoch_permutation(total: int, device: torch.device, out: Optional[torch.Tens
     return out
 
 
+def fused_epoch(learner, adam, bufs, B: int, perm, sums, mstats, limit: Optional[int] = None,
+                reduce: Optional[Callable[[], None]] = None) -> None:
+    """One epoch of the fused update on the flat buffers `bufs` = (obs, act, logp_old, adv, ret), eager
+    or under hipGraph capture. The full minibatches' advantage statistics in one launch when that launch
+    fits (grid y <= 65,535 minibatches, 4 KB of float64 sums each; into `sums` when given); then per
+    minibatch m = perm[m * B:(m + 1) * B], at most `limit` of them: learner.grads (loss statistics into
+    mstats[m]), `reduce` (the gradient all-reduce) when given, adam.step. A short last minibatch (SB3
+    yields one when batch_size does not divide the buffer) and an epoch without the one-launch
+    statistics run grads' own statistics pre-pass -- the same sums either way."""
+    total = bufs[0].shape[0]
+    nmb, n_full = n_minibatches(total, B), total // B
+    rows = None  # (the rollout buffer's advantages do not change during the update)
+    if learner.normalize_advantage and 1 <= n_full <= EPOCH_STATS_MAX_MINIBATCHES:
+        rows = learner.adv_stats_epoch(bufs[3], perm, B, n_full, out=sums)
+    for m in range(nmb if limit is None else min(nmb, limit)):
+        learner.grads(*bufs, perm[m * B:min(total, (m + 1) * B)], mstats[m],
+                      adv_sums=rows[m] if rows is not None and m < n_full else None)
+        if reduce is not None:
+            reduce()
+        adam.step()  # clip_grad_norm_ + Adam.step (quad_clip_adam)
+
+
+def fused_update(learner, adam, bufs, B: int, steps: int, mstats, reduce=None) -> None:
+    """The eager fused update: `steps` minibatches, epoch after epoch, each epoch on its own
+    epoch_permutation (drawn in epoch order; an epoch that runs no minibatch draws none)."""
+    total = bufs[0].shape[0]
+    nmb = n_minibatches(total, B)
+    for k in range(0, steps, nmb):
+        fused_epoch(learner, adam, bufs, B, epoch_permutation(total, bufs[0].device), None, mstats[k:], steps - k,
+                    reduce)
+
+
+@dataclass
+class CapturedEpoch:
+    """PPO._epoch_graph: fused_epoch's launches as a hipGraph, the key of everything they took by value, and
+    the persistent buffers they read (perm) and write (sums, mst)."""
+    key: Optional[tuple]  # None while (re)capturing
+    graph: Optional["torch.cuda.CUDAGraph"]
+    perm: torch.Tensor
+    sums: torch.Tensor
+    mst: torch.Tensor
+
+
 def ppo_loss(policy: ActorCritic, obs, act, logp_old, adv, ret, cfg: PPOConfig):
     """SB3 PPO.train minibatch loss: returns (loss, pg_loss, vf_loss, entropy, clip_fraction)."""
     mean, v = policy.forward_heads(obs)
@@ -252,7 +295,7 @@ class PPO:
                                       self.cfg.normalize_advantage)
                          if self.cfg.fused_update and fusable and self.device.type == "cuda" else None)
         self._adam = FusedAdam(self.opt, self.cfg.max_grad_norm) if self._learner is not None else None
-        self._epoch_graph = None  # (key, graph, perm, sums, mstats) of _train_fused's captured epoch
+        self._epoch_graph: Optional[CapturedEpoch] = None  # _train_graphed's captured epoch
         self._t_host = 0  # running step counter of the one-launch path (keys the action noise)
         self._cursor_resume = None  # the two-launch path's noise counter after load_state_dict
         self._noise_seed = (int(seed) * 0x9E3779B97F4A7C15 + 0x5851F42D4C957F2D) & (2**64 - 1)
@@ -461,94 +504,55 @@ class PPO:
     def _train_fused(self, obs, act, logp_old, adv, ret, B, nmb, epochs, max_minibatches, stats) -> dict:
         """PPO.train with the minibatch gradient from quad_ppo_grad (no autograd graph, no
         minibatch copies), the flat-bucket all-reduce, then clip_grad_norm_ + Adam as quad_clip_adam."""
-        cfg = self.cfg
-        total = obs.shape[0]
-        if (cfg.graph_update and self.world == 1 and max_minibatches is None and total % B == 0
-                and 1 <= nmb <= EPOCH_STATS_MAX_MINIBATCHES and epochs >= 1):
-            return self._train_graphed(obs, act, logp_old, adv, ret, B, nmb, epochs, stats)
+        cfg, bufs = self.cfg, (obs, act, logp_old, adv, ret)
         steps = epochs * nmb if max_minibatches is None else min(epochs * nmb, max_minibatches)
         mstats = torch.zeros(max(steps, 1), 4, dtype=torch.float32, device=self.device)
-        perms, sums = {}, {}
-        # the full minibatches' advantage statistics of an epoch in one launch when that launch fits
-        # (grid y <= 65,535 minibatches, 4 KB of float64 sums each); a short last minibatch (SB3
-        # yields one when batch_size does not divide the buffer) and larger counts run grads' own
-        # statistics pre-pass -- the same sums either way
-        n_full = total // B
-        epoch_stats = 1 <= n_full <= EPOCH_STATS_MAX_MINIBATCHES
-
-        def index_of(k):  # the k-th minibatch of the update: epoch k // nmb, slot k % nmb
-            e, m = divmod(k, nmb)
-            if e not in perms:  # drawn in epoch order, as the per-epoch loop drew them
-                perms[e] = epoch_permutation(total, self.device)
-                # every minibatch's advantage statistics of the epoch in one launch (the rollout
-                # buffer's advantages do not change during the update)
-                sums[e] = self._learner.adv_stats_epoch(adv, perms[e], B, n_full) if epoch_stats else None
-            row = sums[e][m] if sums[e] is not None and m < n_full else None
-            return perms[e][m * B:min(total, (m + 1) * B)], row
-
-        done = 0
-        for k in range(steps):
-            idx, adv_sums = index_of(k)
-            self._learner.grads(obs, act, logp_old, adv, ret, idx, mstats[k], adv_sums=adv_sums)
-            if self.world > 1:
-                allreduce_mean_(self.params, self._flat, self.world, timing=self.comm_events)
-            self._adam.step()  # clip_grad_norm_ + Adam.step (quad_clip_adam)
-            perms.pop(k // nmb - 1, None)
-            sums.pop(k // nmb - 1, None)
-            done += 1
-        a = mstats[:done].double().mean(0).tolist() if done else [0.0] * 4
-        stats.update(pg_loss=a[0], vf_loss=a[1], entropy=a[2], clip_fraction=a[3], n=done)
+        if (cfg.graph_update and self.world == 1 and max_minibatches is None and obs.shape[0] % B == 0
+                and 1 <= nmb <= EPOCH_STATS_MAX_MINIBATCHES and epochs >= 1):
+            self._train_graphed(bufs, B, nmb, epochs, mstats)
+        else:
+            reduce = lambda: allreduce_mean_(self.params, self._flat, self.world, timing=self.comm_events)
+            fused_update(self._learner, self._adam, bufs, B, steps, mstats, reduce if self.world > 1 else None)
+        a = mstats[:steps].double().mean(0).tolist() if steps else [0.0] * 4
+        stats.update(pg_loss=a[0], vf_loss=a[1], entropy=a[2], clip_fraction=a[3], n=steps)
         return stats
 
-    def _epoch_steps(self, obs, act, logp_old, adv, ret, B, nmb, perm, sums, mstats) -> None:
-        """One epoch of the fused update on fixed buffers: the epoch's advantage statistics (one
-        launch), then per minibatch quad_ppo_grad + quad_clip_adam -- the launch sequence
-        _train_fused issues, on the permutation in `perm`."""
-        if self._learner.normalize_advantage:
-            self._learner.adv_stats_epoch(adv, perm, B, nmb, out=sums)
-        for m in range(nmb):
-            self._learner.grads(obs, act, logp_old, adv, ret, perm[m * B:(m + 1) * B], mstats[m],
-                                adv_sums=sums[m] if self._learner.normalize_advantage else None)
-            self._adam.step()
-
-    def _train_graphed(self, obs, act, logp_old, adv, ret, B, nmb, epochs, stats) -> dict:
-        """_train_fused for one GPU when the minibatches tile the buffer: every epoch's launches
-        (advantage statistics + nmb x (quad_ppo_grad + quad_clip_adam)) captured once as a hipGraph
-        on persistent permutation / statistics buffers and replayed per epoch after the epoch's
-        permutation is drawn into its buffer -- the same kernels on the same data in the same
-        order as the eager loop (the same bits), without its per-launch host work (at train.py's
-        scale, 8 envs x 1,024 steps in minibatches of 128, that host work was most of the update).
-        The first epoch after a (re)capture runs eagerly; its launches warm the workspaces. The graph
-        is recaptured whenever anything its launches took by value changes: the buffers, the batch
-        partition, or the optimizer's state tensors / hyperparameters (FusedAdam.signature)."""
-        total, dev = obs.shape[0], self.device
-        key = (B, nmb, tuple(t.data_ptr() for t in (obs, act, logp_old, adv, ret)),
-               self._learner.normalize_advantage, self._adam.signature())
-        mstats = torch.zeros(epochs * nmb, 4, dtype=torch.float32, device=dev)
+    def _train_graphed(self, bufs, B, nmb, epochs, mstats) -> None:
+        """fused_update for one GPU when the minibatches tile the buffer: fused_epoch's launches captured
+        once as a hipGraph on persistent permutation / statistics buffers and replayed per epoch after the
+        epoch's permutation is drawn into its buffer -- the same kernels on the same data in the same
+        order as the eager loop (the same bits), without its per-launch host work (at train.py's scale,
+        8 envs x 1,024 steps in minibatches of 128, that host work was most of the update). The first
+        epoch after a (re)capture runs eagerly, and anything the launches took by value is in the key. The
+        workspaces are reserved for B before the key is taken (or the eager epoch would grow them after it and
+        the next train() recapture for nothing) and after the persistent buffers (the measured allocation order)."""
+        total, dev = bufs[0].shape[0], self.device
+        cap = self._epoch_graph
+        if cap is None or cap.perm.numel() != total or cap.mst.shape[0] != nmb:  # the persistent buffers
+            cap = CapturedEpoch(None, None, torch.empty(total, dtype=torch.int64, device=dev),
+                                torch.empty(nmb, N.ADV_SUM_DOUBLES, dtype=torch.float64, device=dev),
+                                torch.zeros(nmb, 4, dtype=torch.float32, device=dev))
+        self._learner.reserve(B)
+        self._adam.reserve()
+        key = (B, nmb, tuple(t.data_ptr() for t in bufs), self._learner.signature(), self._adam.signature())
         e0 = 0
-        if self._epoch_graph is None or self._epoch_graph[0] != key:
-            perm = torch.empty(total, dtype=torch.int64, device=dev)
-            sums = torch.empty(nmb, N.ADV_SUM_DOUBLES, dtype=torch.float64, device=dev)
-            mst = torch.zeros(nmb, 4, dtype=torch.float32, device=dev)
-            epoch_permutation(total, dev, out=perm)
-            self._epoch_steps(obs, act, logp_old, adv, ret, B, nmb, perm, sums, mstats[:nmb])
+        if cap.key != key:
+            cap.key, cap.graph = None, torch.cuda.CUDAGraph()
+            epoch_permutation(total, dev, out=cap.perm)
+            fused_epoch(self._learner, self._adam, bufs, B, cap.perm, cap.sums, mstats)
             e0 = 1
-            g = torch.cuda.CUDAGraph()
             s = torch.cuda.Stream(dev)
             s.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    self._epoch_steps(obs, act, logp_old, adv, ret, B, nmb, perm, sums, mst)
+                with torch.cuda.graph(cap.graph, stream=s):
+                    fused_epoch(self._learner, self._adam, bufs, B, cap.perm, cap.sums, cap.mst)
             torch.cuda.current_stream(dev).wait_stream(s)
-            self._epoch_graph = (key, g, perm, sums, mst)
-        _, g, perm, sums, mst = self._epoch_graph
+            cap.key = key
+            self._epoch_graph = cap
         for e in range(e0, epochs):
-            epoch_permutation(total, dev, out=perm)
-            g.replay()
-            mstats[e * nmb:(e + 1) * nmb].copy_(mst)
-        a = mstats.double().mean(0).tolist()
-        stats.update(pg_loss=a[0], vf_loss=a[1], entropy=a[2], clip_fraction=a[3], n=epochs * nmb)
-        return stats
+            epoch_permutation(total, dev, out=cap.perm)
+            cap.graph.replay()
+            mstats[e * nmb:(e + 1) * nmb].copy_(cap.mst)
 
     def learn(self, total_timesteps: int, callback: Optional[Callable] = None) -> "PPO":
         it = 0
