@@ -844,6 +844,25 @@ int quad_ppo_adv_stats(const QuadPPOBatch* b, void* workspace, int64_t workspace
 #define QUAD_ADV_SUM_DOUBLES 512
 int quad_ppo_adv_stats_epoch(const float* advantages, const int64_t* perm, int32_t batch, int32_t n_minibatches,
                              double* sums, void* stream);
+/* ---- The same minibatch gradient for the general actor's family: policy net 12 -> h1 -> h2 -> 4 and
+ * value net 12 -> h1 -> h2 -> 1 of the same widths (ActorCritic's MlpExtractor), h1 a multiple of 32 in [32, 512],
+ * h2 in {64, 128, 256}, QUAD_ACTFN_RELU or QUAD_ACTFN_TANH. QuadPolicyParams / QuadPolicyGrads as above with the
+ * arch's shapes (torch's [out, in]): pi_w0, vf_w0 [h1,12]; pi_w1, vf_w1 [h2,h1]; act_w [4,h2]; val_w [1,h2].
+ * Semantics are quad_ppo_grad's: the SB3 loss, the unbiased advantage std (skipped at batch == 1), torch's tie rule
+ * for the min and the closed clamp interval, the state-independent log_std gradient and entropy, stats[4], gradients
+ * overwritten, rows gathered through `index`, no host synchronisation (graph-capturable). The gradient is
+ * bit-identical from run to run and under a physical reordering of the rows into index order (no atomics; every sum
+ * runs over the minibatch positions in a fixed order). normalize_advantage: 0, 1 (own pre-pass) or QUAD_ADV_GIVEN
+ * (adv_sums from quad_ppo_adv_stats_epoch: the same bits as 1); QUAD_ADV_PRECOMPUTED belongs to quad_ppo_grad's
+ * workspace layout and is QUAD_EINVAL here. batch in [1, 2^22]; the workspace holds the hidden images of every row
+ * (about 8 (2 h1 + h2) bytes per row). tanh is the forward kernels' (quad_actor_act). QUAD_EINVAL with nothing
+ * launched and nothing written: an arch outside the family (quad_ppo_arch_workspace_bytes: 0), NULL or misaligned
+ * pointers (4 bytes; obs, actions, workspace 16; index, adv_sums 8), batch < 1, a workspace that is too small,
+ * clip_range <= 0. The 12-128-128 ReLU net is a member; quad_ppo_grad keeps its own kernels for it.
+ * The added entry points did not change the ABI version. */
+int64_t quad_ppo_arch_workspace_bytes(const QuadActorArch* arch, int32_t batch);
+int quad_ppo_arch_grad(const QuadActorArch* arch, const QuadPolicyParams* params, const QuadPPOBatch* b,
+                       const QuadPolicyGrads* grads, void* workspace, int64_t workspace_bytes, void* stream);
 /* Diagnostics (parity tests): quad_ppo_grad through a build of the same kernel body that also
  * records the hidden pre-activations (before the ReLU) it computed for every minibatch row:
  * hidden[(net * batch + pos) * 256 + 128 * layer + neuron], net 0 = actor / 1 = critic, pos = the

@@ -259,7 +259,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_actor_packed_floats", "quad_actor_pack", "quad_actor_act", "quad_actor_episode",
            "quad_actor_waypoints",
            "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode",
-           "quad_brax_actor_sample", "quad_brax_unroll", "quad_brax_ppo_workspace_bytes", "quad_brax_ppo_grad")
+           "quad_brax_actor_sample", "quad_brax_unroll", "quad_brax_ppo_workspace_bytes", "quad_brax_ppo_grad",
+           "quad_ppo_arch_workspace_bytes", "quad_ppo_arch_grad")
 
 
 class QuadRollout(C.Structure):
@@ -415,6 +416,13 @@ def _declare(L):
     L.quad_brax_ppo_grad.argtypes = [C.POINTER(QuadBraxPPOParams), C.POINTER(QuadBraxPPOBatch),
                                      C.POINTER(QuadBraxPPOGrads), vp, C.c_int64, vp]
     L.quad_brax_ppo_grad.restype = C.c_int
+    if not hasattr(L, "quad_ppo_arch_grad"):  # nor with the general learner's
+        raise QuadError(f"{LIB_PATH} was built before the general learner's entry points (quad_ppo_arch_grad); rebuild it")
+    L.quad_ppo_arch_workspace_bytes.argtypes = [arch, i32]
+    L.quad_ppo_arch_workspace_bytes.restype = C.c_int64
+    L.quad_ppo_arch_grad.argtypes = [arch, C.POINTER(QuadPolicyParams), C.POINTER(QuadPPOBatch),
+                                     C.POINTER(QuadPolicyGrads), vp, C.c_int64, vp]
+    L.quad_ppo_arch_grad.restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
     L.quad_pop_detach_eval.argtypes = [vp]

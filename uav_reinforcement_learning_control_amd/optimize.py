@@ -20,7 +20,8 @@ median of the values reported at that index by the trials completed earlier and 
 population. A trial whose parameters turn non-finite scores NaN (optimize.py:165-175).
 
 Only the architecture the fused kernels run is searched: net_arch is fixed to "small" ([128, 128]) and
-activation_fn to "relu"; the reference's medium / large / tanh choices are not sampled. The sampler is random
+activation_fn to "relu"; the reference's medium / large / tanh choices are not sampled (a single learner trains them
+fused, ppo.learner.FusedArchLearner / train --fused-arch-update; populations do not yet). The sampler is random
 search, not TPE; Optuna is not a dependency, so --storage is accepted and ignored.
 """
 from __future__ import annotations

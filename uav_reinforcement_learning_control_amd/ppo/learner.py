@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 
 from .. import _native as N
-from .fused import FusedPolicy, Workspace, _need, _ordered, current_stream  # noqa: F401 (_ordered: re-exported)
+from .fused import FusedActor, FusedPolicy, Workspace, _need, _ordered, current_stream  # noqa: F401 (_ordered: re-exported)
 from .policy import ActorCritic
 
 
@@ -138,6 +138,117 @@ class FusedLearner:
             return
         N.check(self._lib.quad_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), ws.ptr, ws.nbytes, stream),
                 "quad_ppo_grad")
+
+
+class FusedArchLearner(FusedLearner):
+    """quad_ppo_arch_grad for an ActorCritic of the general actor's family (12 -> H1 -> H2 -> 4 | 1 with both nets of
+    the same widths, H1 a multiple of 32 up to 512, H2 in {64, 128, 256}, ReLU or tanh): FusedLearner's interface
+    and semantics on the general learner's kernels (csrc/learner_arch.hip), so fused_epoch, fused_update, the
+    captured epoch and FusedAdam take it as they take FusedLearner. The two-stream advantage pre-pass (adv_stats /
+    adv_ready) and the hidden-activation dump belong to quad_ppo_grad and are not offered."""
+
+    def __init__(self, policy: ActorCritic, clip_range: float, ent_coef: float, vf_coef: float,
+                 normalize_advantage: bool = True):
+        self.arch = arch_of_learner(policy)
+        self.policy = policy
+        self.device = policy.log_std.device
+        if self.device.type != "cuda":
+            raise N.QuadError("FusedArchLearner needs the policy on a ROCm GPU")
+        self.clip_range, self.ent_coef, self.vf_coef = float(clip_range), float(ent_coef), float(vf_coef)
+        self.normalize_advantage = bool(normalize_advantage)
+        self._ws = Workspace(self.device)
+        self._lib = N.lib()
+
+    def reserve(self, B: int) -> None:
+        """Size the workspace for minibatches of B rows (quad_ppo_arch_workspace_bytes) without launching anything."""
+        nbytes = int(self._lib.quad_ppo_arch_workspace_bytes(C.byref(self.arch), B))
+        if nbytes <= 0:
+            raise N.QuadError(f"quad_ppo_arch_workspace_bytes rejected batch {B}")
+        self._ws.reserve(nbytes)
+
+    def signature(self) -> tuple:
+        """Everything a quad_ppo_arch_grad / quad_ppo_adv_stats_epoch launch takes by value besides the batch: the
+        arch, the 13 parameter and 13 gradient pointers, the workspace and the loss coefficients."""
+        prm, grd = self._structs()
+        return ("arch", self.arch.h1, self.arch.h2, self.arch.activation, bytes(prm), bytes(grd), self._ws.ptr,
+                self._ws.nbytes, self.clip_range, self.ent_coef, self.vf_coef, self.normalize_advantage)
+
+    def adv_stats(self, advantages: torch.Tensor, index: torch.Tensor) -> None:
+        raise NotImplementedError("FusedArchLearner: the separate advantage pre-pass (QUAD_ADV_PRECOMPUTED) is "
+                                  "quad_ppo_grad's; use adv_stats_epoch and grads(..., adv_sums=row)")
+
+    def grads(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, advantages: torch.Tensor,
+              returns: torch.Tensor, index: torch.Tensor, stats: Optional[torch.Tensor] = None,
+              adv_ready: bool = False, adv_sums: Optional[torch.Tensor] = None) -> None:
+        """FusedLearner.grads for this arch: overwrite every parameter's .grad with the gradient of the PPO loss on
+        rows `index`; `stats` (float32 [4], optional) receives pg_loss, vf_loss, entropy, clip_fraction; `adv_sums`:
+        this minibatch's row of adv_stats_epoch (the statistics pre-pass is skipped; same bits)."""
+        if adv_ready:
+            raise NotImplementedError("FusedArchLearner: adv_ready (QUAD_ADV_PRECOMPUTED) is quad_ppo_grad's")
+        dev = self.device
+        M = obs.shape[0]
+        _need(obs, (M, 12), torch.float32, dev, "obs")
+        _need(actions, (M, 4), torch.float32, dev, "actions")
+        for t, n in ((log_prob, "log_prob"), (advantages, "advantages"), (returns, "returns")):
+            _need(t, (M,), torch.float32, dev, n)
+        if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != dev:
+            raise ValueError("index: expected a contiguous int64 vector on the policy's device")
+        B = int(index.numel())
+        if B < 1:
+            raise ValueError("empty minibatch")
+        if stats is not None:
+            _need(stats, (4,), torch.float32, dev, "stats")
+        self.reserve(B)
+        prm, grd = self._structs()
+        norm = int(self.normalize_advantage)
+        if norm and adv_sums is not None:
+            if adv_sums.dtype != torch.float64 or adv_sums.numel() != N.ADV_SUM_DOUBLES or not adv_sums.is_contiguous():
+                raise ValueError("adv_sums: one contiguous float64 row of adv_stats_epoch")
+            norm = N.QUAD_ADV_GIVEN
+        b = N.QuadPPOBatch(obs.data_ptr(), actions.data_ptr(), log_prob.data_ptr(), advantages.data_ptr(),
+                           returns.data_ptr(), index.data_ptr(), B, norm,
+                           self.clip_range, self.ent_coef, self.vf_coef,
+                           None if stats is None else stats.data_ptr(),
+                           adv_sums.data_ptr() if norm == N.QUAD_ADV_GIVEN else None)
+        N.check(self._lib.quad_ppo_arch_grad(C.byref(self.arch), C.byref(prm), C.byref(b), C.byref(grd), self._ws.ptr,
+                                             self._ws.nbytes, current_stream(dev)), "quad_ppo_arch_grad")
+
+
+# ((H1, H2), activation, batch_size) for which the fused update did not beat the torch update in
+# profiles/arch_update/bench.json (DESIGN 23, by 19's to 22's rule); train.py --fused-arch-update honours it
+ARCH_UPDATE_KEEP_TORCH = frozenset()
+
+LEARNER_FAMILY = ("12-H1-H2-(4|1) policy and value nets of the same widths, H1 a multiple of 32 up to "
+                  f"{N.ACTOR_MAX_H1}, H2 in {N.ACTOR_H2}, relu / tanh")
+
+
+def arch_of_learner(policy) -> N.QuadActorArch:
+    """The QuadActorArch both of the module's nets share (FusedActor.arch_of on the policy net, the value net's
+    shapes checked against it); ValueError naming the family otherwise."""
+    try:
+        arch = FusedActor.arch_of(policy)
+        vnet = policy.mlp_extractor.value_net
+        lin = [m for m in vnet if isinstance(m, torch.nn.Linear)]
+        shapes = [tuple(l.weight.shape) for l in lin] + [tuple(policy.value_net.weight.shape)]
+        ok = len(vnet) == 4 and shapes == [(arch.h1, 12), (arch.h2, arch.h1), (1, arch.h2)] \
+            and tuple(policy.log_std.shape) == (4,)
+    except (ValueError, AttributeError, IndexError, TypeError):
+        ok = False
+    if not ok:
+        raise ValueError(f"the fused PPO gradient trains {LEARNER_FAMILY}")
+    return arch
+
+
+def fused_learner_for(policy, clip_range: float, ent_coef: float, vf_coef: float, normalize_advantage: bool = True):
+    """The fused minibatch gradient of `policy`: a FusedLearner for the 12-128-128 ReLU net (the specialised kernels,
+    the bits every existing path has), a FusedArchLearner for any other member of the family; ValueError naming the
+    family outside it."""
+    try:
+        FusedPolicy._check_shapes(policy)
+    except (ValueError, AttributeError, IndexError, TypeError):
+        arch_of_learner(policy)
+        return FusedArchLearner(policy, clip_range, ent_coef, vf_coef, normalize_advantage)
+    return FusedLearner(policy, clip_range, ent_coef, vf_coef, normalize_advantage)
 
 
 def adam_state(opt: torch.optim.Adam, params) -> list:

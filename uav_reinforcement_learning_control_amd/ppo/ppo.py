@@ -31,7 +31,7 @@ import torch.nn as nn
 from .. import _native as N
 from .fused import FusedPolicy, rollout_supported
 from .gae import gae
-from .learner import FusedAdam, FusedLearner
+from .learner import FusedAdam, FusedLearner, arch_of_learner, fused_learner_for
 from .policy import ActorCritic
 
 
@@ -50,13 +50,17 @@ class PPOConfig:
     max_grad_norm: float = 0.5
     normalize_advantage: bool = True
     net_arch: tuple = (128, 128)
-    activation: str = "relu"              # "relu" | "tanh" (SB3 activation_fn); tanh trains on the torch path
+    activation: str = "relu"              # "relu" | "tanh" (SB3 activation_fn); tanh trains on the torch path,
+    #                                       or its update on the general learner with fused_update_arch
     adam_eps: float = 1e-5
     fused_policy: bool = True             # rollout policy on the MFMA kernels (ppo/fused.py)
     fused_rollout: bool = True            # whole rollout as quad_rollout launches (needs fused_policy)
     rollout_chunk: int = 1024             # steps per quad_rollout launch
     fused_update: bool = True             # minibatch gradient on MFMA (ppo/learner.py, quad_ppo_grad)
     graph_update: bool = True             # single GPU: replay each epoch's optimizer steps as one hipGraph
+    # the update of any other member of the general actor's family (tanh, other widths) on quad_ppo_arch_grad
+    # (learner.fused_learner_for); needs fused_update; the rollout stays the torch per-step path. Opt-in
+    fused_update_arch: bool = False
 
 
 # quad_ppo_adv_stats_epoch's grid y limit is 65,535; its [n, 512] float64 output is 4 KB per
@@ -294,6 +298,13 @@ class PPO:
         self._learner = (FusedLearner(self.policy, self.cfg.clip_range, self.cfg.ent_coef, self.cfg.vf_coef,
                                       self.cfg.normalize_advantage)
                          if self.cfg.fused_update and fusable and self.device.type == "cuda" else None)
+        if self.cfg.fused_update_arch and not fusable:
+            if self.obs_dim != 12:
+                raise ValueError(f"fused_update_arch trains 12-D observations, got {self.obs_dim}")
+            arch_of_learner(self.policy)  # ValueError naming the family
+            if self.cfg.fused_update and self.device.type == "cuda":
+                self._learner = fused_learner_for(self.policy, self.cfg.clip_range, self.cfg.ent_coef,
+                                                  self.cfg.vf_coef, self.cfg.normalize_advantage)
         self._adam = FusedAdam(self.opt, self.cfg.max_grad_norm) if self._learner is not None else None
         self._epoch_graph: Optional[CapturedEpoch] = None  # _train_graphed's captured epoch
         self._t_host = 0  # running step counter of the one-launch path (keys the action noise)

@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from .envs import QuadVecEnv
 from .ppo import PPO, PPOConfig
+from .ppo.learner import ARCH_UPDATE_KEEP_TORCH
 
 
 def parse(argv=None):
@@ -37,8 +38,15 @@ def parse(argv=None):
     ap.add_argument("--learning-rate", type=float, default=PPOConfig.learning_rate)
     ap.add_argument("--net-arch", nargs=2, type=int, default=[128, 128], metavar=("H1", "H2"),
                     help="hidden widths of both MLPs (the reference's optimize.py: 128 128, 256 256, 512 256); "
-                         "anything but 128 128 relu trains on the torch path")
+                         "128 128 relu trains on its own fused kernels; every other net trains on the torch path,\n"
+                         "or with --fused-arch-update (H1 a multiple of 32 up to 512, H2 in 64 / 128 / 256) on the\n"
+                         "general fused update")
     ap.add_argument("--activation", default="relu", choices=["relu", "tanh"])
+    ap.add_argument("--fused-arch-update", action="store_true",
+                    help="compute each minibatch gradient of a net other than 128 128 relu in fused launches\n"
+                         "(quad_ppo_arch_grad) and step Adam with quad_clip_adam instead of torch autograd; the rollout\n"
+                         "stays the torch per-step path. Off by default; a (net, activation, batch size) the fused\n"
+                         "form did not win in profiles/arch_update (ARCH_UPDATE_KEEP_TORCH) keeps the torch update")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-dir", default="./logs")
     ap.add_argument("--model-dir", default="./models_trained")
@@ -87,6 +95,7 @@ def run_config(a, env, cfg, model, world, stamp) -> dict:
                 "activation_fn": {"relu": "ReLU", "tanh": "Tanh"}[cfg.activation]},
         "env": a.env,
         "backend": "uav_reinforcement_learning_control_amd (MI355X kernels)",
+        **({"fused_arch_update": True} if cfg.fused_update_arch else {}),
     }
 
 
@@ -165,9 +174,22 @@ def main(argv=None):
     wrapper = None if a.wrapper == "none" else a.wrapper
     env = QuadVecEnv(a.num_envs, env=a.env, wrapper=wrapper, device=f"cuda:{local}",
                      seed=a.seed, env_id_base=rank * a.num_envs)
+    arch_update = a.fused_arch_update
+    batch = max(1, a.num_envs * a.n_steps // a.n_minibatches)  # PPO's own derivation
+    if arch_update and (tuple(a.net_arch), a.activation, batch) in ARCH_UPDATE_KEEP_TORCH:
+        arch_update = False
+        if rank == 0:
+            print(f"update: --fused-arch-update keeps the torch update for net {tuple(a.net_arch)} {a.activation}, "
+                  f"batch size {batch} (ARCH_UPDATE_KEEP_TORCH: the fused form did not win that row)", flush=True)
     cfg = PPOConfig(learning_rate=a.learning_rate, n_steps=a.n_steps, n_epochs=a.n_epochs,
-                    n_minibatches=a.n_minibatches, net_arch=tuple(a.net_arch), activation=a.activation)
+                    n_minibatches=a.n_minibatches, net_arch=tuple(a.net_arch), activation=a.activation,
+                    fused_update_arch=arch_update)
     model = PPO(env, cfg, seed=a.seed)
+    if arch_update and rank == 0:
+        form = type(model._learner).__name__ if model._learner is not None else "torch"
+        print(f"update: fused minibatch gradient for net {tuple(a.net_arch)} {a.activation} ({form}: "
+              f"{'quad_ppo_arch_grad' if form == 'FusedArchLearner' else 'quad_ppo_grad'} + quad_clip_adam, "
+              f"batch size {model.batch}){'; torch per-step rollout' if model._fp is None else ''}", flush=True)
     if a.resume:
         model.load_state_dict(torch.load(a.resume, map_location=env.device, weights_only=True))
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
