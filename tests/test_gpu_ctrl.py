@@ -119,10 +119,10 @@ def _edge_states(env, kind):
     """A handful of envs just inside a position bound and moving outward: they terminate within a few
     steps whatever the controller does."""
     st = env.get_state()
-    bound = 3.0 if kind == "trajectory" else 2.0
+    d = 1.2 * env.dt  # 0.012 m at the default time step: 0.8 of a step at 1.5 m/s
     for j, i in enumerate((3, 64, 65, 127, 129)):
         ax = j % 2
-        st["qpos"][i, ax] = bound - 0.012 * (j + 1)
+        st["qpos"][i, ax] = float(env.cfg.term_high[ax]) - d * (j + 1)  # (2 m hover, 3 m trajectory at the defaults)
         st["qvel"][i, ax] = 1.5
         st["qpos"][i, 3:7] = (1, 0, 0, 0)
     env.set_state(qpos=st["qpos"], qvel=st["qvel"])

@@ -52,21 +52,23 @@ def euler_of_quat(qpos):
     return O.quat_to_euler_batch(np.atleast_2d(np.asarray(qpos, np.float64))[:, 3:7]).astype(np.float32)
 
 
-def obs_euler_of_quat(qpos):
-    """obs[3:6] of those angles: normalize (utils/normalization.py:7-17) in float32, NumPy's order."""
+def obs_euler_of_quat(qpos, obs_bounds=None):
+    """obs[3:6] of those angles: normalize (utils/normalization.py:7-17) in float32, NumPy's order.
+    obs_bounds = (obs_low, obs_high) of a handle whose bounds are not the defaults."""
     e = euler_of_quat(qpos)
-    lo, hi = OBS_LOW[3:6], OBS_HIGH[3:6]
+    low, high = (OBS_LOW, OBS_HIGH) if obs_bounds is None else (np.asarray(b, np.float32) for b in obs_bounds)
+    lo, hi = low[3:6], high[3:6]
     return (np.float32(2) * (e - lo)) / (hi - lo) - np.float32(1)
 
 
-def euler_ok(got_s12, got_obs, got_qpos, ref_qpos):
+def euler_ok(got_s12, got_obs, got_qpos, ref_qpos, obs_bounds=None):
     """Per row: (i) the quaternion vs the oracle's and (ii) the Euler columns of state12 (and of obs,
     unless got_obs is None) vs the conversion of the kernel's own quaternion, at the plain bar."""
     gq = np.atleast_2d(got_qpos)
     ok = parity_ok(gq[:, 3:7], np.atleast_2d(ref_qpos)[:, 3:7])
     ok &= parity_ok(np.atleast_2d(got_s12)[:, 3:6], euler_of_quat(gq))
     if got_obs is not None:
-        ok &= parity_ok(np.atleast_2d(got_obs)[:, 3:6], obs_euler_of_quat(gq))
+        ok &= parity_ok(np.atleast_2d(got_obs)[:, 3:6], obs_euler_of_quat(gq, obs_bounds))
     return ok
 
 
@@ -100,7 +102,10 @@ def operand_only(got, ref, pre, rtol=1e-5, atol=1e-6):
     return int(only.sum()), outside
 
 
-def _random_states(n, rng, wide=True):
+def _random_states(n, rng, wide=True, kind=O.ENV_HOVER):
+    """kind: the voltage is drawn in the kind's [min_voltage, nominal_voltage] (7.6 .. 8.4 V hover, 13.2 ..
+    16.8 V trajectory). A trajectory env given a hover voltage clips to min_voltage on its first step, which
+    hides the sag constants vdrop_base / vdrop_load from every comparison."""
     qpos = np.zeros((n, 11), np.float32)
     qpos[:, :3] = rng.uniform([-1.9, -1.9, 0.05], [1.9, 1.9, 1.95], (n, 3))
     q = rng.normal(size=(n, 4))
@@ -111,7 +116,7 @@ def _random_states(n, rng, wide=True):
     qvel[:, :3] = rng.normal(0, s, (n, 3))
     qvel[:, 3:6] = rng.normal(0, 2 * s, (n, 3))
     qvel[:, 6:] = rng.normal(0, 10 * s, (n, 4))
-    volt = rng.uniform(7.6, 8.4, n).astype(np.float32)
+    volt = rng.uniform(*((13.2, 16.8) if kind == O.ENV_TRAJ else (7.6, 8.4)), n).astype(np.float32)
     tgt = rng.uniform([-1.5, -1.5, 0.3], [1.5, 1.5, 1.8], (n, 3)).astype(np.float32)
     step = rng.integers(0, 512, n).astype(np.int32)
     rint = rng.uniform(-0.01, 0.01, (n, 3)).astype(np.float32)
@@ -235,7 +240,7 @@ def test_kernel_form_selection(spec_mode):
 def test_step_matches_oracle_random_states(env_name, wrapper, kind, wrap, kernel_variant, spec_mode):
     n = 3000
     rng = np.random.default_rng(17 + kind * 2 + wrap)
-    st = _random_states(n, rng)
+    st = _random_states(n, rng, kind=kind)
     acts = rng.uniform(-1.3, 1.3, (n, 4)).astype(np.float32)
     env = _env(n, env_name, wrapper, auto_reset=False)
     g = _gpu_step(env, st, acts)
@@ -556,26 +561,10 @@ def test_relpos_wrapper_is_base_obs_plus_prev_action(env_name):
 
 
 def _spline_ref(seed, gid, episode, start, step, L=2048, dur=30.0):
-    """TrajectoryFollowEnv._sample_sinusoid_trajectory restated with scipy (the device draw map:
-    Philox blocks 4..8 of the episode's reset counter)."""
-    from scipy.interpolate import CubicSpline
-    r = []
-    for blk in range(5):
-        r += O.philox([gid & 0xFFFFFFFF, gid >> 32, episode, 4 + blk], [seed & 0xFFFFFFFF, seed >> 32])
-    u = lambda x: np.float32((x >> 8) * 2.0 ** -24)
-    aff = lambda lo, uu, span: np.float32(np.float32(lo) + np.float32(uu * np.float32(span)))
-    nwp = 3 + (((r[3] >> 8) * 3) >> 24)
-    lo, hi, amp = [-1.0, -1.0, 0.4], [1.0, 1.0, 1.4], [0.6, 0.6, 0.4]
-    t = np.linspace(0.0, dur, L)[min(step - 1, L - 1)]
-    out = np.zeros(9)
-    for ax in range(3):
-        center = float(aff(lo[ax], u(r[ax]), np.float32(hi[ax]) - np.float32(lo[ax])))
-        y = np.array([center + float(aff(-amp[ax], u(r[4 + 5 * ax + i]), np.float32(2 * np.float32(amp[ax]))))
-                      for i in range(nwp)])
-        y[0] = float(start[ax])
-        cs = CubicSpline(np.linspace(0.0, dur, nwp), y, bc_type="natural")
-        out[ax], out[3 + ax], out[6 + ax] = cs(t), cs.derivative(1)(t), cs.derivative(2)(t)
-    return out
+    """TrajectoryFollowEnv._sample_sinusoid_trajectory restated with scipy at the reference's spline
+    constants (cfg_cases.spline_ref)."""
+    from cfg_cases import spline_ref
+    return spline_ref(seed, gid, episode, start, step, L=L, dur=dur)
 
 
 def test_trajectory_info_spline_matches_scipy():

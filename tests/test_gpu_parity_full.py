@@ -55,7 +55,7 @@ def _batch(golden_dir, fixture, kind, wrap, n=N_FULL):
     """Golden pre-states + actions in the first rows, random states after (see module doc)."""
     d = np.load(os.path.join(golden_dir, f"golden_{fixture}.npz"))
     rng = np.random.default_rng(1000 + 10 * kind + wrap)
-    st = _random_states(n, rng)
+    st = _random_states(n, rng, kind=kind)
     acts = rng.uniform(-1.2, 1.2, (n, 4)).astype(np.float32)
     ng = len(d["action"])
     for f, k in (("qpos", "pre_qpos"), ("qvel", "pre_qvel"), ("voltage", "pre_voltage"),
@@ -76,9 +76,10 @@ def _env(env_name, wrapper, auto_reset):
     return env, N.lib().quad_kernel_form(env._h)
 
 
-def _check_rows(g, ref, st, rows, what):
+def _check_rows(g, ref, st, rows, what, obs_bounds=None):
     """The suite's bar on `rows` (vectorized); returns the failing row indices (and prints, for
-    each, the fields that fail with got / oracle / pre-step values)."""
+    each, the fields that fail with got / oracle / pre-step values). obs_bounds = (obs_low, obs_high)
+    of a handle whose observation bounds are not the defaults."""
     ok = np.ones(len(rows), bool)
     fails = {}
 
@@ -105,7 +106,7 @@ def _check_rows(g, ref, st, rows, what):
             # (reset rows carry the reset obs in both and are compared bit-exactly elsewhere); the
             # Euler columns against the conversion of the kernel's own quaternion (test_gpu_parity)
             note(k, parity_ok(g["obs"][rows][:, NON_EULER], ref["obs"][rows][:, NON_EULER]))
-            note("obs-euler", parity_ok(g["obs"][rows][:, 3:6], obs_euler_of_quat(g["qpos"][rows])))
+            note("obs-euler", parity_ok(g["obs"][rows][:, 3:6], obs_euler_of_quat(g["qpos"][rows], obs_bounds)))
             note("quat", parity_ok(g["qpos"][rows][:, 3:7], ref["qpos"][rows][:, 3:7]))
         else:
             gk, rk = g[k][rows], ref[k][rows]

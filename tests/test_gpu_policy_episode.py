@@ -129,12 +129,13 @@ def test_deploy_obs_matches_the_fixture_and_the_ref(n):
 
 # ---------------------------------------------------------------------------------------------
 def _inject(env, kind, n):
-    """Envs just inside the x / y position bound, moving outward at 1.5 m/s (0.015 m per step)."""
+    """Envs just inside the x / y position bound, moving outward at 1.5 m/s (0.015 m per step at the default
+    time step). The bound and the time step are the handle's (2 m for hover, 3 m for trajectory at the defaults)."""
     st = env.get_state()
-    bound = 3.0 if kind == "trajectory" else 2.0
+    bound, d = env.cfg.term_high, 1.5 * env.dt
 
     def put(i, steps, ax=0):
-        st["qpos"][i, ax] = bound - 0.015 * steps + 0.0075
+        st["qpos"][i, ax] = float(bound[ax]) - d * steps + d / 2
         st["qvel"][i, ax] = 1.5
         st["qpos"][i, 3:7] = (1, 0, 0, 0)
 

@@ -46,10 +46,11 @@ def fp():
     return f
 
 
-def _sets():
+def _sets(bound=2.0, d=0.015):
+    """bound, d: the handle's x position bound and its metres per step at 1.5 m/s (the defaults' values)."""
     start = np.array([0.3, -0.2, 1.0])
     off = np.array([[0.0, 0.0, 0.0], [0.02, 0.0, 0.0], [0.0, 0.02, 0.01], [-0.02, 0.01, 0.0], [0.01, -0.02, 0.0]])
-    edge = np.array([[2.0 - 0.015 * 3 + 0.0075, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 1.0, 1.0]])  # PE._inject's rule
+    edge = np.array([[bound - d * 3 + d / 2, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 1.0, 1.0]])  # PE._inject's rule
     return [start[None] + 0.1, start + off[:2], start + off[:3], start + off[:5], make_trajectory("square", spacing=0.5),
             edge]
 
@@ -68,7 +69,8 @@ def _start(n, wrapper, limit, set_of=None, radius=RADIUS, sets=None, seed=11):
     env = QuadVecEnv(n, wrapper=wrapper, device=DEV, seed=seed, max_episode_steps=limit, auto_reset=False)
     env.reset()
     so = _set_of(n) if set_of is None else set_of
-    course = WaypointCourse(_sets() if sets is None else sets, n, radius, DEV, set_of=so)
+    course = WaypointCourse(_sets(float(env.cfg.term_high[0]), 1.5 * env.dt) if sets is None else sets, n, radius, DEV,
+                            set_of=so)
     course.begin(env)
     if sets is None and (so == EDGE).any():
         st = env.get_state()
