@@ -872,6 +872,34 @@ int quad_ppo_arch_grad(const QuadActorArch* arch, const QuadPolicyParams* params
 int quad_ppo_hidden(const QuadPolicyParams* params, const QuadPPOBatch* b, const QuadPolicyGrads* grads,
                     float* hidden, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The rollout of the general actor's family: quad_policy_pack / quad_policy_act / quad_rollout_post /
+ * quad_rollout for a policy net 12 -> h1 -> h2 -> 4 and a value net 12 -> h1 -> h2 -> 1 of the same widths and
+ * activation (QuadPolicyParams with the arch's shapes, as quad_ppo_arch_grad reads it), on quad_actor_act's forward.
+ * The packed image is quad_actor_pack's image of the policy net (to the bit), then the value net's image in the same
+ * layout (a head of four outputs whose rows 1..3 are zero), then log_std[4]: 2 quad_actor_packed_floats + 4 floats.
+ *   quad_actor_critic_act   quad_policy_act's semantics for QuadPolicyAct, field for field: the draw
+ *                           Philox(seed; env_id_base + env, t, 0x200) + Box-Muller, a = mean + exp(log_std) z, the
+ *                           log-prob recomputed from the stored a, actions_env = clip(a), every row pointer optional,
+ *                           the cursor protocol, the fused epilogue of step t-1, deterministic. The mean is
+ *                           quad_actor_act's, bit for bit.
+ *   quad_actor_critic_post  quad_rollout_post.
+ *   quad_actor_rollout      quad_rollout for QuadRollout: a handle with env_kind HOVER or TRAJ, wrapper NONE or CTBR,
+ *                           auto_reset = 1; every row pointer required; last_obs / last_start / ep_ret / ep_len carried
+ *                           across calls, stats accumulated; bit-identical to quad_actor_critic_act with the epilogue
+ *                           + quad_step per step, then quad_actor_critic_post, with cursor t = t0.
+ * QUAD_EINVAL with nothing launched and nothing written: an arch outside the family
+ * (quad_actor_critic_packed_floats: < 0), a handle of another kind or wrapper, auto_reset = 0, rows < 1, steps < 1,
+ * t0 < 0, a NULL required pointer, packed / actions / obs_copy / last_obs not 16-byte aligned.
+ * The added entry points did not change the ABI version. */
+int64_t quad_actor_critic_packed_floats(const QuadActorArch* arch);
+int quad_actor_critic_pack(const QuadActorArch* arch, const QuadPolicyParams* p, float* packed, void* stream);
+int quad_actor_critic_act(const QuadActorArch* arch, const float* packed, const QuadPolicyAct* a, int32_t n,
+                          void* stream);
+int quad_actor_critic_post(const QuadActorArch* arch, const float* packed, const QuadRolloutPost* p, uint32_t* cursor,
+                           int32_t n, void* stream);
+int quad_actor_rollout(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadRollout* r,
+                       void* stream);
+
 /* ---- PPO populations in lock-step launches (added within ABI v8, whose number an
  * existing layout test pins: a v8 library built before these entry points lacks the quad_pop_* exports, and the
  * Python binding says so when it loads one): P independent small learners that share

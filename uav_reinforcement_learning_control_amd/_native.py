@@ -260,7 +260,9 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_actor_waypoints",
            "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode",
            "quad_brax_actor_sample", "quad_brax_unroll", "quad_brax_ppo_workspace_bytes", "quad_brax_ppo_grad",
-           "quad_ppo_arch_workspace_bytes", "quad_ppo_arch_grad")
+           "quad_ppo_arch_workspace_bytes", "quad_ppo_arch_grad",
+           "quad_actor_critic_packed_floats", "quad_actor_critic_pack", "quad_actor_critic_act",
+           "quad_actor_critic_post", "quad_actor_rollout")
 
 
 class QuadRollout(C.Structure):
@@ -423,6 +425,16 @@ def _declare(L):
     L.quad_ppo_arch_grad.argtypes = [arch, C.POINTER(QuadPolicyParams), C.POINTER(QuadPPOBatch),
                                      C.POINTER(QuadPolicyGrads), vp, C.c_int64, vp]
     L.quad_ppo_arch_grad.restype = C.c_int
+    if not hasattr(L, "quad_actor_rollout"):  # nor with the general family's rollout
+        raise QuadError(f"{LIB_PATH} was built before the general rollout's entry points (quad_actor_rollout); rebuild it")
+    L.quad_actor_critic_packed_floats.argtypes = [arch]
+    L.quad_actor_critic_packed_floats.restype = C.c_int64
+    L.quad_actor_critic_pack.argtypes = [arch, C.POINTER(QuadPolicyParams), vp, vp]
+    L.quad_actor_critic_act.argtypes = [arch, vp, C.POINTER(QuadPolicyAct), i32, vp]
+    L.quad_actor_critic_post.argtypes = [arch, vp, C.POINTER(QuadRolloutPost), vp, i32, vp]
+    L.quad_actor_rollout.argtypes = [vp, arch, vp, C.POINTER(QuadRollout), vp]
+    for n in ("quad_actor_critic_pack", "quad_actor_critic_act", "quad_actor_critic_post", "quad_actor_rollout"):
+        getattr(L, n).restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
     L.quad_pop_detach_eval.argtypes = [vp]

@@ -9,7 +9,9 @@ statistics) -- instead of ~25 torch kernels. The torch ActorCritic stays the tra
 
 `FusedPolicy` is the 12-128-128 ReLU net of the training kernels. `FusedActor` is the deterministic actor of any
 other supported architecture (quad_actor_*: 12-H1-H2-4, ReLU or tanh) for evaluation episodes and waypoint laps;
-`fused_actor_for(policy)` picks between the two. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
+`fused_actor_for(policy)` picks between the two. `FusedActorCritic` is the rollout policy of that family (policy and
+value net, quad_actor_critic_* / quad_actor_rollout) behind FusedPolicy's interface; `fused_policy_for(policy)` picks
+between it and `FusedPolicy`. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
 21-H1-H2-8 behind the running statistics, ReLU / tanh / SiLU, NormalTanh sampling) for evaluation episodes of the
 brax env kinds and for the learner's unrolls (sample, unroll). `FusedBraxLearner` is the Brax profile's minibatch
 gradient and Adam step (quad_brax_ppo_grad, quad_clip_adam) for (128, 128) ReLU policy and value nets.
@@ -147,7 +149,17 @@ class FusedPolicy:
                             deterministic=int(bool(deterministic)), seed=int(seed) & (2**64 - 1),
                             env_id_base=int(env_id_base),
                             epilogue=C.pointer(epilogue) if epilogue is not None else None)
+        self._launch_act(a, n)
+
+    def _launch_act(self, a: N.QuadPolicyAct, n: int) -> None:
         N.check(N.lib().quad_policy_act(_p(self.packed), C.byref(a), n, current_stream(self.device)), "quad_policy_act")
+
+    def _launch_post(self, epilogue: N.QuadRolloutPost, cursor: torch.Tensor) -> None:
+        N.check(N.lib().quad_rollout_post(_p(self.packed), C.byref(epilogue), _p(cursor), epilogue._n,
+                                          current_stream(self.device)), "quad_rollout_post")
+
+    def _launch_rollout(self, env, r: N.QuadRollout) -> None:
+        N.check(N.lib().quad_rollout(env._h, _p(self.packed), C.byref(r), current_stream(self.device)), "quad_rollout")
 
     def value(self, obs: torch.Tensor, out: torch.Tensor, scratch: torch.Tensor) -> torch.Tensor:
         """V(obs) [N] into out ([1, N]) on the MFMA kernel: per-row results do not depend on the
@@ -179,8 +191,7 @@ class FusedPolicy:
     def post(self, epilogue: N.QuadRolloutPost, cursor: torch.Tensor) -> None:
         """quad_rollout_post: finish the pending step (end of a rollout)."""
         _need(cursor, (4,), torch.int32, self.device, "cursor")
-        N.check(N.lib().quad_rollout_post(_p(self.packed), C.byref(epilogue), _p(cursor), epilogue._n,
-                                          current_stream(self.device)), "quad_rollout_post")
+        self._launch_post(epilogue, cursor)
 
     def rollout(self, env, *, obs_copy, actions, log_prob, value, episode_starts, rewards, last_obs,
                 last_start, ep_ret, ep_len, stats, t0: int, steps: int, seed: int, gamma: float,
@@ -205,7 +216,7 @@ class FusedPolicy:
                           rows=int(rows), t0=int(t0), steps=int(steps),
                           deterministic=int(bool(deterministic)), seed=int(seed) & (2**64 - 1),
                           gamma=float(gamma))
-        N.check(N.lib().quad_rollout(env._h, _p(self.packed), C.byref(r), current_stream(self.device)), "quad_rollout")
+        self._launch_rollout(env, r)
 
     def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
                 max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
@@ -315,6 +326,107 @@ class FusedActor:
         N.check(N.lib().quad_actor_waypoints(env._h, C.byref(self.arch), _p(self.packed), C.byref(run), C.byref(wr),
                                              current_stream(self.device)), "quad_actor_waypoints")
         return res
+
+
+_ARCH_ROLLOUT_FAMILY = ("the general MFMA rollout collects 12-H1-H2-(4|1) policy and value nets of the same widths "
+                        f"(H1 a multiple of 32 up to 512, H2 in {N.ACTOR_H2}, relu / tanh)")
+
+
+class FusedActorCritic(FusedPolicy):
+    """Packed image of an ActorCritic of any member of the general actor's family (policy net 12 -> H1 -> H2 -> 4 and
+    value net 12 -> H1 -> H2 -> 1 of the same widths and activation) for the rollout kernels of
+    csrc/actor_rollout.hip (quad_actor_critic_* / quad_actor_rollout). FusedPolicy's interface and argument checks
+    (pack, act, value, make_epilogue, post, rollout) on this family's launches. The forward-only launches (episode,
+    waypoints) are FusedActor's."""
+
+    @staticmethod
+    def arch_of(policy) -> N.QuadActorArch:
+        """The module's QuadActorArch, the value net's shapes checked too; ValueError outside the family."""
+        try:
+            arch = FusedActor.arch_of(policy)
+            vnet = policy.mlp_extractor.value_net
+            vlin = [m for m in vnet if isinstance(m, torch.nn.Linear)]
+            shapes = [tuple(l.weight.shape) for l in vlin] + [tuple(policy.value_net.weight.shape)]
+            ok = len(vlin) == 2 and len(vnet) == 4 and shapes == [(arch.h1, 12), (arch.h2, arch.h1), (1, arch.h2)]
+        except (ValueError, AttributeError, IndexError, TypeError) as e:
+            raise ValueError(f"{_ARCH_ROLLOUT_FAMILY}: {e}") from None
+        if not ok:
+            raise ValueError(f"{_ARCH_ROLLOUT_FAMILY}, got value net {shapes}")
+        return arch
+
+    def __init__(self, policy: ActorCritic):
+        self.arch = self.arch_of(policy)
+        self.policy = policy
+        self.device = policy.log_std.device
+        if self.device.type != "cuda":
+            raise N.QuadError("FusedActorCritic needs the policy on a ROCm GPU")
+        nf = N.lib().quad_actor_critic_packed_floats(C.byref(self.arch))
+        if nf <= 0:
+            raise N.QuadError("quad_actor_critic_packed_floats rejected the architecture")
+        self.packed = torch.empty(nf, dtype=torch.float32, device=self.device)
+
+    @torch.no_grad()
+    def pack(self) -> None:
+        ts = _ordered(self.policy)
+        for t in ts:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("policy parameters must be contiguous float32")
+        prm = N.QuadPolicyParams(*[t.data_ptr() for t in ts])
+        N.check(N.lib().quad_actor_critic_pack(C.byref(self.arch), C.byref(prm), _p(self.packed),
+                                               current_stream(self.device)), "quad_actor_critic_pack")
+
+    def _launch_act(self, a: N.QuadPolicyAct, n: int) -> None:
+        N.check(N.lib().quad_actor_critic_act(C.byref(self.arch), _p(self.packed), C.byref(a), n,
+                                              current_stream(self.device)), "quad_actor_critic_act")
+
+    def _launch_post(self, epilogue: N.QuadRolloutPost, cursor: torch.Tensor) -> None:
+        N.check(N.lib().quad_actor_critic_post(C.byref(self.arch), _p(self.packed), C.byref(epilogue), _p(cursor),
+                                               epilogue._n, current_stream(self.device)), "quad_actor_critic_post")
+
+    def _launch_rollout(self, env, r: N.QuadRollout) -> None:
+        N.check(N.lib().quad_actor_rollout(env._h, C.byref(self.arch), _p(self.packed), C.byref(r),
+                                           current_stream(self.device)), "quad_actor_rollout")
+
+    def episode(self, *a, **k):
+        raise NotImplementedError("FusedActorCritic collects rollouts; episodes fly on FusedActor (fused_actor_for)")
+
+    waypoints = episode
+
+
+def fused_policy_for(policy):
+    """The fused rollout policy of `policy`: a FusedPolicy for the 12-128-128 ReLU net (its own kernels, the bits
+    every existing path has), a FusedActorCritic for any other member of the family; ValueError naming the family
+    outside it."""
+    try:
+        FusedPolicy._check_shapes(policy)
+    except (ValueError, AttributeError, IndexError, TypeError):
+        FusedActorCritic.arch_of(policy)
+        return FusedActorCritic(policy)
+    return FusedPolicy(policy)
+
+
+# ((H1, H2), activation, num_envs) the drivers keep on the torch per-step rollout because the one-launch form did not
+# beat it in profiles/arch_rollout/bench.json (DESIGN 24, by 19's to 23's rule)
+ARCH_ROLLOUT_KEEP_TORCH = frozenset()
+
+
+def arch_rollout_keeps_torch(hidden, activation: str, num_envs: int) -> bool:
+    """Is this row in ARCH_ROLLOUT_KEEP_TORCH? The one place that forms the set's key (the driver asks before it
+    builds the policy; arch_rollout_supported asks for a built one)."""
+    return (tuple(int(x) for x in hidden), activation, int(num_envs)) in ARCH_ROLLOUT_KEEP_TORCH
+
+
+def arch_rollout_supported(policy, env) -> bool:
+    """The fused rollout of a net of the general family where quad_actor_rollout drives the env (rollout_supported),
+    the policy and value nets are members, and the row is not in ARCH_ROLLOUT_KEEP_TORCH."""
+    if not rollout_supported(env):
+        return False
+    try:
+        arch = FusedActorCritic.arch_of(policy)
+    except ValueError:
+        return False
+    return (policy.log_std.device.type == "cuda"
+            and not arch_rollout_keeps_torch((arch.h1, arch.h2), getattr(policy, "activation", "relu"), env.num_envs))
 
 
 def fused_actor_for(policy):

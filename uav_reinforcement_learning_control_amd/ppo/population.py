@@ -24,7 +24,8 @@ import torch
 
 from .. import _native as N
 from ..envs import QuadVecEnv
-from .fused import current_stream
+from .fused import FusedPolicy, current_stream
+from .learner import FusedLearner
 from .ppo import PPO, PPOConfig, RolloutStats
 
 
@@ -48,8 +49,9 @@ class PopulationPPO:
         c0 = members[0][0]
         total = c0.n_steps * int(n_envs)
         for cfg, _ in members:
-            if tuple(cfg.net_arch) != (128, 128):
-                raise ValueError(f"PopulationPPO runs the fused (128, 128) policy only, got net_arch {cfg.net_arch}")
+            if tuple(cfg.net_arch) != (128, 128) or cfg.activation != "relu":
+                raise ValueError(f"PopulationPPO runs the fused (128, 128) relu policy only, got net_arch "
+                                 f"{cfg.net_arch} {cfg.activation}")
             if not (cfg.fused_policy and cfg.fused_rollout and cfg.fused_update):
                 raise ValueError("PopulationPPO needs fused_policy, fused_rollout and fused_update")
             if cfg.n_steps != c0.n_steps:
@@ -77,7 +79,9 @@ class PopulationPPO:
         for cfg, seed in members:
             e = QuadVecEnv(self.n_envs, env=env, wrapper=wrapper, device=device, seed=int(seed), **kw)
             m = PPO(e, cfg, seed=int(seed))
-            if not m._one_launch or m._learner is None:
+            # exactly the 128-128 ReLU kernels' classes: the quad_pop_* launches read that packed image and that
+            # workspace (a FusedActorCritic / FusedArchLearner of the general family has another layout)
+            if not m._one_launch or type(m._fp) is not FusedPolicy or type(m._learner) is not FusedLearner:
                 raise ValueError("the env / policy is not one the fused rollout and update run")
             self.members.append(m)
             # PPO.__init__ leaves torch's default CPU generator at manual_seed(seed); the stand-alone run then

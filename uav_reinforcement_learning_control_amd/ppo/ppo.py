@@ -29,7 +29,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import _native as N
-from .fused import FusedPolicy, rollout_supported
+from .fused import FusedActorCritic, FusedPolicy, rollout_supported
 from .gae import gae
 from .learner import FusedAdam, FusedLearner, arch_of_learner, fused_learner_for
 from .policy import ActorCritic
@@ -61,6 +61,10 @@ class PPOConfig:
     # the update of any other member of the general actor's family (tanh, other widths) on quad_ppo_arch_grad
     # (learner.fused_learner_for); needs fused_update; the rollout stays the torch per-step path. Opt-in
     fused_update_arch: bool = False
+    # the rollout of any other member of that family on quad_actor_critic_act / quad_actor_rollout
+    # (fused.FusedActorCritic); one launch per chunk with fused_rollout, else two launches per step. Opt-in,
+    # independent of fused_update_arch; like the 128-128 ReLU net's kernels it needs fused_policy (False: torch)
+    fused_rollout_arch: bool = False
 
 
 # quad_ppo_adv_stats_epoch's grid y limit is 65,535; its [n, 512] float64 output is 4 KB per
@@ -282,10 +286,17 @@ class PPO:
         # fused path: cursor {t, pending} (buffer row = t % n_steps; t keys the action noise),
         # per-block episode-statistic slots, the epilogue descriptor
         # (the MFMA training kernels are built for the 12-D HoverEnv obs and 128-128 ReLU nets; any other config
-        # trains on the torch path, and its evaluations fly on the general actor: fused.fused_actor_for)
+        # trains on the torch path -- or, opted in, on the general family's kernels: fused_rollout_arch,
+        # fused_update_arch -- and its evaluations fly on the general actor: fused.fused_actor_for)
         fusable = (self.obs_dim == 12 and tuple(self.cfg.net_arch) == (128, 128) and self.cfg.activation == "relu"
                    and getattr(self.policy, "activation", "relu") == "relu")
         self._fp = FusedPolicy(self.policy) if self.cfg.fused_policy and fusable else None
+        if self.cfg.fused_rollout_arch and not fusable:
+            if self.obs_dim != 12:
+                raise ValueError(f"fused_rollout_arch collects 12-D observations, got {self.obs_dim}")
+            FusedActorCritic.arch_of(self.policy)  # ValueError naming the family
+            if self.cfg.fused_policy and self.device.type == "cuda":
+                self._fp = FusedActorCritic(self.policy)
         self._cursor = torch.zeros(4, dtype=torch.int32, device=self.device)
         self._slots = torch.zeros(N.POLICY_STAT_SLOTS, 3, dtype=torch.float64, device=self.device)
         if self._fp is not None:

@@ -22,6 +22,7 @@ import torch.distributed as dist
 
 from .envs import QuadVecEnv
 from .ppo import PPO, PPOConfig
+from .ppo.fused import FusedActorCritic, arch_rollout_keeps_torch
 from .ppo.learner import ARCH_UPDATE_KEEP_TORCH
 
 
@@ -45,8 +46,15 @@ def parse(argv=None):
     ap.add_argument("--fused-arch-update", action="store_true",
                     help="compute each minibatch gradient of a net other than 128 128 relu in fused launches\n"
                          "(quad_ppo_arch_grad) and step Adam with quad_clip_adam instead of torch autograd; the rollout\n"
-                         "stays the torch per-step path. Off by default; a (net, activation, batch size) the fused\n"
-                         "form did not win in profiles/arch_update (ARCH_UPDATE_KEEP_TORCH) keeps the torch update")
+                         "stays the torch per-step path unless --fused-arch-rollout is given. Off by default; a (net,\n"
+                         "activation, batch size) the fused form did not win in profiles/arch_update\n"
+                         "(ARCH_UPDATE_KEEP_TORCH) keeps the torch update")
+    ap.add_argument("--fused-arch-rollout", action="store_true",
+                    help="collect the rollouts of a net other than 128 128 relu in fused launches (quad_actor_rollout:\n"
+                         "policy, env step, bootstrap and statistics of a whole chunk of steps in one launch) instead of\n"
+                         "the torch per-step path. Off by default; independent of --fused-arch-update; a (net,\n"
+                         "activation, num_envs) the fused form did not win in profiles/arch_rollout\n"
+                         "(ARCH_ROLLOUT_KEEP_TORCH) keeps the torch rollout")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-dir", default="./logs")
     ap.add_argument("--model-dir", default="./models_trained")
@@ -96,6 +104,7 @@ def run_config(a, env, cfg, model, world, stamp) -> dict:
         "env": a.env,
         "backend": "uav_reinforcement_learning_control_amd (MI355X kernels)",
         **({"fused_arch_update": True} if cfg.fused_update_arch else {}),
+        **({"fused_arch_rollout": True} if isinstance(model._fp, FusedActorCritic) else {}),  # the flag, in effect
     }
 
 
@@ -181,10 +190,24 @@ def main(argv=None):
         if rank == 0:
             print(f"update: --fused-arch-update keeps the torch update for net {tuple(a.net_arch)} {a.activation}, "
                   f"batch size {batch} (ARCH_UPDATE_KEEP_TORCH: the fused form did not win that row)", flush=True)
+    arch_rollout = a.fused_arch_rollout
+    if arch_rollout and arch_rollout_keeps_torch(a.net_arch, a.activation, a.num_envs):
+        arch_rollout = False
+        if rank == 0:
+            print(f"rollout: --fused-arch-rollout keeps the torch rollout for net {tuple(a.net_arch)} {a.activation}, "
+                  f"{a.num_envs} envs (ARCH_ROLLOUT_KEEP_TORCH: the fused form did not win that row)", flush=True)
     cfg = PPOConfig(learning_rate=a.learning_rate, n_steps=a.n_steps, n_epochs=a.n_epochs,
                     n_minibatches=a.n_minibatches, net_arch=tuple(a.net_arch), activation=a.activation,
-                    fused_update_arch=arch_update)
+                    fused_update_arch=arch_update, fused_rollout_arch=arch_rollout)
     model = PPO(env, cfg, seed=a.seed)
+    if arch_rollout and rank == 0:
+        if isinstance(model._fp, FusedActorCritic):
+            print(f"rollout: fused rollout for net {tuple(a.net_arch)} {a.activation} (FusedActorCritic: "
+                  f"{'quad_actor_rollout, one launch per chunk' if model._one_launch else 'two launches per step'})",
+                  flush=True)
+        else:  # the 128 128 relu net keeps its own kernels; a CPU device or fused_policy off keeps torch
+            print(f"rollout: --fused-arch-rollout changes nothing for net {tuple(a.net_arch)} {a.activation} here ("
+                  f"{'FusedPolicy, its own kernels' if model._fp is not None else 'the torch per-step path'})", flush=True)
     if arch_update and rank == 0:
         form = type(model._learner).__name__ if model._learner is not None else "torch"
         print(f"update: fused minibatch gradient for net {tuple(a.net_arch)} {a.activation} ({form}: "
