@@ -988,6 +988,30 @@ int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals);
 int quad_pop_detach_eval(QuadPop* pop);
 int quad_pop_episode(QuadPop* pop, int32_t subset, void* stream);
 
+/* ---- Populations of the general actor's family (added within ABI v8 as the entry points above were):
+ * the same QuadPop, QuadPopMember and launch calls for P learners that share one QuadActorArch -- policy net
+ * 12 -> h1 -> h2 -> 4 and value net 12 -> h1 -> h2 -> 1, h1 a multiple of 32 up to 512, h2 in {64, 128, 256}, ReLU or
+ * tanh. A member's params / grads are read with the arch's shapes and its packed image holds
+ * quad_actor_critic_packed_floats(arch) floats. On such a population
+ *   quad_pop_pack            is quad_actor_critic_pack(arch, params -> packed)
+ *   quad_pop_rollout         is quad_actor_rollout(env, arch, packed, rollout with the given t0 / steps); block b of a
+ *                            member's launch holds 64 envs and adds its episode statistics into
+ *                            rollout.stats[b % QUAD_POLICY_STAT_SLOTS]: with more than 64 envs sum the slots
+ *   quad_pop_value           is quad_actor_critic_act(deterministic, rows = 1): V(rollout.last_obs) -> last_values
+ *   quad_pop_ppo_grad        is quad_ppo_arch_grad with QUAD_ADV_GIVEN on minibatch `slot` of the epoch
+ *   quad_pop_attach_eval / quad_pop_episode are quad_actor_episode (env-observation mode) on the policy half of the
+ *                            member's image (its first quad_actor_packed_floats(arch) floats)
+ * and quad_pop_gae / _permutation / _adv_stats_epoch / _clip_adam / _subset / _detach_eval / _destroy are what they
+ * are above; every launch call stays free of allocations, copies and synchronization. */
+/* Device workspace (bytes) one member needs: quad_ppo_arch_workspace_bytes(arch, batch), then the gradient-norm
+ * partials. 0 on invalid arguments (an arch outside the family, batch < 1 or > 8192, an invalid QuadAdam). */
+int64_t quad_pop_arch_workspace_bytes(const QuadActorArch* arch, const QuadAdam* adam, int32_t batch);
+/* quad_pop_create for the family. QUAD_EINVAL (nothing allocated, nothing launched, *out = NULL) for an arch outside
+ * the family, anything quad_pop_create rejects in a member (QUADENV_LEARNER aside), Adam tensors whose sizes are not
+ * the 13 of the arch's module, and a workspace smaller than quad_pop_arch_workspace_bytes. */
+int quad_pop_create_arch(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
+                         int32_t normalize_advantage, QuadPop** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -315,7 +315,9 @@ POP_EXPORTS = ("quad_pop_workspace_bytes", "quad_pop_create", "quad_pop_destroy"
                "quad_pop_rollout", "quad_pop_value", "quad_pop_gae", "quad_pop_permutation",
                "quad_pop_adv_stats_epoch", "quad_pop_ppo_grad", "quad_pop_clip_adam", "quad_pop_attach_eval",
                "quad_pop_detach_eval", "quad_pop_episode")
-EXPORTS = EXPORTS + POP_EXPORTS
+# the general family's populations: the same launch calls on a QuadPop of quad_pop_create_arch
+POP_ARCH_EXPORTS = ("quad_pop_arch_workspace_bytes", "quad_pop_create_arch")
+EXPORTS = EXPORTS + POP_EXPORTS + POP_ARCH_EXPORTS
 
 
 class QuadError(RuntimeError):
@@ -454,6 +456,13 @@ def _declare(L):
     for n in POP_EXPORTS[1:]:
         if n != "quad_pop_destroy":
             getattr(L, n).restype = C.c_int
+    if not hasattr(L, "quad_pop_create_arch"):  # nor with the general family's populations
+        raise QuadError(f"{LIB_PATH} was built before the general family's populations (quad_pop_create_arch); "
+                        "rebuild it")
+    L.quad_pop_arch_workspace_bytes.argtypes = [arch, C.POINTER(QuadAdam), i32]
+    L.quad_pop_arch_workspace_bytes.restype = C.c_int64
+    L.quad_pop_create_arch.argtypes = [arch, C.POINTER(QuadPopMember), i32, i32, i32, C.POINTER(vp)]
+    L.quad_pop_create_arch.restype = C.c_int
     for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
               "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode", "quad_deploy_obs",
               "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints"):

@@ -24,6 +24,7 @@
 #include "handle.h"
 #include "policy_episode.h"
 #include "policy_episode_body.h"
+#include "population.h"
 
 namespace quadenv {
 
@@ -32,6 +33,9 @@ namespace quadenv {
 template <int AKIND, int MB>
 hipError_t launch_actor_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, int obs_mode, const ActorNet& net,
                              const float* packed, const EpisodeArgs& a, const QuadWaypointRun* wr, hipStream_t s);
+template <int AKIND, int MB>  // (the episode kinds, 0 and 1)
+hipError_t launch_pop_actor_inst(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count,
+                                 int n, bool ctbr, const ActorNet& net, hipStream_t s);
 
 #if defined(AA_KIND)
 namespace {
@@ -72,9 +76,41 @@ __global__ __launch_bounds__(128) void k_actor_episode(const KConsts<float>* __r
   ArchForward<MB> fw{packed, net};
   episode_body<KIND, CTBR, 1, MODE, 64, false>(*kc, p, fw, a, nullptr);
 }
+
+// The population form (quad_pop_episode of a population of this family): env-observation mode; the member's entry is
+// read through pop::const_entry (population.h), its image the policy half of the member's actor-critic image
+template <int KIND, bool CTBR, int MB>
+__global__ __launch_bounds__(128) void k_pop_actor_episode(const KConsts<float>* __restrict__ kc,
+                                                           const PopEpisodeEntry* __restrict__ tab,
+                                                           const int32_t* __restrict__ active, actor::Net net) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (pop::const_entry, population.h)
+  const auto& en = pop::const_entry(tab, active[blockIdx.y]);
+  KParams p = en.kp;
+  p.kc = kc;
+  const EpisodeArgs a = en.a;
+  ArchForward<MB> fw{en.packed, net};
+  episode_body<KIND, CTBR, 1, QUAD_OBS_ENV, 64, false>(*kc, p, fw, a, nullptr);
+#endif
+}
 #endif
 
 }  // namespace
+
+#if AA_KIND != 2
+template <int AKIND, int MB>
+hipError_t launch_pop_actor_inst(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count,
+                                 int n, bool ctbr, const ActorNet& net, hipStream_t s) {
+  const actor::Net dn{net.nb1, net.actfn};
+  const int bytes = arch::Layout{net.nb1, MB}.lds_bytes();  // <= 64 KB: no opt-in
+  return with_bool(ctbr, [&](auto cb) {
+    hipLaunchKernelGGL((k_pop_actor_episode<AKIND, decltype(cb)::value, MB>), dim3((n + 63) / 64, count), dim3(128),
+                       bytes, s, kc, tab, active, dn);
+    return hipGetLastError();
+  });
+}
+template hipError_t launch_pop_actor_inst<AA_KIND, AA_MB>(const KConsts<float>*, const PopEpisodeEntry*, const int32_t*,
+                                                          int, int, bool, const ActorNet&, hipStream_t);
+#endif
 
 template <int AKIND, int MB>
 hipError_t launch_actor_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, int obs_mode, const ActorNet& net,
@@ -142,6 +178,19 @@ __global__ __launch_bounds__(actor::ACT_BLK) void k_actor_act(const float* __res
 int actor_net_of(const QuadActorArch* a, ActorNet* out) { return actor::net_of(a, "actor arch", false, out); }
 
 }  // namespace
+
+// the population form of quad_actor_episode (population.h); `arch` is one quad_pop_create_arch checked
+hipError_t pop::launch_pop_actor_episode(const QuadActorArch& arch, const KConsts<float>* kc, const PopEpisodeEntry* tab,
+                                         const int32_t* active, int count, int n, int env_kind, bool ctbr,
+                                         hipStream_t s) {
+  const ActorNet net{arch.h1 / 32, arch.h2 / 32, arch.activation};
+  return with_mb(net.mb, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    return env_kind == QUAD_ENV_TRAJ ? launch_pop_actor_inst<1, MB>(kc, tab, active, count, n, ctbr, net, s)
+                                     : launch_pop_actor_inst<0, MB>(kc, tab, active, count, n, ctbr, net, s);
+  });
+}
+
 }  // namespace quadenv
 
 using namespace quadenv;

@@ -293,7 +293,7 @@ __device__ __forceinline__ float weight(const float* w, int out, int n_out, int 
   return TORCH ? w[size_t(out) * n_in + in] : w[size_t(in) * n_out + out];
 }
 template <class LAY, bool TORCH, int NIN, class P>
-__global__ void k_pack(P p, int h1, int h2, float* __restrict__ out) {
+__device__ __forceinline__ void pack_body(const P& p, int h1, int h2, float* __restrict__ out) {
   constexpr int NOUT = LAY::NOUT;
   const LAY lay{h1 / 32, h2 / 32};
   const int nf = lay.w1p(), n1 = LAY::K1 * lay.nb1 * 64, n2 = lay.steps() * 64;
@@ -340,9 +340,17 @@ __global__ void k_pack(P p, int h1, int h2, float* __restrict__ out) {
   for (int q = 0; q < 3; q++) dst[q * 64] = x.p[q];
 }
 template <class LAY, bool TORCH, int NIN, class P>
+__global__ void k_pack(P p, int h1, int h2, float* __restrict__ out) {
+  pack_body<LAY, TORCH, NIN>(p, h1, h2, out);
+}
+// the grid of k_pack and of its population form (actor_rollout.hip)
+template <class LAY>
+inline int pack_blocks(const LAY& lay) {
+  return (lay.w1p() + (LAY::K1 * lay.nb1 + lay.steps()) * 64 + 255) / 256;
+}
+template <class LAY, bool TORCH, int NIN, class P>
 hipError_t launch_pack(const LAY& lay, const P& p, float* packed, hipStream_t s) {
-  const int threads = lay.w1p() + (LAY::K1 * lay.nb1 + lay.steps()) * 64;
-  hipLaunchKernelGGL((k_pack<LAY, TORCH, NIN, P>), dim3((threads + 255) / 256), dim3(256), 0, s, p, lay.nb1 * 32,
+  hipLaunchKernelGGL((k_pack<LAY, TORCH, NIN, P>), dim3(pack_blocks(lay)), dim3(256), 0, s, p, lay.nb1 * 32,
                      lay.mb * 32, packed);
   return hipGetLastError();
 }

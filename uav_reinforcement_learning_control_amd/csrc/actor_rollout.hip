@@ -21,6 +21,10 @@
 //                               of two one-tile waves, env state and observation in registers for all steps, both
 //                               images' LDS parts staged once, the W2 pieces streamed from L2; a block with at most
 //                               32 envs runs its two nets on its two waves (split blocks, see the kernel)
+//   k_pop_ac_head, k_pop_ac_pack, k_pop_ac_value<MB>, k_pop_ac_rollout<KIND, CTBR, MB>
+//                               the population forms (population.h): the bodies of k_ac_head, the pack
+//                               kernel, k_ac_act and k_ac_rollout behind one more grid dimension, the member's
+//                               arguments read from a device table
 //
 // The sample, the log-prob, the reward row and the forward of either net are one definition each, used by both
 // forms, and this file is built with the episode objects' floating-point flags (-ffp-contract=on, no SLP
@@ -39,6 +43,7 @@
 #include "dispatch.h"
 #include "env_tiles.h"
 #include "handle.h"
+#include "population.h"
 #include "quad_physics.h"
 #include "rollout.h"
 
@@ -48,6 +53,10 @@ namespace quadenv {
 template <int AKIND, int MB>
 hipError_t launch_actor_rollout_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
                                      const float* packed, const RollArgs& a, hipStream_t s);
+template <int AKIND, int MB>
+hipError_t launch_pop_actor_rollout_inst(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active,
+                                         int count, int n, bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps,
+                                         hipStream_t s);
 
 namespace {
 
@@ -162,14 +171,13 @@ __device__ __forceinline__ void store_row(float* __restrict__ base, size_t row, 
   b4[2] = make_float4(v[8], v[9], v[10], v[11]);
 }
 
+// k_ac_rollout's body, shared with the population form below (p.kc is the launch's noalias constant block)
 template <int KIND, bool CTBR, int MB>
-__global__ __launch_bounds__(128) void k_ac_rollout(const KConsts<float>* __restrict__ kc, KParams p,
-                                                    const float* __restrict__ packed, actor::Net net, RollArgs a) {
+__device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams p, const float* __restrict__ packed,
+                                                actor::Net net, RollArgs a) {
   extern __shared__ float lds[];
   __shared__ uint32_t renv[2][64], rep[2][64];
   __shared__ float4 xmean[2][32];
-  p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
-  const KConsts<float>& K = *kc;
   const arch::Layout lay{net.nb1, MB};
   const int w = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));  // a scalar: it selects the wave's nets
   const bool h = (threadIdx.x & 32) != 0;
@@ -303,7 +311,53 @@ __global__ __launch_bounds__(128) void k_ac_rollout(const KConsts<float>* __rest
   }
 }
 
+template <int KIND, bool CTBR, int MB>
+__global__ __launch_bounds__(128) void k_ac_rollout(const KConsts<float>* __restrict__ kc, KParams p,
+                                                    const float* __restrict__ packed, actor::Net net, RollArgs a) {
+  p.kc = kc;  // noalias: constant-block loads stay scalar after the stores (see KParams)
+  ac_rollout_body<KIND, CTBR, MB>(*kc, p, packed, net, a);
+}
+
+// The population form (population.h): block (b, k) is block b of member active[k]'s rollout. As in k_pop_rollout the
+// member's entry is read through pop::const_entry, t0 / steps come with the launch, and the constant block -- the
+// same for every member, like the arch -- stays the noalias kernel argument.
+template <int KIND, bool CTBR, int MB>
+__global__ __launch_bounds__(128) void k_pop_ac_rollout(const KConsts<float>* __restrict__ kc,
+                                                        const pop::RollEntry* __restrict__ tab,
+                                                        const int32_t* __restrict__ active, actor::Net net, uint32_t t0,
+                                                        int32_t steps) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (pop::const_entry, population.h)
+  const auto& en = pop::const_entry(tab, active[blockIdx.y]);
+  KParams p = en.kp;
+  p.kc = kc;
+  RollArgs a = en.a;
+  a.t0 = t0;
+  a.steps = steps;
+  const float* __restrict__ packed = en.packed;
+  ac_rollout_body<KIND, CTBR, MB>(*kc, p, packed, net, a);
+#endif
+}
+
 }  // namespace
+
+template <int AKIND, int MB>
+hipError_t launch_pop_actor_rollout_inst(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active,
+                                         int count, int n, bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps,
+                                         hipStream_t s) {
+  const actor::Net dn{net.nb1, net.actfn};
+  constexpr int MAX_BYTES = 2 * arch::Layout{actor::MAX_H1 / 32, MB}.lds_bytes();  // (launch_actor_rollout_inst's rule)
+  const int bytes = 2 * arch::Layout{net.nb1, MB}.lds_bytes();
+  constexpr int KIND = AKIND == 1 ? QUAD_ENV_TRAJ : QUAD_ENV_HOVER;
+  const dim3 grid((n + 63) / 64, count), block(128);
+  return with_bool(ctbr, [&](auto cb) {
+    constexpr bool CB = decltype(cb)::value;
+    if (const hipError_t e = lds_opt_in<&k_pop_ac_rollout<KIND, CB, MB>>(MAX_BYTES)) return e;
+    return launch_lds<&k_pop_ac_rollout<KIND, CB, MB>>(grid, block, bytes, s, kc, tab, active, dn, t0, steps);
+  });
+}
+template hipError_t launch_pop_actor_rollout_inst<AR_KIND, AR_MB>(const KConsts<float>*, const pop::RollEntry*,
+                                                                  const int32_t*, int, int, bool, const ActorNet&,
+                                                                  uint32_t, int32_t, hipStream_t);
 
 template <int AKIND, int MB>
 hipError_t launch_actor_rollout_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
@@ -341,12 +395,33 @@ struct HeadArgs {
   int32_t h2;
   int64_t image;  // A
 };
-__global__ void k_ac_head(HeadArgs a) {
+__device__ __forceinline__ void ac_head_body(const HeadArgs& a) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   const int nw = ACT * a.h2;
   if (idx < nw) a.packed[idx] = idx < a.h2 ? a.val_w[idx] : 0.f;
   else if (idx < nw + ACT) a.packed[idx] = idx == nw ? a.val_b[0] : 0.f;
   else if (idx < nw + 2 * ACT) a.packed[2 * a.image + (idx - nw - ACT)] = a.log_std[idx - nw - ACT];
+}
+__global__ void k_ac_head(HeadArgs a) { ac_head_body(a); }
+
+// what the pack kernel reads for one net of the module: 1 the value net, its head the padded one k_ac_head left in the
+// first floats of the image, 0 the policy net
+__host__ __device__ inline QuadActorParams net_params(const QuadPolicyParams& p, const float* packed, int h2, int net) {
+  return net ? QuadActorParams{p.vf_w0, p.vf_b0, p.vf_w1, p.vf_b1, packed, packed + ACT * h2}
+             : QuadActorParams{p.pi_w0, p.pi_b0, p.pi_w1, p.pi_b1, p.act_w, p.act_b};
+}
+
+// The population forms of the pack's three launches (population.h): block (b, k) is block b of member active[k]'s
+// launch; the member's entry is quad_policy_pack's (its parameters and its image), the arch comes with the launch
+__global__ void k_pop_ac_head(const pop::PackEntry* __restrict__ tab, const int32_t* __restrict__ active, int32_t h2,
+                              int64_t image) {
+  const pop::PackEntry e = tab[active[blockIdx.y]];
+  ac_head_body(HeadArgs{e.p.val_w, e.p.val_b, e.p.log_std, e.packed, h2, image});
+}
+__global__ void k_pop_ac_pack(const pop::PackEntry* __restrict__ tab, const int32_t* __restrict__ active, int32_t h1,
+                              int32_t h2, int64_t image, int32_t net) {
+  const pop::PackEntry e = tab[active[blockIdx.y]];
+  actor::pack_body<arch::Layout, true, OBS>(net_params(e.p, e.packed, h2, net), h1, h2, e.packed + (net ? image : 0));
 }
 
 struct EpiArgs {  // QuadRolloutPost, flattened
@@ -456,8 +531,8 @@ struct ActArgs {
 };
 
 template <int MB>
-__global__ __launch_bounds__(actor::ACT_BLK) void k_ac_act(const float* __restrict__ packed, actor::Net net, ActArgs a,
-                                                           EpiArgs e) {
+__device__ __forceinline__ void ac_act_body(const float* __restrict__ packed, const actor::Net& net, const ActArgs& a,
+                                            const EpiArgs& e) {
   extern __shared__ float lds[];
   const arch::Layout lay{net.nb1, MB};
   float* Lc = lds + lay.lds_floats();
@@ -510,6 +585,25 @@ __global__ __launch_bounds__(actor::ACT_BLK) void k_ac_act(const float* __restri
 }
 
 template <int MB>
+__global__ __launch_bounds__(actor::ACT_BLK) void k_ac_act(const float* __restrict__ packed, actor::Net net, ActArgs a,
+                                                           EpiArgs e) {
+  ac_act_body<MB>(packed, net, a, e);
+}
+
+// The population form of the bootstrap value (population.h): block (b, k) is block b of member active[k]'s
+// quad_actor_critic_act(deterministic, rows = 1, value = out), FusedActorCritic.value
+template <int MB>
+__global__ __launch_bounds__(actor::ACT_BLK) void k_pop_ac_value(const pop::ValueEntry* __restrict__ tab,
+                                                                 const int32_t* __restrict__ active, actor::Net net,
+                                                                 int32_t n) {
+  const pop::ValueEntry v = tab[active[blockIdx.y]];
+  ActArgs a{};
+  a.obs = v.obs; a.act_env = v.act_env; a.value = v.value;
+  a.rows = 1; a.deterministic = 1; a.n = n;
+  ac_act_body<MB>(v.packed, net, a, EpiArgs{});
+}
+
+template <int MB>
 __global__ __launch_bounds__(actor::ACT_BLK) void k_ac_post(const float* __restrict__ packed, actor::Net net, EpiArgs e,
                                                             uint32_t* cursor, int32_t n) {
   extern __shared__ float lds[];
@@ -528,7 +622,8 @@ __global__ __launch_bounds__(actor::ACT_BLK) void k_ac_post(const float* __restr
 // device and for the widest H1 (dispatch.h), so packing an image is enough for the launches captured into a graph later
 int opt_in() {
   constexpr int BYTES = 2 * arch::Layout{actor::MAX_H1 / 32, 8}.lds_bytes();
-  return lds_opt_in<&k_ac_act<2>, &k_ac_act<4>, &k_ac_act<8>>(BYTES) == hipSuccess
+  return lds_opt_in<&k_ac_act<2>, &k_ac_act<4>, &k_ac_act<8>, &k_pop_ac_value<2>, &k_pop_ac_value<4>,
+                    &k_pop_ac_value<8>>(BYTES) == hipSuccess
              ? QUAD_OK
              : rfail(QUAD_EHIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
 }
@@ -556,7 +651,55 @@ hipError_t launch_by_mb(const KConsts<float>* kc, const KParams& kp, bool ctbr, 
   });
 }
 
+template <int AKIND>
+hipError_t launch_pop_by_mb(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active, int count, int n,
+                            bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps, hipStream_t s) {
+  return with_mb(net.mb, [&](auto mb) {
+    return launch_pop_actor_rollout_inst<AKIND, decltype(mb)::value>(kc, tab, active, count, n, ctbr, net, t0, steps, s);
+  });
+}
+
 }  // namespace
+
+// ---- the population launches of this file's kernels (population.h); `arch` is one quad_pop_create_arch checked
+int pop::launch_pop_ac_pack(const QuadActorArch& arch, const PackEntry* tab, const int32_t* active, int count,
+                            hipStream_t s) {
+  if (int rc = opt_in()) return rc;
+  const arch::Layout lay{arch.h1 / 32, arch.h2 / 32};
+  const int64_t A = lay.floats();
+  hipLaunchKernelGGL(k_pop_ac_head, dim3((ACT * arch.h2 + 2 * ACT + 255) / 256, count), dim3(256), 0, s, tab, active,
+                     arch.h2, A);
+  if (hipGetLastError() != hipSuccess) return rfail(QUAD_EHIP, "k_pop_ac_head launch failed");
+  for (int net = 1; net >= 0; net--) {  // the value half from the padded head, then the policy half over it
+    hipLaunchKernelGGL(k_pop_ac_pack, dim3(actor::pack_blocks(lay), count), dim3(256), 0, s, tab, active, arch.h1,
+                       arch.h2, A, net);
+    if (hipGetLastError() != hipSuccess) return rfail(QUAD_EHIP, "k_pop_ac_pack launch failed");
+  }
+  return QUAD_OK;
+}
+
+int pop::launch_pop_ac_value(const QuadActorArch& arch, const ValueEntry* tab, const int32_t* active, int count, int n,
+                             hipStream_t s) {
+  if (int rc = opt_in()) return rc;
+  const actor::Net net{arch.h1 / 32, arch.activation};
+  const hipError_t err = with_mb(arch.h2 / 32, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    const int bytes = 2 * arch::Layout{net.nb1, MB}.lds_bytes();
+    hipLaunchKernelGGL((k_pop_ac_value<MB>), dim3(actor::act_grid(n).x, count), dim3(actor::ACT_BLK), bytes, s, tab,
+                       active, net, n);
+    return hipGetLastError();
+  });
+  return err == hipSuccess ? QUAD_OK : rfail(QUAD_EHIP, "k_pop_ac_value launch failed");
+}
+
+hipError_t pop::launch_pop_ac_rollout(const QuadActorArch& arch, const KConsts<float>* kc, const RollEntry* tab,
+                                      const int32_t* active, int count, int n, int env_kind, bool ctbr, uint32_t t0,
+                                      int32_t steps, hipStream_t s) {
+  const ActorNet net{arch.h1 / 32, arch.h2 / 32, arch.activation};
+  return env_kind == QUAD_ENV_TRAJ ? launch_pop_by_mb<1>(kc, tab, active, count, n, ctbr, net, t0, steps, s)
+                                   : launch_pop_by_mb<0>(kc, tab, active, count, n, ctbr, net, t0, steps, s);
+}
+
 }  // namespace quadenv
 
 using namespace quadenv;
@@ -586,11 +729,9 @@ int quad_actor_critic_pack(const QuadActorArch* a, const QuadPolicyParams* p, fl
   hipLaunchKernelGGL(k_ac_head, dim3((ACT * h2 + 2 * ACT + 255) / 256), dim3(256), 0, s,
                      HeadArgs{p->val_w, p->val_b, p->log_std, packed, h2, A});
   if (hipGetLastError() != hipSuccess) return rfail(QUAD_EHIP, "k_ac_head launch failed");
-  const QuadActorParams critic{p->vf_w0, p->vf_b0, p->vf_w1, p->vf_b1, packed, packed + ACT * h2};
-  if (actor::launch_pack<arch::Layout, true, OBS>(lay, critic, packed + A, s) != hipSuccess)
+  if (actor::launch_pack<arch::Layout, true, OBS>(lay, net_params(*p, packed, h2, 1), packed + A, s) != hipSuccess)
     return rfail(QUAD_EHIP, "k_actor_pack (value net) launch failed");
-  const QuadActorParams pi{p->pi_w0, p->pi_b0, p->pi_w1, p->pi_b1, p->act_w, p->act_b};
-  if (actor::launch_pack<arch::Layout, true, OBS>(lay, pi, packed, s) != hipSuccess)
+  if (actor::launch_pack<arch::Layout, true, OBS>(lay, net_params(*p, packed, h2, 0), packed, s) != hipSuccess)
     return rfail(QUAD_EHIP, "k_actor_pack (policy net) launch failed");
   return QUAD_OK;
 }

@@ -32,6 +32,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "../../include/quadenv.h"
 #include "dispatch.h"
@@ -772,58 +773,74 @@ int64_t adam_ws_offset(int32_t batch) {
 }
 }  // namespace
 
-int64_t learner_workspace_bytes(const QuadAdam* adam, int32_t batch) {
+int64_t adam_partials_bytes(const QuadAdam* adam) {
   AdamArgs g{};
-  if (batch < 1 || adam_layout(adam, g) != QUAD_OK) return 0;
-  return adam_ws_offset(batch) + ((int64_t(g.nblocks) * int64_t(sizeof(float)) + 15) & ~int64_t(15));
+  if (adam_layout(adam, g) != QUAD_OK) return 0;
+  return (int64_t(g.nblocks) * int64_t(sizeof(float)) + 15) & ~int64_t(15);
 }
 
-int fill_learner(const QuadPopMember& m, int i, int32_t batch, int32_t normalize, GArgs* gt, RArgs* rt, AdamArgs* at) {
+int64_t learner_workspace_bytes(const QuadAdam* adam, int32_t batch) {
+  const int64_t partials = adam_partials_bytes(adam);
+  return batch < 1 || !partials ? 0 : adam_ws_offset(batch) + partials;
+}
+
+// What a member's learner entries share between the 128-128 ReLU form and the general family's (fill_learner below,
+// population.hip's quad_pop_create_arch): the pointer and hyperparameter checks, the GArgs fields the permutation, the
+// advantage sums and row_terms read, and the Adam entry with its partials at workspace + adam_offset
+int fill_member(const char* who, const QuadPopMember& m, int i, int32_t batch, int32_t normalize, int64_t adam_offset,
+                GArgs* gt, AdamArgs* at) {
+  const auto bad = [&](const char* msg) { return lfail(QUAD_EINVAL, (std::string(who) + msg).c_str()); };
   const QuadPolicyParams& p = m.params;
   const QuadPolicyGrads& gr = m.grads;
   if (!p.pi_w0 || !p.pi_b0 || !p.pi_w1 || !p.pi_b1 || !p.act_w || !p.act_b || !p.vf_w0 || !p.vf_b0 || !p.vf_w1 ||
       !p.vf_b1 || !p.val_w || !p.val_b || !p.log_std)
-    return lfail(QUAD_EINVAL, "quad_pop_create: a policy parameter pointer is NULL");
+    return bad(": a policy parameter pointer is NULL");
   if (!gr.pi_w0 || !gr.pi_b0 || !gr.pi_w1 || !gr.pi_b1 || !gr.act_w || !gr.act_b || !gr.vf_w0 || !gr.vf_b0 ||
       !gr.vf_w1 || !gr.vf_b1 || !gr.val_w || !gr.val_b || !gr.log_std)
-    return lfail(QUAD_EINVAL, "quad_pop_create: a gradient pointer is NULL");
+    return bad(": a gradient pointer is NULL");
   const QuadRollout& r = m.rollout;
   if (!r.obs_copy || !r.actions || !r.log_prob || !m.advantages || !m.returns || !m.perm || !m.mb_stats ||
       !m.workspace || (normalize && !m.adv_sums))
-    return lfail(QUAD_EINVAL, "quad_pop_create: a learner buffer is NULL");
+    return bad(": a learner buffer is NULL");
   if ((reinterpret_cast<uintptr_t>(r.obs_copy) | reinterpret_cast<uintptr_t>(r.actions) |
        reinterpret_cast<uintptr_t>(m.workspace)) & 15u)
-    return lfail(QUAD_EINVAL, "quad_pop_create: obs_copy, actions and workspace must be 16-byte aligned");
-  if (!(m.clip_range > 0.f)) return lfail(QUAD_EINVAL, "quad_pop_create: clip_range must be > 0");
+    return bad(": obs_copy, actions and workspace must be 16-byte aligned");
+  if (!(m.clip_range > 0.f)) return bad(": clip_range must be > 0");
   AdamArgs a{};
   if (int rc = adam_layout(&m.adam, a)) return rc;
   const QuadAdam& ad = m.adam;
   if (!(ad.eps > 0.0) || !(ad.lr >= 0.0) || !(ad.beta1 >= 0.0 && ad.beta1 < 1.0) || !(ad.beta2 >= 0.0 && ad.beta2 < 1.0))
-    return lfail(QUAD_EINVAL, "quad_pop_create: need lr >= 0, eps > 0, 0 <= betas < 1");
-  if (m.workspace_bytes < learner_workspace_bytes(&m.adam, batch))
-    return lfail(QUAD_EINVAL, "quad_pop_create: workspace too small");
-  const Layout l = layout_both(batch);
-  char* ws = static_cast<char*>(m.workspace);
-  const bool norm = normalize && batch > 1;
-  GArgs g{};
+    return bad(": need lr >= 0, eps > 0, 0 <= betas < 1");
+  if (m.workspace_bytes < adam_offset + adam_partials_bytes(&m.adam))
+    return bad(": workspace too small");
+  GArgs g{};  // the nets, the minibatch buffers, the epoch's bases and the loss scalars; the caller adds its form's own
   g.actor = NetW{p.pi_w0, p.pi_b0, p.pi_w1, p.pi_b1, p.act_w, p.act_b};
   g.critic = NetW{p.vf_w0, p.vf_b0, p.vf_w1, p.vf_b1, p.val_w, p.val_b};
   g.log_std = p.log_std;
   g.obs = r.obs_copy; g.act = r.actions; g.logp_old = r.log_prob; g.adv = m.advantages; g.ret = m.returns;
   g.idx = m.perm;
-  g.adv_part = norm ? m.adv_sums : nullptr;
-  g.part = reinterpret_cast<float*>(ws);
-  g.batch = batch; g.nb = l.nb; g.per_block = l.per_block; g.nbc = l.nbc; g.per_block_c = l.per_block_c;
+  g.adv_part = (normalize && batch > 1) ? m.adv_sums : nullptr;
+  g.batch = batch;
   g.clip = m.clip_range; g.inv_batch = 1.0f / float(batch); g.vf_coef = m.vf_coef;
+  gt[i] = g;
+  a.part = reinterpret_cast<float*>(static_cast<char*>(m.workspace) + adam_offset);
+  at[i] = a;
+  return QUAD_OK;
+}
+
+int fill_learner(const QuadPopMember& m, int i, int32_t batch, int32_t normalize, GArgs* gt, RArgs* rt, AdamArgs* at) {
+  if (int rc = fill_member("quad_pop_create", m, i, batch, normalize, adam_ws_offset(batch), gt, at)) return rc;
+  const Layout l = layout_both(batch);
+  char* ws = static_cast<char*>(m.workspace);
+  GArgs& g = gt[i];
+  g.part = reinterpret_cast<float*>(ws);
+  g.nb = l.nb; g.per_block = l.per_block; g.nbc = l.nbc; g.per_block_c = l.per_block_c;
   g.dump = nullptr;
   g.wimg = ws + l.part_bytes;
-  gt[i] = g;
   RArgs ra{};
-  ra.gr = gr; ra.part = g.part; ra.log_std = p.log_std; ra.stats = m.mb_stats; ra.nb = l.nb; ra.nbc = l.nbc;
+  ra.gr = m.grads; ra.part = g.part; ra.log_std = m.params.log_std; ra.stats = m.mb_stats; ra.nb = l.nb; ra.nbc = l.nbc;
   ra.inv_batch = 1.0f / float(batch); ra.ent_coef = m.ent_coef;
   rt[i] = ra;
-  a.part = reinterpret_cast<float*>(ws + adam_ws_offset(batch));
-  at[i] = a;
   return QUAD_OK;
 }
 

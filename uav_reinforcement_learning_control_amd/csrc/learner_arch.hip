@@ -327,8 +327,30 @@ __global__ __launch_bounds__(LB) void k_arch_fwd(Args a) {
     fwd_body<1, ACTF>(a, lds_f, blockIdx.x);
 }
 
+// A member's table entry (population.h) holds the epoch's bases; the launch of minibatch `slot` moves the index
+// slice, the advantage sums and the statistics row to it, as k_pop_ppo_grad_x3_sep and k_pop_ppo_reduce do
+__device__ __forceinline__ Args pop_args(const Args* __restrict__ tab, int32_t m, int32_t slot) {
+  Args a = tab[m];
+  a.g.idx += size_t(slot) * size_t(a.g.batch);
+  if (a.g.adv_part) a.g.adv_part += size_t(slot) * QUAD_ADV_SUM_DOUBLES;
+  if (a.stats) a.stats += 4 * size_t(slot);
+  return a;
+}
+
+// the population form (population.h): block (b, net, k) is block (b, net) of member active[k]'s launch
+template <int ACTF>
+__global__ __launch_bounds__(LB) void k_pop_arch_fwd(const Args* __restrict__ tab, const int32_t* __restrict__ active,
+                                                     int32_t slot) {
+  extern __shared__ __attribute__((aligned(16))) float lds_f[];
+  const Args a = pop_args(tab, active[blockIdx.z], slot);
+  if (blockIdx.y == 0)
+    fwd_body<ACT, ACTF>(a, lds_f, blockIdx.x);
+  else
+    fwd_body<1, ACTF>(a, lds_f, blockIdx.x);
+}
+
 // ---- the weight-gradient launch: wave (net, split, tile)
-__global__ __launch_bounds__(LB) void k_arch_wgrad(Args a) {
+__device__ __forceinline__ void wgrad_body(const Args& a) {
   const int wid = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int per_net = a.splits * a.tiles;
   if (wid >= 2 * per_net) return;
@@ -367,9 +389,17 @@ __global__ __launch_bounds__(LB) void k_arch_wgrad(Args a) {
   }
 }
 
+__global__ __launch_bounds__(LB) void k_arch_wgrad(Args a) { wgrad_body(a); }
+
+// the population form: block (b, k) is block b of member active[k]'s launch
+__global__ __launch_bounds__(LB) void k_pop_arch_wgrad(const Args* __restrict__ tab, const int32_t* __restrict__ active,
+                                                       int32_t slot) {
+  wgrad_body(pop_args(tab, active[blockIdx.y], slot));
+}
+
 // ---- the reduction: element e of a net summed over the splits or the forward blocks in order (float64) into the
 // gradient tensor that owns it; the four loss statistics
-__global__ __launch_bounds__(256) void k_arch_reduce(Args a) {
+__device__ __forceinline__ void reduce_body(const Args& a) {
   const int net = blockIdx.y, H1 = a.h1w, H2 = a.h2w;
   const int nout = net == 0 ? ACT : 1;
   const int eb = pb_stride(H1, H2), e = blockIdx.x * 256 + threadIdx.x;
@@ -419,6 +449,14 @@ __global__ __launch_bounds__(256) void k_arch_reduce(Args a) {
   else a.stats[3] = s * a.g.inv_batch;
 }
 
+__global__ __launch_bounds__(256) void k_arch_reduce(Args a) { reduce_body(a); }
+
+// the population form: block (b, net, k) is block (b, net) of member active[k]'s launch
+__global__ __launch_bounds__(256) void k_pop_arch_reduce(const Args* __restrict__ tab,
+                                                         const int32_t* __restrict__ active, int32_t slot) {
+  reduce_body(pop_args(tab, active[blockIdx.z], slot));
+}
+
 int fail(const char* msg) { return set_error(QUAD_EINVAL, msg); }
 
 bool bad(const void* p, uintptr_t al) { return !p || (reinterpret_cast<uintptr_t>(p) & (al - 1)) != 0; }
@@ -431,7 +469,52 @@ hipError_t launch_fwd(const Layout& l, hipStream_t s, const Args& a) {
   return launch_lds<&k_arch_fwd<ACTF>>(dim3(l.nbk, 2), dim3(LB), layout_of(512, 256, 1).lds_bytes, s, a);
 }
 
+// the workspace images and the block / split-K layout of an arch and a batch
+void set_layout(Args& a, const QuadActorArch& arch, const Layout& l, char* ws) {
+  a.x = reinterpret_cast<float*>(ws + l.o_x);
+  a.h1 = reinterpret_cast<float*>(ws + l.o_h1);
+  a.dh2 = reinterpret_cast<float*>(ws + l.o_dh2);
+  a.dh1 = reinterpret_cast<float*>(ws + l.o_dh1);
+  a.sp = reinterpret_cast<float*>(ws + l.o_sp);
+  a.pb = reinterpret_cast<float*>(ws + l.o_pb);
+  a.h1w = arch.h1; a.h2w = arch.h2; a.bp = l.bp; a.nbk = l.nbk; a.rpb = l.rpb;
+  a.tiles = l.tiles; a.splits = l.splits; a.rps = l.rps;
+}
+
+template <int ACTF>
+hipError_t launch_pop_fwd(const Layout& l, hipStream_t s, const Args* tab, const int32_t* active, int count, int slot) {
+  return launch_lds<&k_pop_arch_fwd<ACTF>>(dim3(l.nbk, 2, count), dim3(LB), layout_of(512, 256, 1).lds_bytes, s, tab,
+                                           active, slot);
+}
+
 }  // namespace
+
+// ---- the population launches of this file's kernels (population.h)
+Args pop_entry(const QuadActorArch& arch, const lrn::GArgs& g, const QuadPopMember& m, int32_t batch) {
+  Args a{};
+  a.g = g;
+  a.gr = m.grads;
+  a.stats = m.mb_stats;
+  a.ent_coef = m.ent_coef;
+  set_layout(a, arch, layout_of(arch.h1, arch.h2, batch), static_cast<char*>(m.workspace));
+  return a;
+}
+
+int launch_pop_grad(const QuadActorArch& arch, int32_t batch, const Args* tab, const int32_t* active, int count,
+                    int slot, hipStream_t s) {
+  const Layout l = layout_of(arch.h1, arch.h2, batch);
+  const hipError_t e = arch.activation == QUAD_ACTFN_TANH
+                           ? launch_pop_fwd<QUAD_ACTFN_TANH>(l, s, tab, active, count, slot)
+                           : launch_pop_fwd<QUAD_ACTFN_RELU>(l, s, tab, active, count, slot);
+  if (e != hipSuccess) return set_error(QUAD_EHIP, "k_pop_arch_fwd launch failed");
+  hipLaunchKernelGGL(k_pop_arch_wgrad, dim3((2 * l.splits * l.tiles + 3) / 4, count), dim3(LB), 0, s, tab, active, slot);
+  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_arch_wgrad launch failed");
+  const int elems = pb_stride(arch.h1, arch.h2) + sp_stride(arch.h2);
+  hipLaunchKernelGGL(k_pop_arch_reduce, dim3((elems + 255) / 256, 2, count), dim3(256), 0, s, tab, active, slot);
+  if (hipGetLastError() != hipSuccess) return set_error(QUAD_EHIP, "k_pop_arch_reduce launch failed");
+  return QUAD_OK;
+}
+
 }  // namespace lrna
 }  // namespace quadenv
 
@@ -488,15 +571,8 @@ int quad_ppo_arch_grad(const QuadActorArch* arch, const QuadPolicyParams* p, con
   g.clip = b->clip_range; g.inv_batch = 1.0f / float(b->batch); g.vf_coef = b->vf_coef;
   a.gr = *gr;
   a.stats = b->stats;
-  a.x = reinterpret_cast<float*>(ws + l.o_x);
-  a.h1 = reinterpret_cast<float*>(ws + l.o_h1);
-  a.dh2 = reinterpret_cast<float*>(ws + l.o_dh2);
-  a.dh1 = reinterpret_cast<float*>(ws + l.o_dh1);
-  a.sp = reinterpret_cast<float*>(ws + l.o_sp);
-  a.pb = reinterpret_cast<float*>(ws + l.o_pb);
-  a.h1w = arch->h1; a.h2w = arch->h2; a.bp = l.bp; a.nbk = l.nbk; a.rpb = l.rpb;
-  a.tiles = l.tiles; a.splits = l.splits; a.rps = l.rps;
   a.ent_coef = b->ent_coef;
+  set_layout(a, *arch, l, ws);
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (norm && na == 1) {

@@ -10,6 +10,7 @@
 #include "../../include/quadenv.h"
 #include "env_tiles.h"
 #include "learner.h"
+#include "learner_arch.h"
 #include "policy_episode.h"
 #include "rollout.h"
 
@@ -80,8 +81,34 @@ int launch_pop_adv_stats_epoch(const lrn::GArgs* tab, const int32_t* active, int
                                hipStream_t s);
 int launch_pop_reduce(const lrn::RArgs* rtab, const int32_t* active, int count, int slot, hipStream_t s);
 int launch_pop_clip_adam(const lrn::AdamArgs* atab, const int32_t* active, int count, int nblocks, hipStream_t s);
+// fill_learner's checks and the entries every family's learner shares (`who` prefixes the messages): the GArgs the
+// permutation and the advantage sums read, the Adam entry with its gradient-norm partials at workspace + adam_offset
+int fill_member(const char* who, const QuadPopMember& m, int i, int32_t batch, int32_t normalize, int64_t adam_offset,
+                lrn::GArgs* g, lrn::AdamArgs* a);
+int64_t adam_partials_bytes(const QuadAdam* adam);  // 0: the QuadAdam is invalid
+
+// ---- the general family (actor_rollout.hip, actor_arch.hip): the same entries -- a member's image is
+// quad_actor_critic_pack's, whose first quad_actor_packed_floats floats are the policy net's episode image -- and the
+// population's arch with every launch
+int launch_pop_ac_pack(const QuadActorArch& arch, const PackEntry* tab, const int32_t* active, int count, hipStream_t s);
+int launch_pop_ac_value(const QuadActorArch& arch, const ValueEntry* tab, const int32_t* active, int count, int n,
+                        hipStream_t s);
+hipError_t launch_pop_ac_rollout(const QuadActorArch& arch, const KConsts<float>* kc, const RollEntry* tab,
+                                 const int32_t* active, int count, int n, int env_kind, bool ctbr, uint32_t t0,
+                                 int32_t steps, hipStream_t s);
+hipError_t launch_pop_actor_episode(const QuadActorArch& arch, const KConsts<float>* kc, const PopEpisodeEntry* tab,
+                                    const int32_t* active, int count, int n, int env_kind, bool ctbr, hipStream_t s);
 
 }  // namespace pop
+
+namespace lrna {
+// The general learner's minibatch gradient (learner_arch.hip). A member's entry is quad_ppo_arch_grad's Args with the
+// epoch's bases, as the GArgs entry above: g (fill_member's) with idx = the permutation and adv_part = the sums of
+// every minibatch, stats = the [n_minibatches][4] base; the launch of minibatch `slot` advances the three
+Args pop_entry(const QuadActorArch& arch, const lrn::GArgs& g, const QuadPopMember& m, int32_t batch);
+int launch_pop_grad(const QuadActorArch& arch, int32_t batch, const Args* tab, const int32_t* active, int count,
+                    int slot, hipStream_t s);
+}  // namespace lrna
 
 namespace lrn {
 // k_x3_prep's W2 split + k_ppo_grad_x3_sep for every active member (learner_x3.hip); nb = layout_both(batch).nb

@@ -4,8 +4,11 @@
 // quad_pop_subset uploads a list of member indices once. A launch call then passes (table, subset list,
 // count) to the family's population kernel (rollout.hip, policy.hip, quadenv.hip, learner.hip,
 // learner_x3.hip): no allocation, no copy, no synchronization, so it is stream-ordered and graph-capturable.
+// quad_pop_create_arch builds the same tables for members of one arch of the general family; the launch
+// calls then go to that family's population kernels (actor_rollout.hip, actor_arch.hip, learner_arch.hip).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -31,6 +34,9 @@ struct QuadPop {
   PackEntry* pack = nullptr;
   ValueEntry* value = nullptr;
   LearnerTables lt;
+  bool general = false;        // a population of the general family (quad_pop_create_arch): arch, ga; lt.r unused
+  QuadActorArch arch{};
+  lrna::Args* ga = nullptr;    // the general learner's gradient table
   std::vector<const float*> packed;  // the members' packed images (quad_pop_attach_eval)
   PopEpisodeEntry* eval = nullptr;   // the evaluation table, once attached
   const KConsts<float>* eval_kc = nullptr;
@@ -77,6 +83,7 @@ void release(QuadPop* p) {
   (void)hipFree(p->lt.g);
   (void)hipFree(p->lt.r);
   (void)hipFree(p->lt.a);
+  (void)hipFree(p->ga);
   (void)hipFree(p->eval);
   for (auto& s : p->subsets) (void)hipFree(s.dev);
   delete p;
@@ -115,24 +122,31 @@ const QuadPop::Subset* subset_of(QuadPop* p, int32_t id, const char* what) {
   return &p->subsets[size_t(id)];
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t quad_pop_workspace_bytes(const QuadAdam* adam, int32_t batch) {
-  if (batch < 1 || batch > POP_MAX_BATCH) return 0;
-  return learner_workspace_bytes(adam, batch);
+// the 13 Adam tensors of an arch's module hold these element counts (in any order)
+bool adam_fits(const QuadAdam& ad, const QuadActorArch& a) {
+  std::vector<int32_t> want = {a.h1 * 12, a.h1, a.h2 * a.h1, a.h2, 4 * a.h2, 4, a.h1 * 12, a.h1, a.h2 * a.h1, a.h2,
+                               a.h2, 1, 4};
+  if (ad.count != int32_t(want.size())) return false;
+  std::vector<int32_t> got(ad.numel, ad.numel + ad.count);
+  std::sort(want.begin(), want.end());
+  std::sort(got.begin(), got.end());
+  return want == got;
 }
 
-int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int32_t normalize_advantage,
-                    QuadPop** out) {
-  if (out) *out = nullptr;
-  if (!members || !out) return pfail("quad_pop_create: members / out is NULL");
-  if (P < 1) return pfail("quad_pop_create: P must be >= 1");
-  if (P > POP_MAX_MEMBERS) return pfail("quad_pop_create: P must be <= 65535 (the member is a grid y / z coordinate)");
+// the gradient-norm partials follow the general learner's workspace
+int64_t arch_adam_offset(const QuadActorArch& a, int32_t batch) { return lrna::up16(lrna::layout_of(a.h1, a.h2, batch).bytes); }
+
+// quad_pop_create (arch == NULL: the 128-128 ReLU kernels) and quad_pop_create_arch (the general family's)
+int create(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
+           int32_t normalize_advantage, QuadPop** out) {
+  const std::string fn = arch ? "quad_pop_create_arch" : "quad_pop_create";
+  if (!members || !out) return pfail(fn + ": members / out is NULL");
+  if (P < 1) return pfail(fn + ": P must be >= 1");
+  if (P > POP_MAX_MEMBERS) return pfail(fn + ": P must be <= 65535 (the member is a grid y / z coordinate)");
   if (batch < 1 || batch > POP_MAX_BATCH)
-    return pfail("quad_pop_create: need 1 <= batch <= 8192 (the separate-block gradient form's limit)");
-  if (quad_ppo_grad_form() != 1) return pfail("quad_pop_create: only the bf16x3 gradient has a population form");
+    return pfail(fn + ": need 1 <= batch <= 8192 (the separate-block gradient form's limit)");
+  if (!arch && quad_ppo_grad_form() != 1) return pfail(fn + ": only the bf16x3 gradient has a population form");
+  std::vector<lrna::Args> ga(arch ? static_cast<size_t>(P) : 0);
   std::vector<RollEntry> roll(static_cast<size_t>(P));
   std::vector<GaeEntry> gae(static_cast<size_t>(P));
   std::vector<PackEntry> pack(static_cast<size_t>(P));
@@ -144,7 +158,7 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   for (int32_t i = 0; i < P; i++) {
     const QuadPopMember& m = members[i];
     const QuadRollout& r = m.rollout;
-    const std::string who = "quad_pop_create: member " + std::to_string(i) + ": ";
+    const std::string who = fn + ": member " + std::to_string(i) + ": ";
     if (!m.env || !m.packed) return pfail(who + "env / packed is NULL");
     if (!r.obs_copy || !r.actions || !r.log_prob || !r.value || !r.episode_starts || !r.rewards || !r.last_obs ||
         !r.last_start || !r.ep_ret || !r.ep_len || !r.stats || !m.last_values || !m.scratch_actions)
@@ -174,7 +188,15 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
                               m.advantages, m.returns, r.gamma, m.gae_lambda};
     pack[size_t(i)] = PackEntry{m.params, m.packed};
     value[size_t(i)] = ValueEntry{m.packed, r.last_obs, m.scratch_actions, m.last_values};
-    if (int rc = fill_learner(m, i, batch, normalize_advantage, gt.data(), rt.data(), at.data())) return rc;
+    if (arch) {
+      if (int rc = fill_member(fn.c_str(), m, i, batch, normalize_advantage, arch_adam_offset(*arch, batch), gt.data(),
+                               at.data()))
+        return rc;
+      if (!adam_fits(m.adam, *arch)) return pfail(who + "the Adam tensor sizes are not the arch's");
+      ga[size_t(i)] = lrna::pop_entry(*arch, gt[size_t(i)], m, batch);
+    } else if (int rc = fill_learner(m, i, batch, normalize_advantage, gt.data(), rt.data(), at.data())) {
+      return rc;
+    }
     if (m.adam.count != members[0].adam.count ||
         std::memcmp(m.adam.numel, members[0].adam.numel, sizeof(int32_t) * size_t(m.adam.count)) != 0)
       return pfail(who + "Adam tensor sizes differ from member 0's");
@@ -188,6 +210,8 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   p->spec = v0->spec; p->kc = v0->kdev;
   p->nb = lrn::layout_both(batch).nb;
   p->adam_nblocks = at[0].nblocks;
+  p->general = arch != nullptr;
+  if (arch) p->arch = *arch;
   for (int32_t i = 0; i < P; i++) p->packed.push_back(members[i].packed);
   DeviceGuard g(p->device);
   hipError_t e = upload(&p->roll, roll.data(), roll.size() * sizeof(RollEntry));
@@ -195,11 +219,12 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   if (!e) e = upload(&p->pack, pack.data(), pack.size() * sizeof(PackEntry));
   if (!e) e = upload(&p->value, value.data(), value.size() * sizeof(ValueEntry));
   if (!e) e = upload(&p->lt.g, gt.data(), gt.size() * sizeof(lrn::GArgs));
-  if (!e) e = upload(&p->lt.r, rt.data(), rt.size() * sizeof(lrn::RArgs));
+  if (!e && !arch) e = upload(&p->lt.r, rt.data(), rt.size() * sizeof(lrn::RArgs));
+  if (!e && arch) e = upload(&p->ga, ga.data(), ga.size() * sizeof(lrna::Args));
   if (!e) e = upload(&p->lt.a, at.data(), at.size() * sizeof(lrn::AdamArgs));
   if (e) {
     release(p);
-    return hfail("quad_pop_create", e);
+    return hfail(fn.c_str(), e);
   }
   std::vector<int32_t> all(static_cast<size_t>(P));
   for (int32_t i = 0; i < P; i++) all[size_t(i)] = i;
@@ -209,6 +234,36 @@ int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int3
   }
   *out = p;
   return QUAD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t quad_pop_workspace_bytes(const QuadAdam* adam, int32_t batch) {
+  if (batch < 1 || batch > POP_MAX_BATCH) return 0;
+  return learner_workspace_bytes(adam, batch);
+}
+
+int64_t quad_pop_arch_workspace_bytes(const QuadActorArch* arch, const QuadAdam* adam, int32_t batch) {
+  if (!lrna::in_family(arch) || batch < 1 || batch > POP_MAX_BATCH) return 0;
+  const int64_t partials = adam_partials_bytes(adam);
+  return partials ? arch_adam_offset(*arch, batch) + partials : 0;
+}
+
+int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int32_t normalize_advantage,
+                    QuadPop** out) {
+  if (out) *out = nullptr;
+  return create(nullptr, members, P, batch, normalize_advantage, out);
+}
+
+int quad_pop_create_arch(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
+                         int32_t normalize_advantage, QuadPop** out) {
+  if (out) *out = nullptr;
+  if (!lrna::in_family(arch))
+    return pfail("quad_pop_create_arch: the family is h1 a multiple of 32 in [32, 512], h2 in {64, 128, 256}, "
+                 "QUAD_ACTFN_RELU or QUAD_ACTFN_TANH");
+  return create(arch, members, P, batch, normalize_advantage, out);
 }
 
 void quad_pop_destroy(QuadPop* pop) { release(pop); }
@@ -222,7 +277,9 @@ int quad_pop_pack(QuadPop* pop, int32_t subset, void* stream) {
   const QuadPop::Subset* s = subset_of(pop, subset, "quad_pop_pack");
   if (!s) return QUAD_EINVAL;
   DeviceGuard g(pop->device);
-  return launch_pop_pack(pop->pack, s->dev, s->count, static_cast<hipStream_t>(stream));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return pop->general ? launch_pop_ac_pack(pop->arch, pop->pack, s->dev, s->count, st)
+                      : launch_pop_pack(pop->pack, s->dev, s->count, st);
 }
 
 int quad_pop_rollout(QuadPop* pop, int32_t subset, int32_t t0, int32_t steps, void* stream) {
@@ -230,8 +287,12 @@ int quad_pop_rollout(QuadPop* pop, int32_t subset, int32_t t0, int32_t steps, vo
   if (!s) return QUAD_EINVAL;
   if (steps < 1 || t0 < 0) return pfail("quad_pop_rollout: steps >= 1, t0 >= 0");
   DeviceGuard g(pop->device);
-  if (hipError_t e = launch_pop_rollout(pop->kc, pop->roll, s->dev, s->count, pop->n, pop->env_kind, pop->ctbr,
-                                        pop->spec, uint32_t(t0), steps, static_cast<hipStream_t>(stream)))
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipError_t e = pop->general
+                         ? launch_pop_ac_rollout(pop->arch, pop->kc, pop->roll, s->dev, s->count, pop->n, pop->env_kind,
+                                                 pop->ctbr, uint32_t(t0), steps, st)
+                         : launch_pop_rollout(pop->kc, pop->roll, s->dev, s->count, pop->n, pop->env_kind, pop->ctbr,
+                                              pop->spec, uint32_t(t0), steps, st))
     return hfail("quad_pop_rollout", e);
   return QUAD_OK;
 }
@@ -240,7 +301,9 @@ int quad_pop_value(QuadPop* pop, int32_t subset, void* stream) {
   const QuadPop::Subset* s = subset_of(pop, subset, "quad_pop_value");
   if (!s) return QUAD_EINVAL;
   DeviceGuard g(pop->device);
-  return launch_pop_value(pop->value, s->dev, s->count, pop->n, static_cast<hipStream_t>(stream));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  return pop->general ? launch_pop_ac_value(pop->arch, pop->value, s->dev, s->count, pop->n, st)
+                      : launch_pop_value(pop->value, s->dev, s->count, pop->n, st);
 }
 
 int quad_pop_gae(QuadPop* pop, int32_t subset, void* stream) {
@@ -275,6 +338,7 @@ int quad_pop_ppo_grad(QuadPop* pop, int32_t subset, int32_t slot, void* stream) 
   if (slot < 0 || slot >= pop->nmb) return pfail("quad_pop_ppo_grad: slot out of range");
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  if (pop->general) return lrna::launch_pop_grad(pop->arch, pop->batch, pop->ga, s->dev, s->count, slot, st);
   if (int rc = lrn::launch_pop_grad_x3(pop->lt.g, s->dev, s->count, slot, pop->nb, st)) return rc;
   return launch_pop_reduce(pop->lt.r, s->dev, s->count, slot, st);
 }
@@ -339,8 +403,12 @@ int quad_pop_episode(QuadPop* pop, int32_t subset, void* stream) {
   for (int32_t m : s->members)
     if (!pop->eval_ok[size_t(m)]) return pfail("quad_pop_episode: a member of the subset has no evaluation handle attached");
   DeviceGuard g(pop->device);
-  if (hipError_t e = launch_pop_policy_episode(pop->eval_kc, pop->eval, s->dev, s->count, pop->eval_n, pop->eval_kind,
-                                               pop->eval_ctbr, pop->eval_spec, static_cast<hipStream_t>(stream)))
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipError_t e = pop->general
+                         ? launch_pop_actor_episode(pop->arch, pop->eval_kc, pop->eval, s->dev, s->count, pop->eval_n,
+                                                    pop->eval_kind, pop->eval_ctbr, st)
+                         : launch_pop_policy_episode(pop->eval_kc, pop->eval, s->dev, s->count, pop->eval_n,
+                                                     pop->eval_kind, pop->eval_ctbr, pop->eval_spec, st))
     return hfail("quad_pop_episode", e);
   return QUAD_OK;
 }

@@ -5,7 +5,7 @@
 The reference runs an Optuna study (optimize.py:235-300): one SB3 PPO run per trial on 8 CPU envs, ten
 evaluations of ten deterministic episodes, a median pruner. Here the trials are sampled up front by a seeded
 random search over the same space (optimize.py:33-74, the batch clamp of :135-144), grouped by the shapes a
-population must share -- (n_steps, clamped batch_size) -- and every group trains as ONE ppo.PopulationPPO
+population must share -- (n_steps, clamped batch_size) -- and every group trains as ONE population (ppo.population_for)
 (several when it exceeds --n-jobs): each step of the algorithm is one launch for all the group's trials
 (DESIGN section 18). n_epochs varies inside a group (a member whose epochs are done leaves the launch's subset);
 a pruned trial is deactivated and costs nothing further.
@@ -19,10 +19,11 @@ the warm-up, and once five trials have completed, a trial is pruned when its bes
 median of the values reported at that index by the trials completed earlier and by the other members of its
 population. A trial whose parameters turn non-finite scores NaN (optimize.py:165-175).
 
-Only the architecture the fused kernels run is searched: net_arch is fixed to "small" ([128, 128]) and
-activation_fn to "relu"; the reference's medium / large / tanh choices are not sampled (a single learner trains them
-fused, ppo.learner.FusedArchLearner / train --fused-arch-update; populations do not yet). The sampler is random
-search, not TPE; Optuna is not a dependency, so --storage is accepted and ignored.
+By default net_arch is fixed to "small" ([128, 128]) and activation_fn to "relu", the net of the specialised kernels.
+--search-arch samples the reference's whole space (optimize.py:44-45): net_arch in {small, medium, large} x
+activation_fn in {tanh, relu}. A population shares its arch, so the groups are then keyed on it too, and
+ppo.population_for trains (small, relu) groups on PopulationPPO and the other five on ArchPopulationPPO (DESIGN
+section 25). The sampler is random search, not TPE; Optuna is not a dependency, so --storage is accepted and ignored.
 """
 from __future__ import annotations
 
@@ -45,8 +46,10 @@ N_EVAL_EPISODES = 10
 N_STEPS_CHOICES = (256, 512, 800, 1024, 2048)
 BATCH_CHOICES = (64, 128, 256, 512)
 N_EPOCHS_CHOICES = (3, 5, 10, 20)
-NET_ARCH_NAME, ACTIVATION_NAME = "small", "relu"   # the only architecture the fused path runs
-NET_ARCH = {"small": [128, 128]}
+NET_ARCH_NAME, ACTIVATION_NAME = "small", "relu"   # what is trained without --search-arch
+NET_ARCH = {"small": [128, 128], "medium": [256, 256], "large": [512, 256]}   # the reference's optimize.py:60-64
+NET_ARCH_CHOICES, ACTIVATION_CHOICES = ("small", "medium", "large"), ("tanh", "relu")
+ACTIVATION_CLASS = {"relu": "ReLU", "tanh": "Tanh"}
 
 # the columns of the reference's study_results_<study>.csv (optuna's trials_dataframe)
 CSV_COLUMNS = ("number", "value", "datetime_start", "datetime_complete", "duration", "params_activation_fn",
@@ -60,9 +63,12 @@ def _log_uniform(rng: random.Random, lo: float, hi: float) -> float:
     return math.exp(rng.uniform(math.log(lo), math.log(hi)))
 
 
-def sample_ppo_params(rng: random.Random, n_steps_choices: Sequence[int] = N_STEPS_CHOICES) -> dict:
-    """One draw from the reference's search space (optimize.py:36-45), in its order of suggestions."""
-    return {
+def sample_ppo_params(rng: random.Random, n_steps_choices: Sequence[int] = N_STEPS_CHOICES,
+                      search_arch: bool = False) -> dict:
+    """One draw from the reference's search space (optimize.py:36-45), in its order of suggestions. search_arch: draw
+    net_arch and then activation_fn after ent_coef, as the reference does; without it they are fixed and the rng is
+    not advanced for them."""
+    p = {
         "learning_rate": _log_uniform(rng, 1e-5, 1e-3),
         "n_steps": rng.choice(list(n_steps_choices)),
         "batch_size": rng.choice(BATCH_CHOICES),
@@ -74,6 +80,10 @@ def sample_ppo_params(rng: random.Random, n_steps_choices: Sequence[int] = N_STE
         "net_arch": NET_ARCH_NAME,
         "activation_fn": ACTIVATION_NAME,
     }
+    if search_arch:
+        p["net_arch"] = rng.choice(NET_ARCH_CHOICES)
+        p["activation_fn"] = rng.choice(ACTIVATION_CHOICES)
+    return p
 
 
 def clamp_batch_size(n_steps: int, n_envs: int, batch_size: int) -> int:
@@ -105,27 +115,35 @@ class Trial:
         return 1.0 - self.params["gamma_inv"]
 
 
-def make_trials(n_trials: int, seed: int, n_envs: int, n_steps_choices: Sequence[int] = N_STEPS_CHOICES) -> List[Trial]:
+def make_trials(n_trials: int, seed: int, n_envs: int, n_steps_choices: Sequence[int] = N_STEPS_CHOICES,
+                search_arch: bool = False) -> List[Trial]:
     rng = random.Random(seed)
     out = []
     for k in range(n_trials):
-        p = sample_ppo_params(rng, n_steps_choices)
+        p = sample_ppo_params(rng, n_steps_choices, search_arch)
         out.append(Trial(k, p, seed=int(seed) * 100_003 + k, batch=clamp_batch_size(p["n_steps"], n_envs, p["batch_size"])))
     return out
 
 
 def group_trials(trials: Sequence[Trial], cap: int) -> List[List[Trial]]:
-    """Populations: trials with equal (n_steps, clamped batch) together, at most `cap` per population, in
-    trial order; the populations ordered by their first trial."""
+    """Populations: trials with equal (n_steps, clamped batch, net_arch, activation_fn) together, at most `cap` per
+    population, in trial order; the populations ordered by their first trial."""
     by_shape: Dict[tuple, List[Trial]] = {}
     for t in trials:
-        by_shape.setdefault((t.params["n_steps"], t.batch), []).append(t)
+        by_shape.setdefault((t.params["n_steps"], t.batch, t.params["net_arch"], t.params["activation_fn"]), []).append(t)
     groups = []
     for ts in by_shape.values():
         for i in range(0, len(ts), max(1, int(cap))):
             groups.append(ts[i:i + max(1, int(cap))])
     groups.sort(key=lambda g: g[0].number)
     return groups
+
+
+def population_sizes(groups: Sequence[Sequence[Trial]]) -> str:
+    """How many populations a study trains, the largest and the median size."""
+    sizes = sorted(len(g) for g in groups)
+    return (f"  Populations: {len(sizes)} (largest {sizes[-1]}, median {statistics.median(sizes):g} trials)"
+            if sizes else "  Populations: 0")
 
 
 class MedianPruner:
@@ -213,7 +231,8 @@ def format_best(t: Trial) -> str:
               f"        batch_size={p['batch_size']},", f"        n_epochs={p['n_epochs']},", f"        gamma={t.gamma},",
               f"        gae_lambda={p['gae_lambda']},", f"        clip_range={p['clip_range']},",
               f"        ent_coef={p['ent_coef']},", "        policy_kwargs={",
-              f'            "net_arch": {NET_ARCH[p["net_arch"]]},', '            "activation_fn": nn.ReLU,', "        },",
+              f'            "net_arch": {NET_ARCH[p["net_arch"]]},',
+              f'            "activation_fn": nn.{ACTIVATION_CLASS[p["activation_fn"]]},', "        },",
               "        verbose=1,", '        device="cpu",', "    )", ""]
     return "\n".join(lines)
 
@@ -223,7 +242,8 @@ def ppo_config(t: Trial):
     from .ppo import PPOConfig
     p = t.params
     return PPOConfig(learning_rate=p["learning_rate"], n_steps=p["n_steps"], batch_size=t.batch, n_epochs=p["n_epochs"],
-                     gamma=t.gamma, gae_lambda=p["gae_lambda"], clip_range=p["clip_range"], ent_coef=p["ent_coef"])
+                     gamma=t.gamma, gae_lambda=p["gae_lambda"], clip_range=p["clip_range"], ent_coef=p["ent_coef"],
+                     net_arch=tuple(NET_ARCH[p["net_arch"]]), activation=p["activation_fn"])
 
 
 def _non_finite_members(pop, members: Sequence[int]) -> List[int]:
@@ -246,8 +266,9 @@ def save_best(pop, m: int, t: Trial, out_dir: str, n_envs: int, n_timesteps: int
            "ppo": {"learning_rate": t.params["learning_rate"], "n_steps": t.params["n_steps"], "batch_size": t.batch,
                    "sampled_batch_size": t.params["batch_size"], "n_epochs": t.params["n_epochs"], "gamma": t.gamma,
                    "gae_lambda": t.params["gae_lambda"], "clip_range": t.params["clip_range"],
-                   "ent_coef": t.params["ent_coef"], "net_arch": NET_ARCH[t.params["net_arch"]], "activation_fn": "ReLU"},
-           "backend": "uav_reinforcement_learning_control_amd (MI355X kernels, PopulationPPO)"}
+                   "ent_coef": t.params["ent_coef"], "net_arch": NET_ARCH[t.params["net_arch"]],
+                   "activation_fn": ACTIVATION_CLASS[t.params["activation_fn"]]},
+           "backend": f"uav_reinforcement_learning_control_amd (MI355X kernels, {type(pop).__name__})"}
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(cfg, f, indent=2)
     return path
@@ -255,12 +276,12 @@ def save_best(pop, m: int, t: Trial, out_dir: str, n_envs: int, n_timesteps: int
 
 def run_population(group: Sequence[Trial], finished: List[Trial], pruner: MedianPruner, n_timesteps: int, n_envs: int,
                    device="cuda:0", save_dir: Optional[str] = None, best_so_far: float = -math.inf, log=print) -> float:
-    """Train one group as a PopulationPPO over the evaluation protocol; fills the trials' values / state / value and
+    """Train one group as a population of its arch (ppo.population_for) over the evaluation protocol; fills the trials' values / state / value and
     appends them to `finished` as they end. Returns the best completed value seen (for --save-best)."""
-    from .ppo.population import PopulationPPO
+    from .ppo.population import population_for
     points = [(k + 1) * (n_timesteps // N_EVALUATIONS) for k in range(N_EVALUATIONS)]
-    pop = PopulationPPO([(ppo_config(t), t.seed) for t in group], n_envs=n_envs, env="hover", wrapper=WRAPPER,
-                        device=device)
+    pop = population_for([(ppo_config(t), t.seed) for t in group], n_envs=n_envs, env="hover", wrapper=WRAPPER,
+                         device=device)
     now = _dt.datetime.now
     for t in group:
         t.start = now()
@@ -304,14 +325,17 @@ def run_population(group: Sequence[Trial], finished: List[Trial], pruner: Median
             finish(m, COMPLETE, value)
     finally:
         pop.close()
-    log(f"  population of {len(group)} (n_steps {group[0].params['n_steps']}, batch {group[0].batch}): "
+    arch = f", {group[0].params['net_arch']} {group[0].params['activation_fn']}" if type(pop).__name__ != "PopulationPPO" else ""
+    log(f"  population of {len(group)} (n_steps {group[0].params['n_steps']}, batch {group[0].batch}{arch}): "
         + ", ".join(f"#{t.number} {t.state[0]} {t.value:.1f}" for t in group))
     return best_so_far
 
 
 def run_study(a, n_steps_choices: Sequence[int] = N_STEPS_CHOICES, log=print) -> List[Trial]:
-    trials = make_trials(a.n_trials, a.seed, a.n_envs, n_steps_choices)
+    trials = make_trials(a.n_trials, a.seed, a.n_envs, n_steps_choices, getattr(a, "search_arch", False))
     groups = group_trials(trials, a.n_jobs)
+    if getattr(a, "search_arch", False):  # six arch combinations make the populations about six times thinner
+        log(population_sizes(groups))
     pruner = MedianPruner()
     finished: List[Trial] = []
     t0, best = time.perf_counter(), -math.inf
@@ -327,8 +351,7 @@ def run_study(a, n_steps_choices: Sequence[int] = N_STEPS_CHOICES, log=print) ->
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(
         description="Seeded random-search HPO for PPO hover control on PPO populations (the reference's optimize.py). "
-                    "net_arch is fixed to small ([128, 128]) and activation_fn to relu: the only architecture the "
-                    "fused kernels run.")
+                    "net_arch is fixed to small ([128, 128]) and activation_fn to relu unless --search-arch is given.")
     ap.add_argument("--n-trials", type=int, default=50, help="Number of trials")
     ap.add_argument("--n-jobs", type=int, default=64, help="Largest population: trials trained together in one launch")
     ap.add_argument("--timeout", type=int, default=None, help="No new population starts after this many seconds")
@@ -341,6 +364,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="Write the best trial's hover_policy_final.zip and config.json there")
     ap.add_argument("--out-dir", default=".", help="Where study_results_<study>.csv goes")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--search-arch", action="store_true",
+                    help="Also sample net_arch in {small, medium, large} and activation_fn in {tanh, relu}, the "
+                         "reference's whole space; a population then shares its arch too, so populations get thinner")
     return ap
 
 

@@ -1,5 +1,7 @@
 from .gae import gae
 from .policy import ActorCritic
 from .ppo import PPO, PPOConfig, allreduce_mean_, ppo_loss
+from .population import ArchPopulationPPO, PopulationPPO, population_for
 
-__all__ = ["gae", "ActorCritic", "PPO", "PPOConfig", "ppo_loss", "allreduce_mean_"]
+__all__ = ["gae", "ActorCritic", "PPO", "PPOConfig", "ppo_loss", "allreduce_mean_", "PopulationPPO",
+           "ArchPopulationPPO", "population_for"]

@@ -13,19 +13,23 @@ bit-identical to the stand-alone `PPO` with the same config and seed, after any 
 Shared by all members: the env kind / wrapper / constants, envs per member, n_steps, the minibatch size,
 net_arch (128, 128), normalize_advantage. Per member: the seed, n_epochs (a member whose epochs are done is
 simply not in the launch's subset) and every scalar hyperparameter.
+
+`ArchPopulationPPO` is the same class on the general family's kernels (tanh, other widths), and
+`population_for` picks between the two by the members' arch.
 """
 from __future__ import annotations
 
 import ctypes as C
 import time
+from dataclasses import replace
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from .. import _native as N
 from ..envs import QuadVecEnv
-from .fused import FusedPolicy, current_stream
-from .learner import FusedLearner
+from .fused import FusedActorCritic, FusedPolicy, arch_rollout_keeps_torch, current_stream
+from .learner import ARCH_UPDATE_KEEP_TORCH, LEARNER_FAMILY, FusedArchLearner, FusedLearner
 from .ppo import PPO, PPOConfig, RolloutStats
 
 
@@ -49,9 +53,7 @@ class PopulationPPO:
         c0 = members[0][0]
         total = c0.n_steps * int(n_envs)
         for cfg, _ in members:
-            if tuple(cfg.net_arch) != (128, 128) or cfg.activation != "relu":
-                raise ValueError(f"PopulationPPO runs the fused (128, 128) relu policy only, got net_arch "
-                                 f"{cfg.net_arch} {cfg.activation}")
+            self._check_config(cfg, c0)
             if not (cfg.fused_policy and cfg.fused_rollout and cfg.fused_update):
                 raise ValueError("PopulationPPO needs fused_policy, fused_rollout and fused_update")
             if cfg.n_steps != c0.n_steps:
@@ -79,9 +81,10 @@ class PopulationPPO:
         for cfg, seed in members:
             e = QuadVecEnv(self.n_envs, env=env, wrapper=wrapper, device=device, seed=int(seed), **kw)
             m = PPO(e, cfg, seed=int(seed))
-            # exactly the 128-128 ReLU kernels' classes: the quad_pop_* launches read that packed image and that
-            # workspace (a FusedActorCritic / FusedArchLearner of the general family has another layout)
-            if not m._one_launch or type(m._fp) is not FusedPolicy or type(m._learner) is not FusedLearner:
+            # exactly this population's kernel classes: its launches read that packed image and that workspace
+            # (the 128-128 ReLU net's and the general family's differ in both)
+            if (not m._one_launch or type(m._fp) is not self._policy_class
+                    or type(m._learner) is not self._learner_class):
                 raise ValueError("the env / policy is not one the fused rollout and update run")
             self.members.append(m)
             # PPO.__init__ leaves torch's default CPU generator at manual_seed(seed); the stand-alone run then
@@ -92,8 +95,7 @@ class PopulationPPO:
         self.active = list(range(P))
         dev = self.device
         m0 = self.members[0]
-        a0 = m0._adam._build()
-        ws = int(self._lib.quad_pop_workspace_bytes(C.byref(a0), batch))
+        ws = self._workspace_bytes(m0, batch)
         if ws <= 0:
             raise N.QuadError("quad_pop_workspace_bytes failed: " + self._lib.quad_last_error().decode(errors="replace"))
         ws = (ws + 255) // 256 * 256
@@ -104,12 +106,27 @@ class PopulationPPO:
         arr = (N.QuadPopMember * P)()
         for i, m in enumerate(self.members):
             self._fill(arr[i], m, i, ws)
-        h = C.c_void_p()
-        N.check(self._lib.quad_pop_create(arr, P, batch, int(self.normalize_advantage), C.byref(h)), "quad_pop_create")
-        self._h = h
+        self._h = self._create(arr, P, batch)
         self._subsets = {tuple(range(P)): 0}
         self._t_host = 0
         self._started = False
+
+    # ---- what a kernel family's population differs in (ArchPopulationPPO overrides these) ----------------
+    _policy_class, _learner_class = FusedPolicy, FusedLearner
+    _block_envs = 256  # envs per rollout block: block b adds its episode statistics into slot b
+
+    def _check_config(self, cfg: PPOConfig, c0: PPOConfig) -> None:
+        if tuple(cfg.net_arch) != (128, 128) or cfg.activation != "relu":
+            raise ValueError(f"PopulationPPO runs the fused (128, 128) relu policy only, got net_arch "
+                             f"{cfg.net_arch} {cfg.activation}")
+
+    def _workspace_bytes(self, m0: PPO, batch: int) -> int:
+        return int(self._lib.quad_pop_workspace_bytes(C.byref(m0._adam._build()), batch))
+
+    def _create(self, arr, P: int, batch: int) -> C.c_void_p:
+        h = C.c_void_p()
+        N.check(self._lib.quad_pop_create(arr, P, batch, int(self.normalize_advantage), C.byref(h)), "quad_pop_create")
+        return h
 
     # ------------------------------------------------------------------------------------
     def _fill(self, e: N.QuadPopMember, m: PPO, i: int, ws: int) -> None:
@@ -198,8 +215,9 @@ class PopulationPPO:
         N.check(L.quad_pop_value(h, sid, st), "quad_pop_value")
         N.check(L.quad_pop_gae(h, sid, st), "quad_pop_gae")
         # the episode statistics: block b of a member's rollout adds into slot b, so with one block per member
-        # (<= 256 envs) slot 0 is the sum; more blocks are summed as PPO sums them (the same order)
-        if self.n_envs <= 256:
+        # (<= 256 envs; 64 in the general family) slot 0 is the sum; more blocks are summed as PPO sums them (the same
+        # order)
+        if self.n_envs <= self._block_envs:
             sums = torch.stack([self.members[i]._slots[0] for i in act])
         else:
             sums = torch.stack([self.members[i]._slots.sum(0) for i in act])
@@ -306,3 +324,72 @@ class PopulationPPO:
             if callback is not None and callback(self, it, rs, ts) is False:
                 break
         return self
+
+
+def _arch_key(cfg: PPOConfig) -> tuple:
+    return tuple(int(x) for x in cfg.net_arch), str(cfg.activation)
+
+
+class ArchPopulationPPO(PopulationPPO):
+    """`PopulationPPO` for the general actor's family: P stand-alone `PPO` learners with
+    fused_rollout_arch and fused_update_arch -- policy and value nets 12 -> H1 -> H2 -> 4 / 1, H1 a multiple of 32 up
+    to 512, H2 in {64, 128, 256}, relu or tanh, other than the (128, 128) relu net `PopulationPPO` runs -- driven by
+    the population forms of quad_actor_critic_pack, quad_actor_rollout, quad_actor_critic_act, quad_ppo_arch_grad and
+    quad_actor_episode. Every member shares the arch as it shares the other shapes; member m is bit-identical to
+    `PPO(env, cfg, seed)` with both arch flags (tests/test_gpu_population_arch_ppo.py)."""
+
+    _policy_class, _learner_class = FusedActorCritic, FusedArchLearner
+    _block_envs = 64
+
+    def _check_config(self, cfg: PPOConfig, c0: PPOConfig) -> None:
+        if _arch_key(cfg) != _arch_key(c0):
+            raise ValueError(f"members must share net_arch and activation ({_arch_key(cfg)} != {_arch_key(c0)})")
+        if _arch_key(cfg) == ((128, 128), "relu"):
+            raise ValueError("the (128, 128) relu policy trains on PopulationPPO (population_for picks the class)")
+        if not (cfg.fused_rollout_arch and cfg.fused_update_arch):
+            raise ValueError("ArchPopulationPPO needs fused_rollout_arch and fused_update_arch")
+        hidden, act = _arch_key(cfg)
+        if (len(hidden) != 2 or hidden[0] % 32 or not 32 <= hidden[0] <= N.ACTOR_MAX_H1 or hidden[1] not in N.ACTOR_H2
+                or act not in N.ACTFNS):
+            raise ValueError(f"ArchPopulationPPO trains {LEARNER_FAMILY}, got net_arch {cfg.net_arch} {cfg.activation}")
+
+    def _workspace_bytes(self, m0: PPO, batch: int) -> int:
+        return int(self._lib.quad_pop_arch_workspace_bytes(C.byref(m0._fp.arch), C.byref(m0._adam._build()), batch))
+
+    def _create(self, arr, P: int, batch: int) -> C.c_void_p:
+        h = C.c_void_p()
+        N.check(self._lib.quad_pop_create_arch(C.byref(self.members[0]._fp.arch), arr, P, batch,
+                                               int(self.normalize_advantage), C.byref(h)), "quad_pop_create_arch")
+        return h
+
+
+# ((H1, H2), activation) whose 64-member iteration did not take less than half of 64 stand-alone iterations in
+# profiles/arch_population/bench.json (DESIGN 25, by 18's bar): population_for keeps them off the population path
+ARCH_POPULATION_KEEP_SERIAL = frozenset()
+
+
+def population_for(members: Sequence[Tuple[PPOConfig, int]], n_envs: int = 8, env: str = "hover",
+                   wrapper: Optional[str] = None, device=None, env_kwargs: Optional[dict] = None) -> PopulationPPO:
+    """The population class of `members`' arch, as fused_policy_for / fused_learner_for pick a member's kernels: a
+    PopulationPPO for (128, 128) relu configs, an ArchPopulationPPO (the arch flags switched on in the configs it
+    gets) for any other member of the family. ValueError outside the family, for mixed arches, and for a row the
+    drivers keep off the fused path (ARCH_ROLLOUT_KEEP_TORCH, ARCH_UPDATE_KEEP_TORCH, ARCH_POPULATION_KEEP_SERIAL)."""
+    members = list(members)
+    if len(members) < 1:
+        raise ValueError("population_for needs at least one (PPOConfig, seed)")
+    keys = {_arch_key(cfg) for cfg, _ in members}
+    if len(keys) != 1:
+        raise ValueError(f"members must share net_arch and activation, got {sorted(keys)}")
+    (hidden, act), = keys
+    kw = dict(n_envs=n_envs, env=env, wrapper=wrapper, device=device, env_kwargs=env_kwargs)
+    if (hidden, act) == ((128, 128), "relu"):
+        return PopulationPPO(members, **kw)
+    c0 = members[0][0]
+    total = c0.n_steps * int(n_envs)
+    batch = int(c0.batch_size) if c0.batch_size is not None else max(1, total // c0.n_minibatches)
+    if (arch_rollout_keeps_torch(hidden, act, n_envs) or (hidden, act, batch) in ARCH_UPDATE_KEEP_TORCH
+            or (hidden, act) in ARCH_POPULATION_KEEP_SERIAL):
+        raise ValueError(f"net_arch {hidden} {act} stays off the fused population path at {n_envs} envs, minibatch "
+                         f"{batch} (it did not beat the path it would replace)")
+    return ArchPopulationPPO([(replace(cfg, fused_rollout_arch=True, fused_update_arch=True), seed)
+                              for cfg, seed in members], **kw)
