@@ -717,6 +717,26 @@ int64_t quad_brax_ppo_workspace_bytes(int32_t mb, int32_t L);
 int quad_brax_ppo_grad(const QuadBraxPPOParams* p, const QuadBraxPPOBatch* b, const QuadBraxPPOGrads* gr,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The same gradient for the Brax actor's whole family. Added within ABI v8. Family: the policy net
+ * 21 -> policy_h1 -> policy_h2 -> 8 and the value net 21 -> value_h1 -> value_h2 -> 1, each h1 a multiple of 32 in
+ * [32, 512], each h2 in {64, 128, 256} (quad_brax_actor_*'s family), the two nets' sizes independent of each other;
+ * one activation for both: QUAD_ACTFN_RELU, QUAD_ACTFN_TANH or QUAD_ACTFN_SILU. The structs, the loss, the layouts,
+ * the gather through index, entropy_noise / noise_out (the same Philox draw: for equal arguments noise_out has
+ * quad_brax_ppo_grad's bits), the diagnostics and the guarantees are quad_brax_ppo_grad's, in five launches: the
+ * gradients are OVERWRITTEN, the results are bit-identical from call to call and do not depend on where a
+ * trajectory's rows lie in the buffers, and nothing synchronises with the host. The value loss reads each row's V
+ * from the values array the first launch wrote.
+ * QUAD_EINVAL, with nothing launched and nothing written: an arch outside the family; a NULL or misaligned
+ * parameter, gradient, unroll buffer or index; a misaligned optional buffer or workspace (16 bytes); mb < 1; L
+ * outside [1, 64]; U or N < 1; L mb > 2^22 loss rows; clipping_epsilon <= 0; workspace_bytes <
+ * quad_brax_ppo_arch_workspace_bytes(p, mb, L). */
+/* Device workspace (bytes, 16-byte aligned) quad_brax_ppo_arch_grad needs for p's four sizes and activation (its
+ * pointers are not read); 0 for p NULL or outside the family, mb < 1, L outside [1, 64] or L mb > 2^22. It holds the
+ * x | 1, h1, dh2 and dh1 images of every loss row: about 4 (32 + 2 h1 + h2) bytes per row and net. */
+int64_t quad_brax_ppo_arch_workspace_bytes(const QuadBraxPPOParams* p, int32_t mb, int32_t L);
+int quad_brax_ppo_arch_grad(const QuadBraxPPOParams* p, const QuadBraxPPOBatch* b, const QuadBraxPPOGrads* gr,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Finish the pending step (end of a rollout): the epilogue for row (t-1) % rows if the cursor
  * marks one pending, then clears the mark. A no-op otherwise. */
 int quad_rollout_post(const float* packed, const QuadRolloutPost* p, uint32_t* cursor, int32_t n,

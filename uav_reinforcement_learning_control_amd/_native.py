@@ -215,6 +215,9 @@ class QuadBraxPPOBatch(C.Structure):
 
 
 BRAX_PPO_HIDDEN, BRAX_PPO_MAX_L = (128, 128), 64  # quad_brax_ppo_grad's family
+# quad_brax_ppo_arch_grad's family: each net's (h1, h2) with h1 a multiple of 32 in [32, BRAX_PPO_ARCH_MAX_H1] and h2
+# in BRAX_PPO_ARCH_H2, any of BRAX_ACTFNS, unroll_length in [1, BRAX_PPO_MAX_L], at most BRAX_PPO_ARCH_MAX_ROWS loss rows
+BRAX_PPO_ARCH_MAX_H1, BRAX_PPO_ARCH_H2, BRAX_PPO_ARCH_MAX_ROWS = 512, (64, 128, 256), 1 << 22
 
 POLICY_STAT_SLOTS = 1024
 
@@ -260,6 +263,7 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_actor_waypoints",
            "quad_brax_actor_packed_floats", "quad_brax_actor_pack", "quad_brax_actor_act", "quad_brax_episode",
            "quad_brax_actor_sample", "quad_brax_unroll", "quad_brax_ppo_workspace_bytes", "quad_brax_ppo_grad",
+           "quad_brax_ppo_arch_workspace_bytes", "quad_brax_ppo_arch_grad",
            "quad_ppo_arch_workspace_bytes", "quad_ppo_arch_grad",
            "quad_actor_critic_packed_floats", "quad_actor_critic_pack", "quad_actor_critic_act",
            "quad_actor_critic_post", "quad_actor_rollout")
@@ -420,6 +424,12 @@ def _declare(L):
     L.quad_brax_ppo_grad.argtypes = [C.POINTER(QuadBraxPPOParams), C.POINTER(QuadBraxPPOBatch),
                                      C.POINTER(QuadBraxPPOGrads), vp, C.c_int64, vp]
     L.quad_brax_ppo_grad.restype = C.c_int
+    if not hasattr(L, "quad_brax_ppo_arch_grad"):  # nor with the whole family's gradient
+        raise QuadError(f"{LIB_PATH} was built before the Brax family's gradient (quad_brax_ppo_arch_grad); rebuild it")
+    L.quad_brax_ppo_arch_workspace_bytes.argtypes = [C.POINTER(QuadBraxPPOParams), i32, i32]
+    L.quad_brax_ppo_arch_workspace_bytes.restype = C.c_int64
+    L.quad_brax_ppo_arch_grad.argtypes = L.quad_brax_ppo_grad.argtypes
+    L.quad_brax_ppo_arch_grad.restype = C.c_int
     if not hasattr(L, "quad_ppo_arch_grad"):  # nor with the general learner's
         raise QuadError(f"{LIB_PATH} was built before the general learner's entry points (quad_ppo_arch_grad); rebuild it")
     L.quad_ppo_arch_workspace_bytes.argtypes = [arch, i32]

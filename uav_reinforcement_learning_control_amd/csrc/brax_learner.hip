@@ -30,6 +30,7 @@
 #include "../../include/quadenv.h"
 #include "brax_actor.h"
 #include "brax_learner.h"
+#include "brax_learner_common.h"
 #include "dispatch.h"
 #include "learner_x3_common.h"
 
@@ -94,40 +95,13 @@ __device__ __forceinline__ f32x16 zero16() {
   return z;
 }
 
-// trajectory m = u N + n, step t -> row (u L + t) N + n of the time-major buffers
-__device__ __forceinline__ size_t step_row(const Args& a, int64_t m, int t) {
-  const int64_t u = m / a.N, n = m - u * a.N;
-  return size_t((u * a.L + t) * a.N + n);
-}
-
-__device__ __forceinline__ void stage_norm(const Args& a, float* Lf) {
-  const int tid = threadIdx.x;
-  if (tid < 32) {
-    Lf[O_MS + tid] = tid < OBSB ? a.mean[tid] : 0.f;
-    Lf[O_MS + 32 + tid] = tid < OBSB ? a.std[tid] : 1.f;
-  }
-}
-
 // rows q0 .. q0 + 63 of the time-major minibatch (row q = t mb + j: step t of trajectory index[j]; t = L is the
 // bootstrap row, from next_obs) normalised as RunningStats.normalize does, into the observation image; rows past
 // `nrows` are all zero, their 1.0 column included
 __device__ __forceinline__ void stage_x(const Args& a, float* Lf, int q0, int nrows) {
   const int tid = threadIdx.x, row = tid >> 2, f0 = (tid & 3) * 8;
-  const int q = q0 + row;
   float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) v[j] = 0.f;
-  if (q < nrows) {
-    const int t = q / a.mb, jj = q - t * a.mb;
-    const int64_t m = a.idx[jj];
-    const float* src = t < a.L ? a.obs + step_row(a, m, t) * OBSB : a.next_obs + size_t(m) * OBSB;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-      const int f = f0 + j;
-      if (f < OBSB) v[j] = __fdiv_rn(__fsub_rn(src[f], Lf[O_MS + f]), Lf[O_MS + 32 + f]);
-      else if (f == OBSB) v[j] = 1.f;
-    }
-  }
+  gather_row8(a, Lf + O_MS, q0 + row, nrows, f0, v);
 #pragma unroll
   for (int j = 0; j < 8; j++) Lf[O_X + row * XS + f0 + j] = v[j];
 }
@@ -223,7 +197,7 @@ __global__ __launch_bounds__(LB, 1) void k_brax_value(Args a) {
   extern __shared__ __attribute__((aligned(16))) float lds_v[];
   float* const Lf = lds_v;
   const Lane ln;
-  stage_norm(a, Lf);
+  stage_norm(a, Lf + O_MS);
   stage_head_weights<1>(a.vf, Lf);
   __syncthreads();
   const int q0 = blockIdx.x * RND;
@@ -279,41 +253,6 @@ __global__ __launch_bounds__(256) void k_brax_gae(Args a) {
   if (tid == 0) { a.adv_part[2 * blockIdx.x] = red[0][0]; a.adv_part[2 * blockIdx.x + 1] = red[1][0]; }
 }
 
-// Box-Muller on Philox(seed; trajectory, step, ENTROPY_STREAM): brax_actor.h gauss4_brax's draw on the entropy
-// sample's own stream
-__device__ __forceinline__ void gauss4_entropy(uint64_t seed, uint64_t traj, uint32_t step, float z[4]) {
-  uint32_t c[4] = {uint32_t(traj), uint32_t(traj >> 32), step, ENTROPY_STREAM};
-  philox4x32_10(c, uint32_t(seed), uint32_t(seed >> 32));
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const float u1 = (float(c[2 * k] >> 8) + 1.0f) * 0x1p-24f;  // (0, 1]
-    const float u2 = float(c[2 * k + 1] >> 8) * 0x1p-24f;
-    const float rr = __builtin_amdgcn_sqrtf(-1.38629436111989061f * __builtin_amdgcn_logf(u1));  // -2 ln u1
-    z[2 * k] = rr * __builtin_amdgcn_cosf(u2);
-    z[2 * k + 1] = rr * __builtin_amdgcn_sinf(u2);
-  }
-}
-
-// the advantage normalisation of the minibatch: a fixed-order float64 tree over the GAE launch's block sums, then
-// mean and std(unbiased=False) + 1e-8 as brax_ppo_loss forms them; {0, 1} without normalisation
-struct AdvNorm { float mu, den; };
-__device__ __forceinline__ AdvNorm adv_norm(const Args& a, float* Lf) {
-  if (!a.norm_adv) return AdvNorm{0.f, 1.f};
-  double* const red0 = reinterpret_cast<double*>(Lf + O_RED);
-  double* const red1 = red0 + LB;
-  const int tid = threadIdx.x;
-  red0[tid] = tid < a.gae_blocks ? a.adv_part[2 * tid] : 0.0;
-  red1[tid] = tid < a.gae_blocks ? a.adv_part[2 * tid + 1] : 0.0;
-  __syncthreads();
-  for (int o = LB / 2; o > 0; o >>= 1) {
-    if (tid < o) { red0[tid] += red0[tid + o]; red1[tid] += red1[tid + o]; }
-    __syncthreads();
-  }
-  const double n = double(a.rows_loss), s = red0[0], s2 = red1[0];
-  const double var = fmax((s2 - s * s / n) / n, 0.0);
-  return AdvNorm{float(s / n), float(sqrt(var)) + 1e-8f};
-}
-
 // a pointer the compiler cannot see through: loads from it stay inside the round loop (learner_x3.hip: hoisted out,
 // the loop-invariant weight operands take more registers than there are)
 __device__ __forceinline__ const float* opaque(const float* p) {
@@ -329,8 +268,8 @@ __device__ __forceinline__ void grad_body(const Args& a, float* Lf, int blk) {
   const Lane ln;
   const int tid = ln.tid, w = ln.w, r = ln.r, h = ln.h;
   AdvNorm an{0.f, 1.f};
-  if constexpr (NOUT == NLOG) an = adv_norm(a, Lf);
-  stage_norm(a, Lf);
+  if constexpr (NOUT == NLOG) an = adv_norm(a, reinterpret_cast<double*>(Lf + O_RED), reinterpret_cast<double*>(Lf + O_RED) + LB);
+  stage_norm(a, Lf + O_MS);
   stage_head_weights<NOUT>(W0, Lf);
   __syncthreads();
 
@@ -364,54 +303,7 @@ __device__ __forceinline__ void grad_body(const Args& a, float* Lf, int blk) {
       for (int o = 0; o < NOUT; o++) d[o] = 0.f;
       if (q < a.rows_loss) {
         if constexpr (NOUT == NLOG) {
-          const int t = q / a.mb, jj = q - t * a.mb;
-          const int64_t m = a.idx[jj];
-          const size_t row = step_row(a, m, t);
-          const float4 r4 = reinterpret_cast<const float4*>(a.raw)[row];
-          const float raw[4] = {r4.x, r4.y, r4.z, r4.w};
-          float z[4];
-          if (a.noise) {
-            const float4 z4 = reinterpret_cast<const float4*>(a.noise)[q];
-            z[0] = z4.x; z[1] = z4.y; z[2] = z4.z; z[3] = z4.w;
-          } else {
-            gauss4_entropy(a.seed, uint64_t(m), a.noise_step * uint32_t(a.L) + uint32_t(t), z);
-          }
-          if (a.noise_out) reinterpret_cast<float4*>(a.noise_out)[q] = make_float4(z[0], z[1], z[2], z[3]);
-          float lg[NLOG], sc[4];
-#pragma unroll
-          for (int o = 0; o < NLOG; o++) lg[o] = Lf[O_LOGIT + tid * 8 + o];
-#pragma unroll
-          for (int k = 0; k < 4; k++) sc[k] = __fadd_rn(brax::softplus_f32(lg[4 + k]), a.min_std);
-          const float lp = brax::log_prob(lg, raw, sc);
-          const float rho = expf(lp - a.logp[row]);
-          const float A = a.norm_adv ? __fdiv_rn(a.adv[q] - an.mu, an.den) : a.adv[q];
-          if (a.d_adv) a.d_adv[q] = A;
-          // the clipped surrogate and its derivative: learner.h row_terms' tie rule and closed clamp interval
-          const float cr = fminf(fmaxf(rho, 1.f - a.clip), 1.f + a.clip);
-          const float sa = rho * A, sb = cr * A;
-          const float w1 = sa < sb ? 1.f : (sa == sb ? 0.5f : 0.f);
-          const float inr = (rho >= 1.f - a.clip && rho <= 1.f + a.clip) ? 1.f : 0.f;
-          const float dlp = -a.inv_rows * A * (w1 + (1.f - w1) * inr) * rho;
-          st0 += fminf(sa, sb);
-          // the entropy at x = loc + scale z: sum of 1/2 + 1/2 log 2 pi + log scale + 2 (log 2 - x - softplus(-2x));
-          // d/dx of the last term is -2 tanh(x)
-          constexpr float HALF_LOG_2PI = 0.918938533204672742f, LOG2 = 0.693147180559945309f;
-          float ent = 0.f;
-#pragma unroll
-          for (int k = 0; k < 4; k++) {
-            const float x = __fadd_rn(lg[k], __fmul_rn(sc[k], z[k]));
-            const float th = actor::tanh_f32(x);
-            const float det = 2.f * ((LOG2 - x) - brax::softplus_f32(-2.f * x));
-            ent += ((0.5f + HALF_LOG_2PI) + logf(sc[k])) + det;
-            const float isc = __fdiv_rn(1.f, sc[k]);
-            const float tt = (raw[k] - lg[k]) * isc;
-            const float dloc = dlp * tt * isc + ce * 2.f * th;
-            const float dscale = dlp * (tt * tt - 1.f) * isc - ce * (isc - 2.f * th * z[k]);
-            const float sig = __fdiv_rn(1.f, 1.f + expf(-lg[4 + k]));  // d softplus
-            d[k] = dloc;
-            d[4 + k] = dscale * sig;
-          }
-          st1 += ent;
+          policy_row_terms(a, Lf + O_LOGIT + tid * 8, q, an, ce, d, st0, st1);
         } else {
           const float err = a.vs[q] - Lf[O_LOGIT + tid * 8];
           d[0] = -0.5f * err * a.inv_rows;
@@ -579,6 +471,12 @@ int fail(int code, const char* msg) { return set_error(code, msg); }
 bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 }  // namespace
+
+hipError_t launch_gae(const Args& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_brax_gae, dim3(a.gae_blocks), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace braxl
 }  // namespace quadenv
 
@@ -649,8 +547,7 @@ int quad_brax_ppo_grad(const QuadBraxPPOParams* p, const QuadBraxPPOBatch* b, co
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (launch_lds<&k_brax_value>(dim3(l.nbv), dim3(LB), LDS_BYTES, s, a) != hipSuccess)
     return fail(QUAD_EHIP, "k_brax_value launch failed");
-  hipLaunchKernelGGL(k_brax_gae, dim3(l.gae_blocks), dim3(256), 0, s, a);
-  if (hipGetLastError() != hipSuccess) return fail(QUAD_EHIP, "k_brax_gae launch failed");
+  if (launch_gae(a, s) != hipSuccess) return fail(QUAD_EHIP, "k_brax_gae launch failed");
   if (launch_lds<&k_brax_grad>(dim3(2 * l.nb), dim3(LB), LDS_BYTES, s, a) != hipSuccess)
     return fail(QUAD_EHIP, "k_brax_grad launch failed");
   RArgs ra{};

@@ -65,6 +65,9 @@ class BraxPPOConfig:
     # compute each minibatch gradient in fused launches (FusedBraxLearner: quad_brax_ppo_grad + quad_clip_adam, Philox
     # entropy noise) instead of torch autograd (torch.Generator noise): another sample path of the same algorithm
     fused_update: bool = False
+    # the same for every two-hidden-layer net of the Brax actor's family (fused_brax_learner_for: FusedBraxLearner for
+    # (128, 128) ReLU, FusedBraxArchLearner -- quad_brax_ppo_arch_grad -- for every other member)
+    fused_update_arch: bool = False
 
 
 _ACT = {"relu": F.relu, "tanh": torch.tanh, "silu": F.silu}
@@ -272,6 +275,9 @@ class BraxPPO:
         if c.fused_update:
             from .fused import brax_update_family
             brax_update_family(c)  # ValueError naming the family
+        elif c.fused_update_arch:
+            from .fused import brax_update_arch_family
+            brax_update_arch_family(c)  # ValueError naming the general family
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)
         self.net = BraxActorCritic(env.obs_dim, 4, c).to(self.device)
@@ -286,11 +292,14 @@ class BraxPPO:
         self._flat = torch.zeros(sum(p.numel() for p in self.net.parameters()), device=self.device)
         from .ppo import bind_grad_bucket
         bind_grad_bucket(list(self.net.parameters()), self._flat)  # in-place all-reduce
-        self._learner = None     # FusedBraxLearner of self.net (fused_update)
+        self._learner = None     # FusedBraxLearner / FusedBraxArchLearner of self.net (fused_update / _arch)
         self._update_t = 0       # noise step of the next fused minibatch step: advances once per step, never reset
         if c.fused_update:
             from .fused import FusedBraxLearner
             self._learner = FusedBraxLearner(self.net, self.norm, c, opt=self.opt, seed=self.seed)
+        elif c.fused_update_arch:
+            from .fused import fused_brax_learner_for
+            self._learner = fused_brax_learner_for(self.net, self.norm, c, opt=self.opt, seed=self.seed)
 
     @torch.no_grad()
     def _unrolls_fused(self):
@@ -352,7 +361,8 @@ class BraxPPO:
     def training_step(self) -> BraxStepStats:
         """Unrolls, the statistics update, then num_updates_per_batch passes over a fresh permutation of the
         trajectories in num_minibatches minibatches. A minibatch step is the gradient (autograd of brax_ppo_loss, or
-        with fused_update FusedBraxLearner.grads: no transposed copies), the all-reduce when world > 1, Adam's step."""
+        with fused_update / fused_update_arch the fused learner's grads: no transposed copies), the all-reduce when
+        world > 1, Adam's step."""
         c = self.cfg
         t0 = time.perf_counter()
         obs, nxt, raw, logp, rew, disc, trunc, finished, ret_sum = self._unrolls()
@@ -360,7 +370,7 @@ class BraxPPO:
         self.norm.update(obs)  # acme running statistics, after the unrolls
         M = U * N
         mb = M // c.num_minibatches
-        if c.fused_update:
+        if self._learner is not None:
             bufs = dict(obs=obs, nxt=nxt, raw=raw, logp=logp, rew=rew, disc=disc, trunc=trunc)
             st = torch.zeros(3, dtype=torch.float32, device=self.device)
             apply = self._learner.adam_step

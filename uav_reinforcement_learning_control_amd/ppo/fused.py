@@ -14,7 +14,9 @@ value net, quad_actor_critic_* / quad_actor_rollout) behind FusedPolicy's interf
 between it and `FusedPolicy`. `FusedBraxActor` is the Brax profile's policy (quad_brax_*:
 21-H1-H2-8 behind the running statistics, ReLU / tanh / SiLU, NormalTanh sampling) for evaluation episodes of the
 brax env kinds and for the learner's unrolls (sample, unroll). `FusedBraxLearner` is the Brax profile's minibatch
-gradient and Adam step (quad_brax_ppo_grad, quad_clip_adam) for (128, 128) ReLU policy and value nets.
+gradient and Adam step (quad_brax_ppo_grad, quad_clip_adam) for (128, 128) ReLU policy and value nets;
+`FusedBraxArchLearner` is the same for every two-hidden-layer net of the Brax actor's family (quad_brax_ppo_arch_grad),
+and `fused_brax_learner_for` chooses between them.
 """
 from __future__ import annotations
 
@@ -699,24 +701,34 @@ class FusedBraxLearner:
     parameters' .grad tensors; adam_step() updates the parameters through the state tensors of `opt` (the learner's
     own torch.optim.Adam), so opt.state_dict() and checkpoints stay what they are."""
 
+    entry = "quad_brax_ppo_grad"             # the C entry point grads() calls
+    _family, _check = _BRAX_UPDATE_FAMILY, staticmethod(brax_update_family)
+
     def __init__(self, net, norm, cfg, opt: Optional[torch.optim.Adam] = None, seed: int = 0):
-        brax_update_family(cfg)
+        self._check(cfg)
         self.net, self.norm, self.cfg, self.opt, self.seed = net, norm, cfg, opt, int(seed)
         self.params = [*net.policy.kernels, *net.policy.biases, *net.value.kernels, *net.value.biases]
         shapes = [tuple(p.shape) for p in self.params]
-        h = N.BRAX_PPO_HIDDEN[0]
-        want = [(N.BRAX_OBS, h), (h, h), (h, N.BRAX_LOGITS), (h,), (h,), (N.BRAX_LOGITS,),
-                (N.BRAX_OBS, h), (h, h), (h, 1), (h,), (h,), (1,)]
+        (p1, p2), (v1, v2) = self.sizes = self._sizes(cfg)
+        want = [(N.BRAX_OBS, p1), (p1, p2), (p2, N.BRAX_LOGITS), (p1,), (p2,), (N.BRAX_LOGITS,),
+                (N.BRAX_OBS, v1), (v1, v2), (v2, 1), (v1,), (v2,), (1,)]
         if shapes != want:
-            raise ValueError(f"{_BRAX_UPDATE_FAMILY} on 21-D observations and 4-D actions, got {shapes}")
+            raise ValueError(f"{self._family} on 21-D observations and 4-D actions, got {shapes}")
         self.device = self.params[0].device
         if self.device.type != "cuda":
-            raise N.QuadError("FusedBraxLearner needs the nets on a ROCm GPU")
+            raise N.QuadError(f"{type(self).__name__} needs the nets on a ROCm GPU")
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous():
                 raise ValueError("parameters must be contiguous float32")
         self._ws = Workspace(self.device)
         self._adam = None
+
+    @staticmethod
+    def _sizes(cfg):
+        return N.BRAX_PPO_HIDDEN, N.BRAX_PPO_HIDDEN
+
+    def _workspace_bytes(self, prm, mb: int, L: int) -> int:
+        return int(N.lib().quad_brax_ppo_workspace_bytes(mb, L))
 
     def _ordered(self, ts):
         """[k0, k1, k2, b0, b1, b2] of each net -> w0, b0, w1, b1, w2, b2 of the policy, then of the value net."""
@@ -732,8 +744,8 @@ class FusedBraxLearner:
         overwrite the parameters' .grad (created when absent)."""
         prm, b, grd = self.describe(buffers, index, entropy_noise=entropy_noise, noise_step=noise_step, stats=stats,
                                     diag=diag)
-        N.check(N.lib().quad_brax_ppo_grad(C.byref(prm), C.byref(b), C.byref(grd), self._ws.ptr, self._ws.nbytes,
-                                           current_stream(self.device)), "quad_brax_ppo_grad")
+        N.check(getattr(N.lib(), self.entry)(C.byref(prm), C.byref(b), C.byref(grd), self._ws.ptr, self._ws.nbytes,
+                                             current_stream(self.device)), self.entry)
 
     def describe(self, buffers: dict, index: torch.Tensor, *, entropy_noise=None, noise_step: int = 0, stats=None,
                  diag: Optional[dict] = None):
@@ -763,11 +775,14 @@ class FusedBraxLearner:
         mean, std = self.norm.mean, self.norm.std
         _need(mean, (N.BRAX_OBS,), f32, dev, "mean")
         _need(std, (N.BRAX_OBS,), f32, dev, "std")
-        self._ws.reserve(max(int(N.lib().quad_brax_ppo_workspace_bytes(mb, L)), 16))
-        h = N.BRAX_PPO_HIDDEN
+        (p1, p2), (v1, v2) = self.sizes
         prm = N.QuadBraxPPOParams(*[p.data_ptr() for p in self._ordered(self.params)], mean.data_ptr(),
-                                  std.data_ptr(), float(self.net.dist.min_std), h[0], h[1], h[0], h[1],
+                                  std.data_ptr(), float(self.net.dist.min_std), p1, p2, v1, v2,
                                   N.BRAX_ACTFNS[c.activation])
+        need = self._workspace_bytes(prm, mb, L)
+        if need <= 0:
+            raise ValueError(f"{self.entry}: a minibatch of {mb} trajectories of {L} steps is outside its limits")
+        self._ws.reserve(max(need, 16))
         grd = N.QuadBraxPPOGrads(*[p.grad.data_ptr() for p in self._ordered(self.params)])
         b = N.QuadBraxPPOBatch(
             obs=obs.data_ptr(), next_obs=buffers["nxt"].data_ptr(), raw=buffers["raw"].data_ptr(),
@@ -786,8 +801,71 @@ class FusedBraxLearner:
         """opt.step() of the learner's Adam (optax defaults: no clipping, eps 1e-8) as quad_clip_adam on the
         optimizer's own state tensors."""
         if self.opt is None:
-            raise ValueError("FusedBraxLearner.adam_step needs the optimizer (opt=...)")
+            raise ValueError(f"{type(self).__name__}.adam_step needs the optimizer (opt=...)")
         if self._adam is None:
             from .learner import FusedAdam
             self._adam = FusedAdam(self.opt, 0.0)
         self._adam.step()
+
+
+# (num_envs, num_minibatches, unroll_length, (policy sizes, value sizes, activation)) for which the general family's
+# fused update did not beat the torch update in profiles/brax_arch_update/bench.json (DESIGN 26, by 19's to 22's rule)
+BRAX_ARCH_UPDATE_KEEP_TORCH = frozenset()
+
+_BRAX_UPDATE_ARCH_FAMILY = ("the general fused Brax update (quad_brax_ppo_arch_grad) trains two-hidden-layer policy and "
+                            f"value nets (h1, h2), each h1 a multiple of 32 in [32, {N.BRAX_PPO_ARCH_MAX_H1}], each h2 in "
+                            f"{N.BRAX_PPO_ARCH_H2}, one of relu / tanh / silu, unroll_length in [1, {N.BRAX_PPO_MAX_L}]")
+
+
+def _brax_arch_sizes(cfg):
+    return (tuple(int(x) for x in cfg.policy_hidden_sizes), tuple(int(x) for x in cfg.value_hidden_sizes))
+
+
+def brax_update_arch_family(cfg) -> None:
+    """ValueError naming the family unless cfg's nets, activation and unroll length are quad_brax_ppo_arch_grad's."""
+    sizes = _brax_arch_sizes(cfg)
+    ok = all(len(s) == 2 and s[0] % 32 == 0 and 32 <= s[0] <= N.BRAX_PPO_ARCH_MAX_H1 and s[1] in N.BRAX_PPO_ARCH_H2
+             for s in sizes)
+    if not ok or cfg.activation not in N.BRAX_ACTFNS or not 1 <= int(cfg.unroll_length) <= N.BRAX_PPO_MAX_L:
+        raise ValueError(f"{_BRAX_UPDATE_ARCH_FAMILY}, got policy {sizes[0]}, value {sizes[1]}, {cfg.activation!r}, "
+                         f"unroll_length {cfg.unroll_length}")
+
+
+def brax_update_arch_supported(cfg, env=None) -> bool:
+    """The general fused update where its family holds and it did not lose to the torch update
+    (BRAX_ARCH_UPDATE_KEEP_TORCH)."""
+    try:
+        brax_update_arch_family(cfg)
+    except (ValueError, TypeError, AttributeError):
+        return False
+    if env is not None and getattr(env, "device", torch.device("cpu")).type != "cuda":
+        return False
+    key = (int(cfg.num_envs), int(cfg.num_minibatches), int(cfg.unroll_length), (*_brax_arch_sizes(cfg), cfg.activation))
+    return key not in BRAX_ARCH_UPDATE_KEEP_TORCH
+
+
+class FusedBraxArchLearner(FusedBraxLearner):
+    """FusedBraxLearner for every two-hidden-layer net of the Brax actor's family (csrc/brax_learner_arch.hip,
+    quad_brax_ppo_arch_grad: five launches): tanh, SiLU and ReLU, h1 up to 512, h2 up to 256, the policy's and the
+    value net's sizes independent. The interface -- grads, describe, adam_step, params -- is FusedBraxLearner's."""
+
+    entry = "quad_brax_ppo_arch_grad"
+    _family, _check = _BRAX_UPDATE_ARCH_FAMILY, staticmethod(brax_update_arch_family)
+    _sizes = staticmethod(_brax_arch_sizes)
+
+    def _workspace_bytes(self, prm, mb: int, L: int) -> int:
+        return int(N.lib().quad_brax_ppo_arch_workspace_bytes(C.byref(prm), mb, L))
+
+
+def brax_learner_class_for(cfg):
+    """FusedBraxLearner for (128, 128) ReLU policy and value nets -- the specialised kernels keep their net, as
+    fused_learner_for's do -- and FusedBraxArchLearner for every other member of the general family; ValueError
+    naming that family outside it."""
+    brax_update_arch_family(cfg)
+    special = _brax_arch_sizes(cfg) == (N.BRAX_PPO_HIDDEN, N.BRAX_PPO_HIDDEN) and cfg.activation == "relu"
+    return FusedBraxLearner if special else FusedBraxArchLearner
+
+
+def fused_brax_learner_for(net, norm, cfg, opt: Optional[torch.optim.Adam] = None, seed: int = 0):
+    """The fused learner of a BraxActorCritic of the general family: brax_learner_class_for(cfg)'s class."""
+    return brax_learner_class_for(cfg)(net, norm, cfg, opt=opt, seed=seed)

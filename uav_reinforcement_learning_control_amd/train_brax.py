@@ -7,7 +7,9 @@ Same arguments and defaults as train_brax_ppo.py where they apply (the JAX/MJX-s
 evaluation (K evaluations evenly spaced over the run on a separate eval env, BraxPPO.evaluate: one launch per
 evaluation); its default here is 0, so a run without the flag prints and writes what it always did. --fused-unroll
 collects each training step's unrolls in one launch (ppo/fused.py FusedBraxActor.unroll), off by default;
---fused-update computes each minibatch gradient in fused launches (ppo/fused.py FusedBraxLearner), off by default. Outputs mirror the
+--fused-update computes each minibatch gradient in fused launches (ppo/fused.py FusedBraxLearner), off by default;
+--fused-arch-update does so for every two-hidden-layer net of the Brax actor's family (tanh, SiLU, wider, policy and
+value of different sizes: ppo/fused.py fused_brax_learner_for), off by default. Outputs mirror the
 reference's run directory: <output-dir>/<timestamp>/ppo_params.msgpack (brax model.save_params
 format, ppo/brax_ppo.py + export.save_brax_params), checkpoints/params_step_<n>.msgpack every
 --checkpoint-interval steps, and training_summary.json.
@@ -98,6 +100,11 @@ def parse(argv=None):
                     help="compute each minibatch gradient in four fused launches (quad_brax_ppo_grad, Philox entropy\n"
                          "noise) and step Adam with quad_clip_adam instead of torch autograd; needs (128, 128) ReLU\n"
                          "policy and value nets. Off by default: the output of a run without the flag is unchanged")
+    ap.add_argument("--fused-arch-update", action="store_true",
+                    help="the fused minibatch gradient for every two-hidden-layer policy and value net of the MFMA\n"
+                         "family (h1 a multiple of 32 up to 512, h2 in 64 / 128 / 256, relu / tanh / silu, the two\n"
+                         "nets' sizes independent): quad_brax_ppo_arch_grad, and quad_brax_ppo_grad for (128, 128)\n"
+                         "ReLU. Off by default: the output of a run without the flag is unchanged")
     return ap.parse_args(argv)
 
 
@@ -115,7 +122,8 @@ def main(argv=None):
                         num_updates_per_batch=a.num_updates_per_batch, gae_lambda=a.gae_lambda,
                         reward_scaling=a.reward_scaling, policy_hidden_sizes=_sizes(a.policy_hidden_sizes),
                         value_hidden_sizes=_sizes(a.value_hidden_sizes), activation=a.activation,
-                        fused_unroll=a.fused_unroll, fused_update=a.fused_update)
+                        fused_unroll=a.fused_unroll, fused_update=a.fused_update,
+                        fused_update_arch=a.fused_arch_update)
     kind = {"hover": "brax_hover", "jax_mjx_quad": "brax_jax_mjx"}[a.env]
     env = QuadVecEnv(a.num_envs, env=kind, device=f"cuda:{local}", seed=a.seed, env_id_base=rank * a.num_envs,
                      max_episode_steps=a.episode_length, cfg_overrides={"traj_duration": a.traj_duration_seconds})
@@ -132,6 +140,10 @@ def main(argv=None):
     if a.fused_update and rank == 0:
         print(f"update: fused minibatch gradient ({cfg.num_updates_per_batch} x {cfg.num_minibatches} steps of "
               f"quad_brax_ppo_grad + quad_clip_adam per training step)", flush=True)
+    if a.fused_arch_update and not a.fused_update and rank == 0:
+        print(f"update: fused minibatch gradient, general family (policy {tuple(cfg.policy_hidden_sizes)}, value "
+              f"{tuple(cfg.value_hidden_sizes)}, {cfg.activation}: {cfg.num_updates_per_batch} x {cfg.num_minibatches} "
+              f"steps of {type(model._learner).entry} + quad_clip_adam per training step)", flush=True)
     stamp = datetime.now().strftime("%Y%m%d_%H%M%S")
     run = os.path.abspath(os.path.join(a.output_dir, stamp))
     ckdir = os.path.join(run, "checkpoints")
@@ -187,6 +199,8 @@ def main(argv=None):
             summary["fused_unroll"] = True
         if a.fused_update:
             summary["fused_update"] = True
+        if a.fused_arch_update:
+            summary["fused_arch_update"] = True
         if a.num_evals > 0:
             summary["num_evals"] = a.num_evals
             summary["final_metrics"]["eval/episode_reward"] = eval_reward
