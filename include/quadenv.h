@@ -402,6 +402,17 @@ typedef struct QuadVelEst {
 int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
                     double timestamp, int32_t n, float* obs, float* vel_est, void* stream);
 
+/* quad_deploy_obs with one timestamp per row (device float64 [n]) and a code per row (device uint8 [n], or NULL:
+ * every row is 1), for a batch whose envs sit at different step counts and reset at different times:
+ *   0  the row is skipped: its estimator state, its obs row and its vel_est row stay untouched
+ *   1  the row is updated, as quad_deploy_obs updates it
+ *   2  the row's eight estimator words are set to zero first (a new VelocityEstimator), then it is updated
+ * Any other code is undefined (not checked on the device). The same two functions as quad_deploy_obs: with equal
+ * timestamps and rows == NULL it is bit-identical to it. The same argument checks, and timestamps is required. */
+int quad_deploy_obs_rows(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                         const double* timestamps, const uint8_t* rows, int32_t n, float* obs, float* vel_est,
+                         void* stream);
+
 /* The deterministic policy's whole episodes in ONE launch from the envs' current state: per step the actor
  * (MFMA), clip(mean, -1, 1), the env step, QuadPidRun's metrics, the estimator update and its error. Every
  * env runs until its first terminated / truncated step or max_steps and is then frozen, never reset (the
@@ -919,6 +930,32 @@ int quad_actor_critic_post(const QuadActorArch* arch, const float* packed, const
                            int32_t n, void* stream);
 int quad_actor_rollout(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadRollout* r,
                        void* stream);
+
+/* ---- quad_actor_rollout on the deployed observation: the policy is trained on what policy_node.py will
+ * hand it -- the velocity of QuadVelEst's low-pass on finite differences of the position, the normalised vector
+ * clipped to [-1, 1]. quad_actor_rollout's requirements and buffers; est->state (float64 [8][N], required) is read at
+ * entry and written at exit, est->alpha may be NULL (alpha_all), the timestamp of step count k is k * est_dt.
+ * Per env and step: both nets act on the deployed row in hand, which goes to obs_copy (sample, log-prob, clip and
+ * the stored rows as in quad_actor_rollout); the env step, unchanged; one estimator update on the step's state12
+ * position at (the env's step count after the step) * est_dt, and deploy_obs with the target the step's own
+ * observation was built with: row D. On a time-limit truncation the bootstrap is gamma * V(D). An env that finished
+ * is auto-reset as in quad_actor_rollout; its estimator is emptied (eight zeros) and updated once with the reset
+ * state's position at (the reset step count) * est_dt, and the next row in hand is deploy_obs of the reset state, as
+ * quad_observe reports it, with the new target (velocity 0); an env that did not finish carries D. At exit last_obs holds the row in hand and
+ * est->state the estimators, so a rollout split over several calls gives the bits of one call.
+ * Contract: bit-identical to this loop on a second handle, with cursor t = t0: per step quad_actor_critic_act, its
+ * epilogue reading a terminal_obs buffer that holds D; quad_step; quad_deploy_obs_rows (rows NULL, timestamps the
+ * new step counts * est_dt) on the step's state12 and the pre-reset target, D written to that buffer and to
+ * last_obs; quad_observe with state12, then quad_deploy_obs_rows into last_obs with code 2 on the rows that
+ * finished and 0 elsewhere (the handle's new target, timestamps the reset step counts * est_dt); and
+ * quad_actor_critic_post at the end.
+ * QUAD_EINVAL with nothing launched and nothing written: everything quad_actor_rollout refuses; a NULL est, a NULL
+ * est->state or one that is not 8-byte aligned; QuadVelEst's own checks (alpha_all, max_dt); est_dt <= 0 or not
+ * finite. quad_rollout (the 128-128 ReLU kernel, at its register limit) and the quad_pop_* forms have no deployed
+ * form: the family's (128, 128) ReLU instance collects that net. The added entry points did not change the ABI
+ * version. */
+int quad_actor_rollout_deployed(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadRollout* r,
+                                const QuadVelEst* est, double est_dt, void* stream);
 
 /* ---- PPO populations in lock-step launches (added within ABI v8, whose number an
  * existing layout test pins: a v8 library built before these entry points lacks the quad_pop_* exports, and the

@@ -266,7 +266,8 @@ EXPORTS = ("quad_abi_version", "quad_last_error", "quad_default_cfg", "quad_crea
            "quad_brax_ppo_arch_workspace_bytes", "quad_brax_ppo_arch_grad",
            "quad_ppo_arch_workspace_bytes", "quad_ppo_arch_grad",
            "quad_actor_critic_packed_floats", "quad_actor_critic_pack", "quad_actor_critic_act",
-           "quad_actor_critic_post", "quad_actor_rollout")
+           "quad_actor_critic_post", "quad_actor_rollout",
+           "quad_deploy_obs_rows", "quad_actor_rollout_deployed")
 
 
 class QuadRollout(C.Structure):
@@ -447,6 +448,14 @@ def _declare(L):
     L.quad_actor_rollout.argtypes = [vp, arch, vp, C.POINTER(QuadRollout), vp]
     for n in ("quad_actor_critic_pack", "quad_actor_critic_act", "quad_actor_critic_post", "quad_actor_rollout"):
         getattr(L, n).restype = C.c_int
+    # the deployed-observation rollout. A library built before it still loads (the A/B tools time such
+    # builds against this tree); need_deployed() is what the callers of the two entry points ask first
+    if hasattr(L, "quad_actor_rollout_deployed"):
+        L.quad_deploy_obs_rows.argtypes = [vp, C.POINTER(QuadVelEst), vp, vp, vp, vp, i32, vp, vp, vp]
+        L.quad_actor_rollout_deployed.argtypes = [vp, arch, vp, C.POINTER(QuadRollout), C.POINTER(QuadVelEst),
+                                                  C.c_double, vp]
+        for n in ("quad_deploy_obs_rows", "quad_actor_rollout_deployed"):
+            getattr(L, n).restype = C.c_int
     if not hasattr(L, "quad_pop_create"):  # the version number did not change with the quad_pop_* additions
         raise QuadError(f"{LIB_PATH} was built before the population entry points (quad_pop_*); rebuild it")
     L.quad_pop_detach_eval.argtypes = [vp]
@@ -497,6 +506,15 @@ def lib():
             raise QuadError("libquadenv.so ABI version mismatch; rebuild it")
         _lib = L
     return _lib
+
+
+def need_deployed():
+    """lib(), or QuadError when it was built before quad_deploy_obs_rows / quad_actor_rollout_deployed."""
+    L = lib()
+    if not hasattr(L, "quad_actor_rollout_deployed"):
+        raise QuadError(f"{LIB_PATH} was built before the deployed rollout's entry points "
+                        "(quad_actor_rollout_deployed); rebuild it")
+    return L
 
 
 def check(rc: int, what: str = "") -> None:

@@ -21,6 +21,8 @@
 //                               of two one-tile waves, env state and observation in registers for all steps, both
 //                               images' LDS parts staged once, the W2 pieces streamed from L2; a block with at most
 //                               32 envs runs its two nets on its two waves (split blocks, see the kernel)
+//   k_ac_rollout_deployed<KIND, CTBR, MB>  k_ac_rollout acting on quad_deploy.h's observation: the velocity estimator
+//                               in registers beside the env, updated after every step and emptied by a reset
 //   k_pop_ac_head, k_pop_ac_pack, k_pop_ac_value<MB>, k_pop_ac_rollout<KIND, CTBR, MB>
 //                               the population forms (population.h): the bodies of k_ac_head, the pack
 //                               kernel, k_ac_act and k_ac_rollout behind one more grid dimension, the member's
@@ -33,17 +35,22 @@
 //
 // Compiled once without AR_KIND (the entry points, k_ac_head / k_ac_act / k_ac_post, the launch dispatch) and once
 // per (AR_KIND, AR_MB): AR_KIND = 0 hover / 1 trajectory, AR_MB = H2 / 32 = 2 / 4 / 8 -- six objects of two
-// kernels each (CTBR or not) that build in parallel.
+// kernels each (CTBR or not) that build in parallel, and six more with AR_DEPLOYED: k_ac_rollout_deployed, the body in
+// its deployed-observation mode (quad_actor_rollout_deployed).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
+#include <string>
 
 #include "../../include/quadenv.h"
 #include "actor_arch.h"
 #include "dispatch.h"
 #include "env_tiles.h"
 #include "handle.h"
+#include "policy_episode.h"
 #include "population.h"
+#include "quad_deploy.h"
 #include "quad_physics.h"
 #include "rollout.h"
 
@@ -57,6 +64,11 @@ template <int AKIND, int MB>
 hipError_t launch_pop_actor_rollout_inst(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active,
                                          int count, int n, bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps,
                                          hipStream_t s);
+// one (kind, MB) deployed object's instantiations (AR_DEPLOYED)
+template <int AKIND, int MB>
+hipError_t launch_actor_rollout_deployed_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
+                                              const float* packed, const RollArgs& a, const EstArgs& est, double est_dt,
+                                              hipStream_t s);
 
 namespace {
 
@@ -171,10 +183,18 @@ __device__ __forceinline__ void store_row(float* __restrict__ base, size_t row, 
   b4[2] = make_float4(v[8], v[9], v[10], v[11]);
 }
 
-// k_ac_rollout's body, shared with the population form below (p.kc is the launch's noalias constant block)
-template <int KIND, bool CTBR, int MB>
+// k_ac_rollout's body, shared with the population form below (p.kc is the launch's noalias constant block).
+// MODE = QUAD_OBS_DEPLOYED (k_ac_rollout_deployed; est / est_dt are read in that mode only): the row in hand is the
+// deployed one. Every lane keeps its env's estimator (quad_deploy.h: eight float64 words, and alpha) in registers for
+// all steps and updates it after the env step, on the step's state12 at the new step count; the row D it builds
+// feeds the bootstrap and is the next row in hand. A reset empties the estimator and updates it once with the reset
+// state. In a split block both waves run the same update on the same values, so V(D) on the value wave is V of the
+// row the policy wave stores; the policy wave stores the estimators.
+template <int KIND, bool CTBR, int MB, int MODE = QUAD_OBS_ENV>
 __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams p, const float* __restrict__ packed,
-                                                actor::Net net, RollArgs a) {
+                                                actor::Net net, RollArgs a, EstArgs est = EstArgs{},
+                                                double est_dt = 0.0) {
+  constexpr bool DEP = MODE == QUAD_OBS_DEPLOYED;
   extern __shared__ float lds[];
   __shared__ uint32_t renv[2][64], rep[2][64];
   __shared__ float4 xmean[2][32];
@@ -212,6 +232,12 @@ __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams
     ob[8] = x2.x; ob[9] = x2.y; ob[10] = x2.z; ob[11] = x2.w;
   }
   float ls = a.last_start[i], ret = a.ep_ret[i], len = a.ep_len[i];
+  double ve[EST_NSTATE] = {}, alpha = 0.0;
+  if constexpr (DEP) {
+    alpha = est.alpha ? est.alpha[i] : est.alpha_all;
+#pragma unroll
+    for (int j = 0; j < EST_NSTATE; j++) ve[j] = est.state[size_t(j) * n + size_t(i)];
+  }
   // both images' LDS parts, once per launch: the policy net's at 0, the value net's behind it
   float* Lc = lds + lay.lds_floats();
   {
@@ -258,6 +284,11 @@ __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams
     StepRes r;
     env_step<float, CTBR>(K, e, ac, r);
     const bool done = r.term || r.trunc;
+    if constexpr (DEP) {  // row D: the estimator's sample of this step, the step's own target (before any reset)
+      double vel[3];
+      vel_est_update(alpha, est.max_dt, r.state12, double(e.step) * est_dt, ve, vel);
+      deploy_obs(K.obs_lo, K.obs_span, K.obs_rspan, r.state12, e.target, vel, r.obs);
+    }
     // ---- TimeLimit bootstrap: r += gamma V(terminal_obs) (the value net only if the wave holds one)
     const bool timeout = ok && r.trunc && !r.term;
     float tv = 0.f;
@@ -284,6 +315,16 @@ __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams
       reset_affine_u(K.init_lo, K.init_span, K.tgt_lo, K.tgt_span, u16, init12, tgt);
       env_reset_from<float, KIND>(K, e, init12, tgt, ob, s12);
       ep += 1u;
+      if constexpr (DEP) {  // a new VelocityEstimator, its first sample the reset state: velocity 0
+        // the state as quad_observe reports it (the attitude read back from the quaternion, as the node reads the
+        // mocap's and as the episode kernels' first row has it), not the drawn Euler angles
+        observe(K, e, ob, s12);
+        double vel[3];
+#pragma unroll
+        for (int j = 0; j < EST_NSTATE; j++) ve[j] = 0.0;
+        vel_est_update(alpha, est.max_dt, s12, double(e.step) * est_dt, ve, vel);
+        deploy_obs(K.obs_lo, K.obs_span, K.obs_rspan, s12, e.target, vel, ob);
+      }
     }
   }
 
@@ -295,6 +336,10 @@ __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams
     a.last_start[i] = ls;
     a.ep_ret[i] = ret;
     a.ep_len[i] = len;
+    if constexpr (DEP) {
+#pragma unroll
+      for (int j = 0; j < EST_NSTATE; j++) est.state[size_t(j) * n + size_t(i)] = ve[j];
+    }
   }
   // Monitor statistics: block sum into this block's slot (uncontended double atomics), as k_rollout's
   __shared__ double red[3][2];
@@ -311,6 +356,39 @@ __device__ __forceinline__ void ac_rollout_body(const KConsts<float>& K, KParams
   }
 }
 
+#if defined(AR_DEPLOYED)  // the deployed objects: k_ac_rollout's body in QUAD_OBS_DEPLOYED mode, and its launch
+template <int KIND, bool CTBR, int MB>
+__global__ __launch_bounds__(128) void k_ac_rollout_deployed(const KConsts<float>* __restrict__ kc, KParams p,
+                                                             const float* __restrict__ packed, actor::Net net,
+                                                             RollArgs a, EstArgs est, double est_dt) {
+  p.kc = kc;  // (k_ac_rollout's note)
+  ac_rollout_body<KIND, CTBR, MB, QUAD_OBS_DEPLOYED>(*kc, p, packed, net, a, est, est_dt);
+}
+
+}  // namespace
+
+template <int AKIND, int MB>
+hipError_t launch_actor_rollout_deployed_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
+                                              const float* packed, const RollArgs& a, const EstArgs& est, double est_dt,
+                                              hipStream_t s) {
+  const actor::Net dn{net.nb1, net.actfn};
+  constexpr int MAX_BYTES = 2 * arch::Layout{actor::MAX_H1 / 32, MB}.lds_bytes();  // (launch_actor_rollout_inst's rule)
+  const int bytes = 2 * arch::Layout{net.nb1, MB}.lds_bytes();
+  constexpr int KIND = AKIND == 1 ? QUAD_ENV_TRAJ : QUAD_ENV_HOVER;
+  const dim3 grid((kp.n + 63) / 64), block(128);
+  return with_bool(ctbr, [&](auto cb) {
+    constexpr bool CB = decltype(cb)::value;
+    if (const hipError_t e = lds_opt_in<&k_ac_rollout_deployed<KIND, CB, MB>>(MAX_BYTES)) return e;
+    return launch_lds<&k_ac_rollout_deployed<KIND, CB, MB>>(grid, block, bytes, s, kc, kp, packed, dn, a, est, est_dt);
+  });
+}
+template hipError_t launch_actor_rollout_deployed_inst<AR_KIND, AR_MB>(const KConsts<float>*, const KParams&, bool,
+                                                                       const ActorNet&, const float*, const RollArgs&,
+                                                                       const EstArgs&, double, hipStream_t);
+
+}  // namespace quadenv
+
+#else  // the env-observation objects
 template <int KIND, bool CTBR, int MB>
 __global__ __launch_bounds__(128) void k_ac_rollout(const KConsts<float>* __restrict__ kc, KParams p,
                                                     const float* __restrict__ packed, actor::Net net, RollArgs a) {
@@ -379,6 +457,7 @@ template hipError_t launch_actor_rollout_inst<AR_KIND, AR_MB>(const KConsts<floa
                                                               hipStream_t);
 
 }  // namespace quadenv
+#endif  // AR_DEPLOYED
 
 #else  // the C entry points' object
 
@@ -652,6 +731,39 @@ hipError_t launch_by_mb(const KConsts<float>* kc, const KParams& kp, bool ctbr, 
 }
 
 template <int AKIND>
+hipError_t launch_deployed_by_mb(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
+                                 const float* packed, const RollArgs& a, const EstArgs& est, double est_dt,
+                                 hipStream_t s) {
+  return with_mb(net.mb, [&](auto mb) {
+    return launch_actor_rollout_deployed_inst<AKIND, decltype(mb)::value>(kc, kp, ctbr, net, packed, a, est, est_dt, s);
+  });
+}
+
+// quad_actor_rollout's argument checks and its flattened arguments (also quad_actor_rollout_deployed's)
+int rollout_args(const QuadHandle* h, const QuadActorArch* arch_, const float* packed, const QuadRollout* r,
+                 const char* who, ActorNet* net, RollArgs* out) {
+  const std::string w(who);
+  if (int rc = ac_net_of(arch_, net)) return rc;
+  if (!h || !packed || !r) return fail(QUAD_EINVAL, w + ": handle/packed/rollout is NULL");
+  if (!r->obs_copy || !r->actions || !r->log_prob || !r->value || !r->episode_starts || !r->rewards ||
+      !r->last_obs || !r->last_start || !r->ep_ret || !r->ep_len || !r->stats)
+    return fail(QUAD_EINVAL, w + ": NULL buffer");
+  if (r->rows < 1 || r->steps < 1 || r->t0 < 0) return fail(QUAD_EINVAL, w + ": rows, steps >= 1, t0 >= 0");
+  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(r->actions) |
+       reinterpret_cast<uintptr_t>(r->obs_copy) | reinterpret_cast<uintptr_t>(r->last_obs)) & 15u)
+    return fail(QUAD_EINVAL, w + ": packed, actions, obs_copy and last_obs must be 16-byte aligned");
+  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
+  if (h->cfg.wrapper != QUAD_WRAP_NONE && h->cfg.wrapper != QUAD_WRAP_CTBR)
+    return fail(QUAD_EINVAL, w + ": the policy takes 12-D obs (wrapper NONE or CTBR)");
+  if (!h->cfg.auto_reset) return fail(QUAD_EINVAL, w + ": the handle needs auto_reset = 1");
+  *out = RollArgs{r->obs_copy, r->actions, r->log_prob, r->value, r->episode_starts, r->rewards, r->last_obs,
+                  r->last_start, r->ep_ret, r->ep_len, r->stats, uint32_t(r->rows), uint32_t(r->t0), r->steps,
+                  r->deterministic, r->seed, r->gamma};
+  return QUAD_OK;
+}
+
+template <int AKIND>
 hipError_t launch_pop_by_mb(const KConsts<float>* kc, const pop::RollEntry* tab, const int32_t* active, int count, int n,
                             bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps, hipStream_t s) {
   return with_mb(net.mb, [&](auto mb) {
@@ -789,30 +901,36 @@ int quad_actor_critic_post(const QuadActorArch* arch_, const float* packed, cons
 int quad_actor_rollout(QuadHandle* h, const QuadActorArch* arch_, const float* packed, const QuadRollout* r,
                        void* stream) {
   ActorNet net;
-  if (int rc = ac_net_of(arch_, &net)) return rc;
-  if (!h || !packed || !r) return fail(QUAD_EINVAL, "quad_actor_rollout: handle/packed/rollout is NULL");
-  if (!r->obs_copy || !r->actions || !r->log_prob || !r->value || !r->episode_starts || !r->rewards ||
-      !r->last_obs || !r->last_start || !r->ep_ret || !r->ep_len || !r->stats)
-    return fail(QUAD_EINVAL, "quad_actor_rollout: NULL buffer");
-  if (r->rows < 1 || r->steps < 1 || r->t0 < 0)
-    return fail(QUAD_EINVAL, "quad_actor_rollout: rows, steps >= 1, t0 >= 0");
-  if ((reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(r->actions) |
-       reinterpret_cast<uintptr_t>(r->obs_copy) | reinterpret_cast<uintptr_t>(r->last_obs)) & 15u)
-    return fail(QUAD_EINVAL, "quad_actor_rollout: packed, actions, obs_copy and last_obs must be 16-byte aligned");
-  if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_actor_rollout: env_kind must be HOVER or TRAJ");
-  if (h->cfg.wrapper != QUAD_WRAP_NONE && h->cfg.wrapper != QUAD_WRAP_CTBR)
-    return fail(QUAD_EINVAL, "quad_actor_rollout: the policy takes 12-D obs (wrapper NONE or CTBR)");
-  if (!h->cfg.auto_reset) return fail(QUAD_EINVAL, "quad_actor_rollout: the handle needs auto_reset = 1");
+  RollArgs a;
+  if (int rc = rollout_args(h, arch_, packed, r, "quad_actor_rollout", &net, &a)) return rc;
   DeviceGuard g(h->device);
-  const RollArgs a{r->obs_copy, r->actions, r->log_prob, r->value, r->episode_starts, r->rewards, r->last_obs,
-                   r->last_start, r->ep_ret, r->ep_len, r->stats, uint32_t(r->rows), uint32_t(r->t0), r->steps,
-                   r->deterministic, r->seed, r->gamma};
   const bool ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const hipError_t e = h->cfg.env_kind == QUAD_ENV_TRAJ ? launch_by_mb<1>(h->kdev, h->kp, ctbr, net, packed, a, s)
                                                         : launch_by_mb<0>(h->kdev, h->kp, ctbr, net, packed, a, s);
   return e == hipSuccess ? QUAD_OK : hip_fail(e, "k_ac_rollout launch");
+}
+
+int quad_actor_rollout_deployed(QuadHandle* h, const QuadActorArch* arch_, const float* packed, const QuadRollout* r,
+                                const QuadVelEst* est, double est_dt, void* stream) {
+  ActorNet net;
+  RollArgs a;
+  if (int rc = rollout_args(h, arch_, packed, r, "quad_actor_rollout_deployed", &net, &a)) return rc;
+  if (!est) return fail(QUAD_EINVAL, "quad_actor_rollout_deployed: est is NULL");
+  if (int rc = check_est(est, "quad_actor_rollout_deployed")) return rc;
+  if (!est->state) return fail(QUAD_EINVAL, "quad_actor_rollout_deployed: the estimator state block is required");
+  if ((reinterpret_cast<uintptr_t>(est->state) | reinterpret_cast<uintptr_t>(est->alpha)) & 7u)
+    return fail(QUAD_EINVAL, "quad_actor_rollout_deployed: est->state and est->alpha must be 8-byte aligned");
+  if (!(est_dt > 0.0) || !std::isfinite(est_dt))
+    return fail(QUAD_EINVAL, "quad_actor_rollout_deployed: est_dt must be > 0 and finite");
+  DeviceGuard g(h->device);
+  const bool ctbr = h->cfg.wrapper == QUAD_WRAP_CTBR;
+  const EstArgs ea{est->alpha, est->alpha_all, est->max_dt, est->state};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const hipError_t e = h->cfg.env_kind == QUAD_ENV_TRAJ
+                           ? launch_deployed_by_mb<1>(h->kdev, h->kp, ctbr, net, packed, a, ea, est_dt, s)
+                           : launch_deployed_by_mb<0>(h->kdev, h->kp, ctbr, net, packed, a, ea, est_dt, s);
+  return e == hipSuccess ? QUAD_OK : hip_fail(e, "k_ac_rollout_deployed launch");
 }
 
 }  // extern "C"

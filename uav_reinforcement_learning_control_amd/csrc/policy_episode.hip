@@ -2,7 +2,8 @@
 // (quad_policy_episode), and the deployed observation law alone (quad_deploy_obs).
 //
 // Kernels
-//   k_deploy_obs                               vel_est_update + deploy_obs (quad_deploy.h) over [n,12]
+//   k_deploy_obs, k_deploy_obs_rows            vel_est_update + deploy_obs (quad_deploy.h) over [n,12]: one timestamp,
+//                                              or one timestamp and one code (skip / update / empty first) per row
 //                                              states, caller-owned [8][n] estimator block
 //   k_policy_episode<KIND, CTBR, NT, SPEC, MODE, EB>
 //                                              the fused closed loop: k_rollout's block shape and
@@ -199,13 +200,12 @@ hipError_t launch(const KConsts<float>* kc, const KParams& kp, const float* pack
 #if PE_KIND == 0
 constexpr int DEPLOY_BLOCK = 256;
 
-__global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float>* __restrict__ kc, EstArgs est,
-                                                             const float* __restrict__ state12,
-                                                             const float* __restrict__ target3, double timestamp,
-                                                             int32_t n, float* __restrict__ obs,
-                                                             float* __restrict__ vel_est) {
-  const int i = blockIdx.x * DEPLOY_BLOCK + threadIdx.x;
-  if (i >= n) return;
+// one row of quad_deploy_obs / quad_deploy_obs_rows; code: 0 skip, 1 update, 2 empty the estimator first
+__device__ __forceinline__ void deploy_row(const KConsts<float>* __restrict__ kc, const EstArgs& est,
+                                           const float* __restrict__ state12, const float* __restrict__ target3,
+                                           double timestamp, int code, int i, int32_t n, float* __restrict__ obs,
+                                           float* __restrict__ vel_est) {
+  if (code == 0) return;
   float s[12], tg[3];
 #pragma unroll
   for (int j = 0; j < 12; j++) s[j] = state12[size_t(i) * 12 + j];
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float
   for (int j = 0; j < 3; j++) tg[j] = target3[size_t(i) * 3 + j];
   double st[EST_NSTATE], vel[3];
 #pragma unroll
-  for (int j = 0; j < EST_NSTATE; j++) st[j] = est.state[size_t(j) * size_t(n) + size_t(i)];
+  for (int j = 0; j < EST_NSTATE; j++) st[j] = code == 2 ? 0.0 : est.state[size_t(j) * size_t(n) + size_t(i)];
   vel_est_update(est.alpha ? est.alpha[i] : est.alpha_all, est.max_dt, s, timestamp, st, vel);
 #pragma unroll
   for (int j = 0; j < EST_NSTATE; j++) est.state[size_t(j) * size_t(n) + size_t(i)] = st[j];
@@ -225,6 +225,27 @@ __global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float
 #pragma unroll
     for (int j = 0; j < 3; j++) vel_est[size_t(i) * 3 + j] = float(vel[j]);
   }
+}
+
+__global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs(const KConsts<float>* __restrict__ kc, EstArgs est,
+                                                             const float* __restrict__ state12,
+                                                             const float* __restrict__ target3, double timestamp,
+                                                             int32_t n, float* __restrict__ obs,
+                                                             float* __restrict__ vel_est) {
+  const int i = blockIdx.x * DEPLOY_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  deploy_row(kc, est, state12, target3, timestamp, 1, i, n, obs, vel_est);
+}
+
+__global__ __launch_bounds__(DEPLOY_BLOCK) void k_deploy_obs_rows(const KConsts<float>* __restrict__ kc, EstArgs est,
+                                                                  const float* __restrict__ state12,
+                                                                  const float* __restrict__ target3,
+                                                                  const double* __restrict__ timestamps,
+                                                                  const uint8_t* __restrict__ rows, int32_t n,
+                                                                  float* __restrict__ obs, float* __restrict__ vel_est) {
+  const int i = blockIdx.x * DEPLOY_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  deploy_row(kc, est, state12, target3, timestamps[i], rows ? int(rows[i]) : 1, i, n, obs, vel_est);
 }
 #endif
 
@@ -335,19 +356,40 @@ using namespace quadenv;
 
 extern "C" {
 
-int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
-                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
+// quad_deploy_obs' and quad_deploy_obs_rows' argument checks
+static int deploy_obs_args(const QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                           int32_t n, const float* obs, const char* who) {
+  const std::string w(who);
   if (!h || !est) return fail(QUAD_EINVAL, "handle/est is NULL");
   if (h->cfg.env_kind != QUAD_ENV_HOVER && h->cfg.env_kind != QUAD_ENV_TRAJ)
-    return fail(QUAD_EINVAL, "quad_deploy_obs: env_kind must be HOVER or TRAJ");
-  if (int rc = check_est(est, "quad_deploy_obs")) return rc;
-  if (!est->state) return fail(QUAD_EINVAL, "quad_deploy_obs: the estimator state block is required");
-  if (!state12 || !target3 || !obs) return fail(QUAD_EINVAL, "quad_deploy_obs: state12, target3 and obs are required");
-  if (n < 1) return fail(QUAD_EINVAL, "quad_deploy_obs: n must be >= 1");
+    return fail(QUAD_EINVAL, w + ": env_kind must be HOVER or TRAJ");
+  if (int rc = check_est(est, who)) return rc;
+  if (!est->state) return fail(QUAD_EINVAL, w + ": the estimator state block is required");
+  if (!state12 || !target3 || !obs) return fail(QUAD_EINVAL, w + ": state12, target3 and obs are required");
+  if (n < 1) return fail(QUAD_EINVAL, w + ": n must be >= 1");
+  return QUAD_OK;
+}
+
+int quad_deploy_obs(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                    double timestamp, int32_t n, float* obs, float* vel_est, void* stream) {
+  if (int rc = deploy_obs_args(h, est, state12, target3, n, obs, "quad_deploy_obs")) return rc;
   DeviceGuard g(h->device);
   hipLaunchKernelGGL(k_deploy_obs, dim3((n + DEPLOY_BLOCK - 1) / DEPLOY_BLOCK), dim3(DEPLOY_BLOCK), 0,
                      static_cast<hipStream_t>(stream), h->kdev, EstArgs{est->alpha, est->alpha_all, est->max_dt, est->state},
                      state12, target3, timestamp, n, obs, vel_est);
+  HIP_TRY(hipGetLastError());
+  return QUAD_OK;
+}
+
+int quad_deploy_obs_rows(QuadHandle* h, const QuadVelEst* est, const float* state12, const float* target3,
+                         const double* timestamps, const uint8_t* rows, int32_t n, float* obs, float* vel_est,
+                         void* stream) {
+  if (int rc = deploy_obs_args(h, est, state12, target3, n, obs, "quad_deploy_obs_rows")) return rc;
+  if (!timestamps) return fail(QUAD_EINVAL, "quad_deploy_obs_rows: timestamps is required");
+  DeviceGuard g(h->device);
+  hipLaunchKernelGGL(k_deploy_obs_rows, dim3((n + DEPLOY_BLOCK - 1) / DEPLOY_BLOCK), dim3(DEPLOY_BLOCK), 0,
+                     static_cast<hipStream_t>(stream), h->kdev, EstArgs{est->alpha, est->alpha_all, est->max_dt, est->state},
+                     state12, target3, timestamps, rows, n, obs, vel_est);
   HIP_TRY(hipGetLastError());
   return QUAD_OK;
 }

@@ -289,6 +289,35 @@ class QuadVecEnv:
                                         _ptr(out), _ptr(vel_est), self._stream()), "quad_deploy_obs")
         return out
 
+    def deploy_obs_rows(self, state12: torch.Tensor, target3: torch.Tensor, timestamps: torch.Tensor,
+                        est_state: torch.Tensor, rows: Optional[torch.Tensor] = None, alpha=None,
+                        alpha_all: float = 0.8, max_dt: float = 0.1, out: Optional[torch.Tensor] = None,
+                        vel_est: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """deploy_obs with one timestamp per row (quad_deploy_obs_rows): timestamps float64 [n]; rows uint8 [n] or
+        None (every row updated): 0 leaves the row's estimator, obs and vel_est untouched, 1 updates it, 2 empties
+        its estimator first (an episode start). `out` is required with `rows` (skipped rows keep what it holds)."""
+        n = int(state12.shape[0])
+        self._check(state12, (n, 12), torch.float32)
+        self._check(target3, (n, 3), torch.float32)
+        self._check(timestamps, (n,), torch.float64)
+        self._check(est_state, (N.EST_NSTATE, n), torch.float64)
+        if rows is not None:
+            self._check(rows, (n,), torch.uint8)
+            if out is None:
+                raise ValueError("deploy_obs_rows: give `out` with `rows` (skipped rows keep its contents)")
+        out = torch.empty(n, 12, dtype=torch.float32, device=self.device) if out is None else out
+        self._check(out, (n, 12), torch.float32)
+        if vel_est is not None:
+            self._check(vel_est, (n, 3), torch.float32)
+        if alpha is not None:
+            self._check(alpha, (n,), torch.float64)
+        est = N.QuadVelEst(alpha=_ptr(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt),
+                           state=_ptr(est_state))
+        N.check(N.need_deployed().quad_deploy_obs_rows(self._h, C.byref(est), _ptr(state12), _ptr(target3),
+                                                       _ptr(timestamps), _ptr(rows), n, _ptr(out), _ptr(vel_est),
+                                                       self._stream()), "quad_deploy_obs_rows")
+        return out
+
     # ------------------------------------------------------------------------------------
     _FIELDS = (("qpos", 11, np.float32), ("qvel", 10, np.float32), ("voltage", 1, np.float32),
                ("target", 3, np.float32), ("rate_int", 3, np.float32),

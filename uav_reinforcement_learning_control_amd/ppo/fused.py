@@ -195,12 +195,18 @@ class FusedPolicy:
         _need(cursor, (4,), torch.int32, self.device, "cursor")
         self._launch_post(epilogue, cursor)
 
-    def rollout(self, env, *, obs_copy, actions, log_prob, value, episode_starts, rewards, last_obs,
-                last_start, ep_ret, ep_len, stats, t0: int, steps: int, seed: int, gamma: float,
-                deterministic: bool = False) -> None:
+    def rollout(self, env, **rollout) -> None:
         """quad_rollout: `steps` whole rollout steps (policy + env step + bootstrap + statistics)
         of `env` (a QuadVecEnv: hover/trajectory, no wrapper or RateControlWrapper, auto-reset) in
-        one launch; step t = t0 + s writes row t % rows of the [rows, N, ...] buffers."""
+        one launch; step t = t0 + s writes row t % rows of the [rows, N, ...] buffers. Keyword arguments: obs_copy,
+        actions, log_prob, value, episode_starts, rewards, last_obs, last_start, ep_ret, ep_len, stats, t0, steps,
+        seed, gamma, deterministic = False."""
+        self._rollout_with(self._launch_rollout, env, **rollout)
+
+    def _rollout_with(self, launch, env, *, obs_copy, actions, log_prob, value, episode_starts, rewards, last_obs,
+                      last_start, ep_ret, ep_len, stats, t0: int, steps: int, seed: int, gamma: float,
+                      deterministic: bool = False) -> None:
+        """rollout's checks and descriptor, handed to launch(env, QuadRollout)."""
         n, dev, f32 = env.num_envs, self.device, torch.float32
         rows = rewards.shape[0]
         for t, shp, name in ((obs_copy, (rows, n, 12), "obs_copy"), (actions, (rows, n, 4), "actions"),
@@ -218,7 +224,7 @@ class FusedPolicy:
                           rows=int(rows), t0=int(t0), steps=int(steps),
                           deterministic=int(bool(deterministic)), seed=int(seed) & (2**64 - 1),
                           gamma=float(gamma))
-        self._launch_rollout(env, r)
+        launch(env, r)
 
     def episode(self, env, *, max_steps: Optional[int] = None, obs_mode="env", alpha=None, alpha_all: float = 0.8,
                 max_dt: float = 0.1, trace_envs: int = 0, est_state: Optional[torch.Tensor] = None) -> dict:
@@ -388,6 +394,24 @@ class FusedActorCritic(FusedPolicy):
     def _launch_rollout(self, env, r: N.QuadRollout) -> None:
         N.check(N.lib().quad_actor_rollout(env._h, C.byref(self.arch), _p(self.packed), C.byref(r),
                                            current_stream(self.device)), "quad_actor_rollout")
+
+    def rollout_deployed(self, env, *, est_state: torch.Tensor, alpha=None, alpha_all: float = 0.8,
+                         max_dt: float = 0.1, **rollout) -> None:
+        """quad_actor_rollout_deployed: rollout() with the policy acting on the deployed observation (the velocity
+        of the reference node's estimator, the row clipped to [-1, 1]). est_state float64 [8, N] holds the
+        envs' estimators, read and written (start it with env.deploy_obs_rows after env.reset()); alpha float64 [N]
+        or None for alpha_all; last_obs is the deployed row in hand. The other arguments are rollout()'s."""
+        n, dev = env.num_envs, self.device
+        _need(est_state, (N.EST_NSTATE, n), torch.float64, dev, "est_state")
+        if alpha is not None:
+            _need(alpha, (n,), torch.float64, dev, "alpha")
+        est = N.QuadVelEst(alpha=_p(alpha), alpha_all=float(alpha_all), max_dt=float(max_dt), state=_p(est_state))
+        L = N.need_deployed()
+        launch = lambda e, r: N.check(L.quad_actor_rollout_deployed(e._h, C.byref(self.arch), _p(self.packed), C.byref(r),
+                                                                    C.byref(est), float(e.dt),
+                                                                    current_stream(self.device)),
+                                      "quad_actor_rollout_deployed")
+        self._rollout_with(launch, env, **rollout)
 
     def episode(self, *a, **k):
         raise NotImplementedError("FusedActorCritic collects rollouts; episodes fly on FusedActor (fused_actor_for)")

@@ -37,6 +37,14 @@ def _p(t: torch.Tensor):
     return t.data_ptr()
 
 
+def refuse_deployed(who: str, k: int, cfg: PPOConfig) -> None:
+    """The quad_pop_* launches collect the env's own observation: a member asking for the deployed one
+    is refused by name, before anything is built."""
+    if getattr(cfg, "obs_mode", "env") != "env":
+        raise ValueError(f"{who}: member {k} has obs_mode={cfg.obs_mode!r}; the population launches collect the env "
+                         'observation only (train it alone: PPO with obs_mode="deployed")')
+
+
 class PopulationPPO:
     """P stand-alone `PPO` learners driven by population launches.
 
@@ -52,7 +60,8 @@ class PopulationPPO:
             raise ValueError("PopulationPPO needs at least one (PPOConfig, seed)")
         c0 = members[0][0]
         total = c0.n_steps * int(n_envs)
-        for cfg, _ in members:
+        for k, (cfg, _) in enumerate(members):
+            refuse_deployed(type(self).__name__, k, cfg)
             self._check_config(cfg, c0)
             if not (cfg.fused_policy and cfg.fused_rollout and cfg.fused_update):
                 raise ValueError("PopulationPPO needs fused_policy, fused_rollout and fused_update")
@@ -377,6 +386,8 @@ def population_for(members: Sequence[Tuple[PPOConfig, int]], n_envs: int = 8, en
     members = list(members)
     if len(members) < 1:
         raise ValueError("population_for needs at least one (PPOConfig, seed)")
+    for k, (cfg, _) in enumerate(members):
+        refuse_deployed("population_for", k, cfg)
     keys = {_arch_key(cfg) for cfg, _ in members}
     if len(keys) != 1:
         raise ValueError(f"members must share net_arch and activation, got {sorted(keys)}")

@@ -20,6 +20,8 @@ gradients are averaged with ONE all_reduce over a single flat fp32 bucket (RCCL 
 """
 from __future__ import annotations
 
+import functools
+import math
 import time
 from dataclasses import dataclass, field
 from typing import Callable, Optional
@@ -65,6 +67,48 @@ class PPOConfig:
     # (fused.FusedActorCritic); one launch per chunk with fused_rollout, else two launches per step. Opt-in,
     # independent of fused_update_arch; like the 128-128 ReLU net's kernels it needs fused_policy (False: torch)
     fused_rollout_arch: bool = False
+    # "deployed": collect the rollouts on the observation the reference's ROS2 node hands the policy (the velocity
+    # of its low-pass on finite differences of the position, coefficient velocity_alpha, samples further apart than
+    # est_max_dt restart it; the row clipped to [-1, 1]) in quad_actor_rollout_deployed launches, for every net of
+    # the general family. "env": the env's own observation, every path as it was
+    obs_mode: str = "env"
+    velocity_alpha: float = 0.8
+    est_max_dt: float = 0.1
+
+
+OBS_MODES = ("env", "deployed")
+
+
+def check_obs_mode(env, cfg: PPOConfig, policy=None) -> None:
+    """ValueError unless cfg.obs_mode is known and, when "deployed", the one path that collects it exists for
+    (env, cfg): quad_actor_rollout_deployed through a FusedActorCritic. Touches no device."""
+    if cfg.obs_mode not in OBS_MODES:
+        raise ValueError(f"obs_mode must be one of {OBS_MODES}, got {cfg.obs_mode!r}")
+    if cfg.obs_mode == "env":
+        return
+    who = 'obs_mode="deployed"'
+    if torch.device(env.device).type != "cuda":
+        raise ValueError(f"{who} collects on a ROCm GPU (quad_actor_rollout_deployed), got device {env.device}")
+    ecfg = getattr(env, "cfg", None)
+    if getattr(env, "brax", False) or (ecfg is not None and ecfg.env_kind not in (N.ENV_HOVER, N.ENV_TRAJ)):
+        raise ValueError(f"{who} is the hover / trajectory envs' ROS2 observation; the brax kinds have none")
+    if int(getattr(env, "obs_dim", 12)) != 12:
+        raise ValueError(f"{who} builds the 12-D observation, got a {getattr(env, 'obs_dim', 12)}-D env")
+    if ecfg is None or ecfg.auto_reset != 1:
+        raise ValueError(f"{who} needs an env that resets itself (auto_reset): the launch steps it through resets")
+    if not (cfg.fused_policy and cfg.fused_rollout):
+        raise ValueError(f"{who} needs fused_policy and fused_rollout: there is no per-step deployed path, only the "
+                         "one-launch rollout")
+    if policy is not None:
+        FusedActorCritic.arch_of(policy)  # ValueError naming the family
+    else:
+        h = tuple(int(x) for x in cfg.net_arch)
+        if not (len(h) == 2 and h[0] % 32 == 0 and 32 <= h[0] <= N.ACTOR_MAX_H1 and h[1] in N.ACTOR_H2
+                and cfg.activation in N.ACTFNS):
+            raise ValueError(f"{who} collects 12-H1-H2-(4|1) nets (H1 a multiple of 32 up to {N.ACTOR_MAX_H1}, H2 in "
+                             f"{N.ACTOR_H2}, relu / tanh), got {h} {cfg.activation!r}")
+    if not (math.isfinite(cfg.velocity_alpha) and cfg.est_max_dt > 0):
+        raise ValueError(f"{who}: velocity_alpha must be finite and est_max_dt > 0")
 
 
 # quad_ppo_adv_stats_epoch's grid y limit is 65,535; its [n, 512] float64 output is 4 KB per
@@ -244,6 +288,8 @@ class PPO:
         self.env = env
         self.cfg = config or PPOConfig()
         self.device = env.device
+        check_obs_mode(env, self.cfg, policy)  # before anything is built
+        self._deployed = self.cfg.obs_mode == "deployed"
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         torch.manual_seed(seed)  # identical policy init on every rank
         self.obs_dim = int(getattr(env, "obs_dim", 12))
@@ -290,8 +336,13 @@ class PPO:
         # fused_update_arch -- and its evaluations fly on the general actor: fused.fused_actor_for)
         fusable = (self.obs_dim == 12 and tuple(self.cfg.net_arch) == (128, 128) and self.cfg.activation == "relu"
                    and getattr(self.policy, "activation", "relu") == "relu")
-        self._fp = FusedPolicy(self.policy) if self.cfg.fused_policy and fusable else None
-        if self.cfg.fused_rollout_arch and not fusable:
+        self._fp = FusedPolicy(self.policy) if self.cfg.fused_policy and fusable and not self._deployed else None
+        if self._deployed:
+            # every net of the family, (128, 128) ReLU included, collects on the general kernel: k_rollout has no
+            # deployed form. That net's update stays FusedLearner's: the same module, the same 12-D rows
+            self._fp = FusedActorCritic(self.policy)
+            self.est_state = torch.zeros(N.EST_NSTATE, n, dtype=torch.float64, device=self.device)
+        elif self.cfg.fused_rollout_arch and not fusable:
             if self.obs_dim != 12:
                 raise ValueError(f"fused_rollout_arch collects 12-D observations, got {self.obs_dim}")
             FusedActorCritic.arch_of(self.policy)  # ValueError naming the family
@@ -394,6 +445,8 @@ class PPO:
             self._fp.pack()  # the kernels' copy of the weights the last update produced
         if not self._started:
             self.last_obs.copy_(env.reset())
+            if self._deployed:
+                self._start_estimators()
             self.last_start.fill_(1.0)
             self._started = True
             if use_graph and not self._one_launch:
@@ -422,6 +475,19 @@ class PPO:
             cfg.gamma, cfg.gae_lambda, self.buf_adv, self.buf_ret)
         return self._rollout_stats(t0)
 
+    def _start_estimators(self) -> None:
+        """After env.reset(): every env's estimator emptied and given the reset state's position at the reset step
+        count, and the deployed row of that state (velocity 0) into last_obs -- what the launch does at a reset."""
+        env = self.env
+        _, s12 = env.observe(state=True)
+        st = env.get_state()
+        dev = self.device
+        target = torch.as_tensor(st["target"], dtype=torch.float32, device=dev).contiguous()
+        ts = torch.as_tensor(st["step_count"], device=dev).to(torch.float64) * float(env.dt)
+        env.deploy_obs_rows(s12, target, ts, self.est_state, rows=torch.full((env.num_envs,), 2, dtype=torch.uint8,
+                                                                             device=dev),
+                            alpha_all=self.cfg.velocity_alpha, max_dt=self.cfg.est_max_dt, out=self.last_obs)
+
     @torch.no_grad()
     def _collect_one_launch(self) -> RolloutStats:
         """collect_rollouts as quad_rollout launches (rollout_chunk steps each): same buffers, same
@@ -433,11 +499,15 @@ class PPO:
         s = 0
         while s < cfg.n_steps:
             k = min(chunk, cfg.n_steps - s)
-            self._fp.rollout(env, obs_copy=self.buf_obs, actions=self.buf_act, log_prob=self.buf_logp,
-                             value=self.buf_val, episode_starts=self.buf_start, rewards=self.buf_rew,
-                             last_obs=self.last_obs, last_start=self.last_start, ep_ret=self.ep_ret,
-                             ep_len=self.ep_len, stats=self._slots, t0=self._t_host + s, steps=k,
-                             seed=self._noise_seed, gamma=cfg.gamma)
+            roll = self._fp.rollout
+            if self._deployed:
+                roll = functools.partial(self._fp.rollout_deployed, est_state=self.est_state,
+                                         alpha_all=cfg.velocity_alpha, max_dt=cfg.est_max_dt)
+            roll(env, obs_copy=self.buf_obs, actions=self.buf_act, log_prob=self.buf_logp,
+                 value=self.buf_val, episode_starts=self.buf_start, rewards=self.buf_rew,
+                 last_obs=self.last_obs, last_start=self.last_start, ep_ret=self.ep_ret,
+                 ep_len=self.ep_len, stats=self._slots, t0=self._t_host + s, steps=k,
+                 seed=self._noise_seed, gamma=cfg.gamma)
             s += k
         self._t_host += cfg.n_steps
         self._done_stats.copy_(self._slots.sum(0))
@@ -590,8 +660,11 @@ class PPO:
         """What a resumed run needs: policy, optimizer (Adam moments, step counts), the timestep
         count and the rollout's action-noise counter (so resumed rollouts draw fresh noise)."""
         noise = self._t_host if self._one_launch else int(self._cursor[0].item())
-        return {"policy": self.policy.state_dict(), "optimizer": self.opt.state_dict(),
-                "num_timesteps": self.num_timesteps, "noise_step": noise}
+        sd = {"policy": self.policy.state_dict(), "optimizer": self.opt.state_dict(),
+              "num_timesteps": self.num_timesteps, "noise_step": noise}
+        if self._deployed:  # the envs' velocity estimators (obs_mode="deployed")
+            sd["est_state"] = self.est_state.clone()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         """Restore state_dict() (parameters are copied in place, so the gradient bucket binding
@@ -604,6 +677,8 @@ class PPO:
                 st["step"] = st["step"].to(device=self.device, dtype=torch.float32)
         self._epoch_graph = None  # its launches hold the replaced Adam state tensors
         self.num_timesteps = int(sd["num_timesteps"])
+        if self._deployed and "est_state" in sd:
+            self.est_state.copy_(sd["est_state"])
         ns = int(sd.get("noise_step", 0))
         self._t_host = ns
         # the two-launch path keys its noise on the device cursor, whose step count also selects the

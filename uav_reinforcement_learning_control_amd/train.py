@@ -55,6 +55,13 @@ def parse(argv=None):
                          "the torch per-step path. Off by default; independent of --fused-arch-update; a (net,\n"
                          "activation, num_envs) the fused form did not win in profiles/arch_rollout\n"
                          "(ARCH_ROLLOUT_KEEP_TORCH) keeps the torch rollout")
+    ap.add_argument("--deployed", action="store_true",
+                    help="train on the observation the reference's ROS2 node hands the policy (velocity from its\n"
+                         "low-pass on position differences, the row clipped to [-1, 1]) instead of the env's own:\n"
+                         "quad_actor_rollout_deployed, one launch per chunk, for every net of the general family\n"
+                         "(128 128 relu included); the in-training evaluations fly on the same observation")
+    ap.add_argument("--velocity-alpha", type=float, default=0.8,
+                    help="the estimator's low-pass coefficient under --deployed (policy_node.py's default 0.8)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--log-dir", default="./logs")
     ap.add_argument("--model-dir", default="./models_trained")
@@ -105,6 +112,8 @@ def run_config(a, env, cfg, model, world, stamp) -> dict:
         "backend": "uav_reinforcement_learning_control_amd (MI355X kernels)",
         **({"fused_arch_update": True} if cfg.fused_update_arch else {}),
         **({"fused_arch_rollout": True} if isinstance(model._fp, FusedActorCritic) else {}),  # the flag, in effect
+        "obs_mode": cfg.obs_mode,
+        "velocity_alpha": cfg.velocity_alpha,  # read in the deployed mode only
     }
 
 
@@ -155,8 +164,10 @@ class EvalCallback:
         while self.next <= self.model.num_timesteps:
             self.next += self.freq
         from .evaluate import evaluate_episodes
+        dep = self.cfg.obs_mode == "deployed"  # the evaluations fly on the observation the rollouts collect
         r = evaluate_episodes(self.model.policy, num_episodes=self.n, wrapper=self.wrapper, env=self.env_kind,
-                              device=self.device, seed=self.seed + 7919 * (len(self.timesteps) + 1))
+                              device=self.device, seed=self.seed + 7919 * (len(self.timesteps) + 1),
+                              **(dict(obs_mode="deployed", velocity_alpha=self.cfg.velocity_alpha) if dep else {}))
         self.timesteps.append(self.model.num_timesteps)
         self.results.append(r["rewards"])
         self.lengths.append(r["lengths"])
@@ -198,8 +209,12 @@ def main(argv=None):
                   f"{a.num_envs} envs (ARCH_ROLLOUT_KEEP_TORCH: the fused form did not win that row)", flush=True)
     cfg = PPOConfig(learning_rate=a.learning_rate, n_steps=a.n_steps, n_epochs=a.n_epochs,
                     n_minibatches=a.n_minibatches, net_arch=tuple(a.net_arch), activation=a.activation,
-                    fused_update_arch=arch_update, fused_rollout_arch=arch_rollout)
+                    fused_update_arch=arch_update, fused_rollout_arch=arch_rollout,
+                    obs_mode="deployed" if a.deployed else "env", velocity_alpha=a.velocity_alpha)
     model = PPO(env, cfg, seed=a.seed)
+    if a.deployed and rank == 0:
+        print(f"observation: deployed (velocity_alpha {cfg.velocity_alpha}; FusedActorCritic: "
+              "quad_actor_rollout_deployed, one launch per chunk)", flush=True)
     if arch_rollout and rank == 0:
         if isinstance(model._fp, FusedActorCritic):
             print(f"rollout: fused rollout for net {tuple(a.net_arch)} {a.activation} (FusedActorCritic: "
