@@ -951,9 +951,9 @@ int quad_actor_rollout(QuadHandle* h, const QuadActorArch* arch, const float* pa
  * quad_actor_critic_post at the end.
  * QUAD_EINVAL with nothing launched and nothing written: everything quad_actor_rollout refuses; a NULL est, a NULL
  * est->state or one that is not 8-byte aligned; QuadVelEst's own checks (alpha_all, max_dt); est_dt <= 0 or not
- * finite. quad_rollout (the 128-128 ReLU kernel, at its register limit) and the quad_pop_* forms have no deployed
- * form: the family's (128, 128) ReLU instance collects that net. The added entry points did not change the ABI
- * version. */
+ * finite. quad_rollout (the 128-128 ReLU kernel, at its register limit) has no deployed form: the family's
+ * (128, 128) ReLU instance collects that net. The population form is quad_pop_create_deployed (below). The added
+ * entry points did not change the ABI version. */
 int quad_actor_rollout_deployed(QuadHandle* h, const QuadActorArch* arch, const float* packed, const QuadRollout* r,
                                 const QuadVelEst* est, double est_dt, void* stream);
 
@@ -1068,6 +1068,40 @@ int64_t quad_pop_arch_workspace_bytes(const QuadActorArch* arch, const QuadAdam*
  * the 13 of the arch's module, and a workspace smaller than quad_pop_arch_workspace_bytes. */
 int quad_pop_create_arch(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
                          int32_t normalize_advantage, QuadPop** out);
+
+/* ---- Populations trained on the deployed observation (added within ABI v8 as the entry points above
+ * were, no existing struct changed): quad_pop_create_arch's QuadPop, QuadPopMember and launch calls for P learners of
+ * one QuadActorArch whose rollouts are quad_actor_rollout_deployed's. deploy[m] is member m's estimator -- what
+ * quad_actor_rollout_deployed takes: est.state float64 [8][N] required, read at the entry of a rollout launch and
+ * written at its exit, referenced and not copied; est.alpha [N] or NULL for alpha_all -- and est_dt; members may
+ * differ in alpha_all, in their alpha arrays and in max_dt. On such a population
+ *   quad_pop_pack, quad_pop_value   are the family's (quad_actor_critic_pack / quad_actor_critic_act), as on a
+ *                            quad_pop_create_arch population; packed holds quad_actor_critic_packed_floats(arch)
+ *   quad_pop_rollout         is quad_actor_rollout_deployed(env, arch, packed, rollout with the given t0 / steps,
+ *                            &deploy[m].est, deploy[m].est_dt): rollout.last_obs holds the deployed row in hand
+ *   quad_pop_ppo_grad        is quad_ppo_arch_grad, as on a quad_pop_create_arch population -- except for the
+ *                            (128, 128) ReLU arch: there it is quad_ppo_grad (bf16x3 form) as on a quad_pop_create
+ *                            population, the pairing a single deployed learner of that net has, with the workspace
+ *                            of quad_pop_workspace_bytes
+ *   quad_pop_attach_eval     requires obs_mode == QUAD_OBS_DEPLOYED on every attached run (its estimator arguments
+ *                            as quad_actor_episode takes them) and refuses QUAD_OBS_ENV; on every other population
+ *                            it refuses QUAD_OBS_DEPLOYED, as before
+ *   quad_pop_episode         is quad_actor_episode in deployed mode on the policy half of the member's image
+ * and quad_pop_gae / _permutation / _adv_stats_epoch / _clip_adam / _subset / _detach_eval / _destroy are what they are
+ * above. Launch calls stay free of allocations, copies and synchronization. */
+typedef struct QuadPopDeploy {
+  QuadVelEst est;
+  double est_dt;            /* the timestamp of step count k is k * est_dt (the env's dt) */
+} QuadPopDeploy;            /* one per member */
+/* Device workspace (bytes) one member needs: quad_pop_workspace_bytes(adam, batch) for the (128, 128) ReLU arch,
+ * quad_pop_arch_workspace_bytes(arch, adam, batch) for every other arch of the family. 0 on invalid arguments. */
+int64_t quad_pop_deployed_workspace_bytes(const QuadActorArch* arch, const QuadAdam* adam, int32_t batch);
+/* QUAD_EINVAL (nothing allocated, nothing launched, *out = NULL) for everything quad_pop_create_arch rejects (the
+ * (128, 128) ReLU arch is accepted here; for it also QUADENV_LEARNER=f32, as quad_pop_create), a NULL deploy, and per
+ * member: a NULL est.state or one that is not 8-byte aligned, an est.alpha that is not 8-byte aligned, QuadVelEst's
+ * own checks (alpha_all finite when alpha is NULL, max_dt > 0), est_dt <= 0 or not finite. */
+int quad_pop_create_deployed(const QuadActorArch* arch, const QuadPopMember* members, const QuadPopDeploy* deploy,
+                             int32_t P, int32_t batch, int32_t normalize_advantage, QuadPop** out);
 
 #ifdef __cplusplus
 }

@@ -322,7 +322,16 @@ POP_EXPORTS = ("quad_pop_workspace_bytes", "quad_pop_create", "quad_pop_destroy"
                "quad_pop_detach_eval", "quad_pop_episode")
 # the general family's populations: the same launch calls on a QuadPop of quad_pop_create_arch
 POP_ARCH_EXPORTS = ("quad_pop_arch_workspace_bytes", "quad_pop_create_arch")
-EXPORTS = EXPORTS + POP_EXPORTS + POP_ARCH_EXPORTS
+
+
+class QuadPopDeploy(C.Structure):
+    """One member's estimator in a population trained on the deployed observation (quad_pop_create_deployed)."""
+    _fields_ = [("est", QuadVelEst), ("est_dt", C.c_double)]
+
+
+# populations on the deployed observation (DESIGN 28): the same launch calls on a QuadPop of quad_pop_create_deployed
+POP_DEPLOYED_EXPORTS = ("quad_pop_deployed_workspace_bytes", "quad_pop_create_deployed")
+EXPORTS = EXPORTS + POP_EXPORTS + POP_ARCH_EXPORTS + POP_DEPLOYED_EXPORTS
 
 
 class QuadError(RuntimeError):
@@ -482,6 +491,14 @@ def _declare(L):
     L.quad_pop_arch_workspace_bytes.restype = C.c_int64
     L.quad_pop_create_arch.argtypes = [arch, C.POINTER(QuadPopMember), i32, i32, i32, C.POINTER(vp)]
     L.quad_pop_create_arch.restype = C.c_int
+    # populations on the deployed observation. As with the deployed rollout, a library built before them
+    # still loads; need_deployed_population() is what their callers ask first
+    if hasattr(L, "quad_pop_create_deployed"):
+        L.quad_pop_deployed_workspace_bytes.argtypes = [arch, C.POINTER(QuadAdam), i32]
+        L.quad_pop_deployed_workspace_bytes.restype = C.c_int64
+        L.quad_pop_create_deployed.argtypes = [arch, C.POINTER(QuadPopMember), C.POINTER(QuadPopDeploy), i32, i32, i32,
+                                               C.POINTER(vp)]
+        L.quad_pop_create_deployed.restype = C.c_int
     for n in ("quad_pid_default_gains", "quad_pid_act", "quad_pid_episode", "quad_target_info",
               "quad_ctrl_default_params", "quad_ctrl_act", "quad_ctrl_episode", "quad_deploy_obs",
               "quad_policy_episode", "quad_ctrl_waypoints", "quad_policy_waypoints"):
@@ -514,6 +531,15 @@ def need_deployed():
     if not hasattr(L, "quad_actor_rollout_deployed"):
         raise QuadError(f"{LIB_PATH} was built before the deployed rollout's entry points "
                         "(quad_actor_rollout_deployed); rebuild it")
+    return L
+
+
+def need_deployed_population():
+    """need_deployed(), or QuadError when the library was built before quad_pop_create_deployed."""
+    L = need_deployed()
+    if not hasattr(L, "quad_pop_create_deployed"):
+        raise QuadError(f"{LIB_PATH} was built before the deployed populations' entry points "
+                        "(quad_pop_create_deployed); rebuild it")
     return L
 
 

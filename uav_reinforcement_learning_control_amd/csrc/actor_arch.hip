@@ -9,6 +9,7 @@
 //   k_actor_episode<KIND, CTBR, MODE, MB>, k_actor_waypoints<CTBR, MODE, MB>
 //                                       episode_body<.., NT = 1, EB = 64, ..> (64-env blocks of two one-tile
 //                                       waves), the handle's constant block read from memory (no SPEC form)
+//   k_pop_actor_episode<KIND, CTBR, MODE, MB>  k_actor_episode behind the population's grid dimension
 //
 // This file is compiled once without AA_KIND (every quad_actor_* entry point, the pack kernel, k_actor_act, the
 // launch dispatch) and once per (AA_KIND, AA_MB): AA_KIND = 0 hover / 1 trajectory / 2 hover waypoint laps, AA_MB =
@@ -35,7 +36,7 @@ hipError_t launch_actor_inst(const KConsts<float>* kc, const KParams& kp, bool c
                              const float* packed, const EpisodeArgs& a, const QuadWaypointRun* wr, hipStream_t s);
 template <int AKIND, int MB>  // (the episode kinds, 0 and 1)
 hipError_t launch_pop_actor_inst(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count,
-                                 int n, bool ctbr, const ActorNet& net, hipStream_t s);
+                                 int n, bool ctbr, int obs_mode, const ActorNet& net, hipStream_t s);
 
 #if defined(AA_KIND)
 namespace {
@@ -77,9 +78,10 @@ __global__ __launch_bounds__(128) void k_actor_episode(const KConsts<float>* __r
   episode_body<KIND, CTBR, 1, MODE, 64, false>(*kc, p, fw, a, nullptr);
 }
 
-// The population form (quad_pop_episode of a population of this family): env-observation mode; the member's entry is
-// read through pop::const_entry (population.h), its image the policy half of the member's actor-critic image
-template <int KIND, bool CTBR, int MB>
+// The population form (quad_pop_episode of a population of this family), in k_actor_episode's two observation modes
+// (QUAD_OBS_DEPLOYED: a quad_pop_create_deployed population); the member's entry is read through
+// pop::const_entry (population.h), its image the policy half of the member's actor-critic image
+template <int KIND, bool CTBR, int MODE, int MB>
 __global__ __launch_bounds__(128) void k_pop_actor_episode(const KConsts<float>* __restrict__ kc,
                                                            const PopEpisodeEntry* __restrict__ tab,
                                                            const int32_t* __restrict__ active, actor::Net net) {
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(128) void k_pop_actor_episode(const KConsts<float>*
   p.kc = kc;
   const EpisodeArgs a = en.a;
   ArchForward<MB> fw{en.packed, net};
-  episode_body<KIND, CTBR, 1, QUAD_OBS_ENV, 64, false>(*kc, p, fw, a, nullptr);
+  episode_body<KIND, CTBR, 1, MODE, 64, false>(*kc, p, fw, a, nullptr);
 #endif
 }
 #endif
@@ -99,17 +101,21 @@ __global__ __launch_bounds__(128) void k_pop_actor_episode(const KConsts<float>*
 #if AA_KIND != 2
 template <int AKIND, int MB>
 hipError_t launch_pop_actor_inst(const KConsts<float>* kc, const PopEpisodeEntry* tab, const int32_t* active, int count,
-                                 int n, bool ctbr, const ActorNet& net, hipStream_t s) {
+                                 int n, bool ctbr, int obs_mode, const ActorNet& net, hipStream_t s) {
   const actor::Net dn{net.nb1, net.actfn};
   const int bytes = arch::Layout{net.nb1, MB}.lds_bytes();  // <= 64 KB: no opt-in
   return with_bool(ctbr, [&](auto cb) {
-    hipLaunchKernelGGL((k_pop_actor_episode<AKIND, decltype(cb)::value, MB>), dim3((n + 63) / 64, count), dim3(128),
-                       bytes, s, kc, tab, active, dn);
-    return hipGetLastError();
+    return with_bool(obs_mode == QUAD_OBS_DEPLOYED, [&](auto dm) {
+      constexpr bool CB = decltype(cb)::value;
+      constexpr int MD = decltype(dm)::value ? QUAD_OBS_DEPLOYED : QUAD_OBS_ENV;
+      hipLaunchKernelGGL((k_pop_actor_episode<AKIND, CB, MD, MB>), dim3((n + 63) / 64, count), dim3(128), bytes, s, kc,
+                         tab, active, dn);
+      return hipGetLastError();
+    });
   });
 }
 template hipError_t launch_pop_actor_inst<AA_KIND, AA_MB>(const KConsts<float>*, const PopEpisodeEntry*, const int32_t*,
-                                                          int, int, bool, const ActorNet&, hipStream_t);
+                                                          int, int, bool, int, const ActorNet&, hipStream_t);
 #endif
 
 template <int AKIND, int MB>
@@ -182,12 +188,12 @@ int actor_net_of(const QuadActorArch* a, ActorNet* out) { return actor::net_of(a
 // the population form of quad_actor_episode (population.h); `arch` is one quad_pop_create_arch checked
 hipError_t pop::launch_pop_actor_episode(const QuadActorArch& arch, const KConsts<float>* kc, const PopEpisodeEntry* tab,
                                          const int32_t* active, int count, int n, int env_kind, bool ctbr,
-                                         hipStream_t s) {
+                                         int obs_mode, hipStream_t s) {
   const ActorNet net{arch.h1 / 32, arch.h2 / 32, arch.activation};
   return with_mb(net.mb, [&](auto mb) {
     constexpr int MB = decltype(mb)::value;
-    return env_kind == QUAD_ENV_TRAJ ? launch_pop_actor_inst<1, MB>(kc, tab, active, count, n, ctbr, net, s)
-                                     : launch_pop_actor_inst<0, MB>(kc, tab, active, count, n, ctbr, net, s);
+    return env_kind == QUAD_ENV_TRAJ ? launch_pop_actor_inst<1, MB>(kc, tab, active, count, n, ctbr, obs_mode, net, s)
+                                     : launch_pop_actor_inst<0, MB>(kc, tab, active, count, n, ctbr, obs_mode, net, s);
   });
 }
 

@@ -27,6 +27,8 @@
 //                               the population forms (population.h): the bodies of k_ac_head, the pack
 //                               kernel, k_ac_act and k_ac_rollout behind one more grid dimension, the member's
 //                               arguments read from a device table
+//   k_pop_ac_rollout_deployed<KIND, CTBR, MB>  k_ac_rollout_deployed's population form: the member's
+//                               estimator arguments from a second table, pop::EstEntry
 //
 // The sample, the log-prob, the reward row and the forward of either net are one definition each, used by both
 // forms, and this file is built with the episode objects' floating-point flags (-ffp-contract=on, no SLP
@@ -35,8 +37,8 @@
 //
 // Compiled once without AR_KIND (the entry points, k_ac_head / k_ac_act / k_ac_post, the launch dispatch) and once
 // per (AR_KIND, AR_MB): AR_KIND = 0 hover / 1 trajectory, AR_MB = H2 / 32 = 2 / 4 / 8 -- six objects of two
-// kernels each (CTBR or not) that build in parallel, and six more with AR_DEPLOYED: k_ac_rollout_deployed, the body in
-// its deployed-observation mode (quad_actor_rollout_deployed).
+// kernels each (CTBR or not) that build in parallel, and six more with AR_DEPLOYED: k_ac_rollout_deployed and
+// k_pop_ac_rollout_deployed, the body in its deployed-observation mode (quad_actor_rollout_deployed).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -69,6 +71,11 @@ template <int AKIND, int MB>
 hipError_t launch_actor_rollout_deployed_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
                                               const float* packed, const RollArgs& a, const EstArgs& est, double est_dt,
                                               hipStream_t s);
+template <int AKIND, int MB>
+hipError_t launch_pop_actor_rollout_deployed_inst(const KConsts<float>* kc, const pop::RollEntry* tab,
+                                                  const pop::EstEntry* etab, const int32_t* active, int count, int n,
+                                                  bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps,
+                                                  hipStream_t s);
 
 namespace {
 
@@ -365,7 +372,55 @@ __global__ __launch_bounds__(128) void k_ac_rollout_deployed(const KConsts<float
   ac_rollout_body<KIND, CTBR, MB, QUAD_OBS_DEPLOYED>(*kc, p, packed, net, a, est, est_dt);
 }
 
+// The population form (population.h): block (b, k) is block b of member active[k]'s
+// quad_actor_rollout_deployed. The member's rollout entry is k_pop_ac_rollout's, read the same way; its estimator
+// arguments and est_dt come from a table of their own (pop::EstEntry, indexed by member), read through
+// pop::const_entry too: the body reads them once, before its step loop, into the registers the single kernel's
+// arguments reach it in.
+template <int KIND, bool CTBR, int MB>
+__global__ __launch_bounds__(128) void k_pop_ac_rollout_deployed(const KConsts<float>* __restrict__ kc,
+                                                                 const pop::RollEntry* __restrict__ tab,
+                                                                 const pop::EstEntry* __restrict__ etab,
+                                                                 const int32_t* __restrict__ active, actor::Net net,
+                                                                 uint32_t t0, int32_t steps) {
+#if defined(__HIP_DEVICE_COMPILE__)  // (pop::const_entry, population.h)
+  const int32_t m = active[blockIdx.y];
+  const auto& en = pop::const_entry(tab, m);
+  const auto& ee = pop::const_entry(etab, m);
+  KParams p = en.kp;
+  p.kc = kc;
+  RollArgs a = en.a;
+  a.t0 = t0;
+  a.steps = steps;
+  const float* __restrict__ packed = en.packed;
+  const EstArgs est = ee.est;
+  ac_rollout_body<KIND, CTBR, MB, QUAD_OBS_DEPLOYED>(*kc, p, packed, net, a, est, ee.est_dt);
+#endif
+}
+
 }  // namespace
+
+template <int AKIND, int MB>
+hipError_t launch_pop_actor_rollout_deployed_inst(const KConsts<float>* kc, const pop::RollEntry* tab,
+                                                  const pop::EstEntry* etab, const int32_t* active, int count, int n,
+                                                  bool ctbr, const ActorNet& net, uint32_t t0, int32_t steps,
+                                                  hipStream_t s) {
+  const actor::Net dn{net.nb1, net.actfn};
+  constexpr int MAX_BYTES = 2 * arch::Layout{actor::MAX_H1 / 32, MB}.lds_bytes();  // (launch_actor_rollout_inst's rule)
+  const int bytes = 2 * arch::Layout{net.nb1, MB}.lds_bytes();
+  constexpr int KIND = AKIND == 1 ? QUAD_ENV_TRAJ : QUAD_ENV_HOVER;
+  const dim3 grid((n + 63) / 64, count), block(128);
+  return with_bool(ctbr, [&](auto cb) {
+    constexpr bool CB = decltype(cb)::value;
+    if (const hipError_t e = lds_opt_in<&k_pop_ac_rollout_deployed<KIND, CB, MB>>(MAX_BYTES)) return e;
+    return launch_lds<&k_pop_ac_rollout_deployed<KIND, CB, MB>>(grid, block, bytes, s, kc, tab, etab, active, dn, t0,
+                                                                 steps);
+  });
+}
+template hipError_t launch_pop_actor_rollout_deployed_inst<AR_KIND, AR_MB>(const KConsts<float>*, const pop::RollEntry*,
+                                                                           const pop::EstEntry*, const int32_t*, int,
+                                                                           int, bool, const ActorNet&, uint32_t,
+                                                                           int32_t, hipStream_t);
 
 template <int AKIND, int MB>
 hipError_t launch_actor_rollout_deployed_inst(const KConsts<float>* kc, const KParams& kp, bool ctbr, const ActorNet& net,
@@ -771,6 +826,16 @@ hipError_t launch_pop_by_mb(const KConsts<float>* kc, const pop::RollEntry* tab,
   });
 }
 
+template <int AKIND>
+hipError_t launch_pop_deployed_by_mb(const KConsts<float>* kc, const pop::RollEntry* tab, const pop::EstEntry* etab,
+                                     const int32_t* active, int count, int n, bool ctbr, const ActorNet& net, uint32_t t0,
+                                     int32_t steps, hipStream_t s) {
+  return with_mb(net.mb, [&](auto mb) {
+    return launch_pop_actor_rollout_deployed_inst<AKIND, decltype(mb)::value>(kc, tab, etab, active, count, n, ctbr, net,
+                                                                              t0, steps, s);
+  });
+}
+
 }  // namespace
 
 // ---- the population launches of this file's kernels (population.h); `arch` is one quad_pop_create_arch checked
@@ -810,6 +875,15 @@ hipError_t pop::launch_pop_ac_rollout(const QuadActorArch& arch, const KConsts<f
   const ActorNet net{arch.h1 / 32, arch.h2 / 32, arch.activation};
   return env_kind == QUAD_ENV_TRAJ ? launch_pop_by_mb<1>(kc, tab, active, count, n, ctbr, net, t0, steps, s)
                                    : launch_pop_by_mb<0>(kc, tab, active, count, n, ctbr, net, t0, steps, s);
+}
+
+hipError_t pop::launch_pop_ac_rollout_deployed(const QuadActorArch& arch, const KConsts<float>* kc, const RollEntry* tab,
+                                               const EstEntry* etab, const int32_t* active, int count, int n,
+                                               int env_kind, bool ctbr, uint32_t t0, int32_t steps, hipStream_t s) {
+  const ActorNet net{arch.h1 / 32, arch.h2 / 32, arch.activation};
+  return env_kind == QUAD_ENV_TRAJ
+             ? launch_pop_deployed_by_mb<1>(kc, tab, etab, active, count, n, ctbr, net, t0, steps, s)
+             : launch_pop_deployed_by_mb<0>(kc, tab, etab, active, count, n, ctbr, net, t0, steps, s);
 }
 
 }  // namespace quadenv

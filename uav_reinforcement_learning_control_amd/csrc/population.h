@@ -96,8 +96,22 @@ int launch_pop_ac_value(const QuadActorArch& arch, const ValueEntry* tab, const 
 hipError_t launch_pop_ac_rollout(const QuadActorArch& arch, const KConsts<float>* kc, const RollEntry* tab,
                                  const int32_t* active, int count, int n, int env_kind, bool ctbr, uint32_t t0,
                                  int32_t steps, hipStream_t s);
+// obs_mode: QUAD_OBS_ENV, or QUAD_OBS_DEPLOYED for a quad_pop_create_deployed population (every entry's estimator
+// arguments are then read)
 hipError_t launch_pop_actor_episode(const QuadActorArch& arch, const KConsts<float>* kc, const PopEpisodeEntry* tab,
-                                    const int32_t* active, int count, int n, int env_kind, bool ctbr, hipStream_t s);
+                                    const int32_t* active, int count, int n, int env_kind, bool ctbr, int obs_mode,
+                                    hipStream_t s);
+
+// ---- the deployed observation (actor_rollout.hip's AR_DEPLOYED objects): quad_actor_rollout_deployed's
+// estimator arguments, per member, in a table of their own beside the RollEntry table (which every rollout kernel of
+// both families reads, and which keeps its size): members may differ in alpha_all, their alpha arrays and max_dt
+struct EstEntry {
+  EstArgs est;
+  double est_dt;
+};
+hipError_t launch_pop_ac_rollout_deployed(const QuadActorArch& arch, const KConsts<float>* kc, const RollEntry* tab,
+                                          const EstEntry* etab, const int32_t* active, int count, int n, int env_kind,
+                                          bool ctbr, uint32_t t0, int32_t steps, hipStream_t s);
 
 }  // namespace pop
 

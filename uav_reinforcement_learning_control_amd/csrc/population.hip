@@ -6,9 +6,12 @@
 // learner_x3.hip): no allocation, no copy, no synchronization, so it is stream-ordered and graph-capturable.
 // quad_pop_create_arch builds the same tables for members of one arch of the general family; the launch
 // calls then go to that family's population kernels (actor_rollout.hip, actor_arch.hip, learner_arch.hip).
+// quad_pop_create_deployed adds the estimator table of the deployed rollout; its (128, 128) ReLU populations
+// pair the family's actor tables with the 128-128 ReLU learner's, as a single deployed learner of that net does.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -34,8 +37,13 @@ struct QuadPop {
   PackEntry* pack = nullptr;
   ValueEntry* value = nullptr;
   LearnerTables lt;
-  bool general = false;        // a population of the general family (quad_pop_create_arch): arch, ga; lt.r unused
+  bool fam_actor = false;      // pack, rollout, value and episode are the general family's (arch): quad_pop_create_arch
+                               // and quad_pop_create_deployed
+  bool fam_learner = false;    // the gradient is the general learner's (ga; lt.r unused): every arch of those two but
+                               // the deployed (128, 128) ReLU one, whose gradient is quad_ppo_grad's (lt.r)
+  bool deployed = false;       // quad_pop_create_deployed: est, the rollout and the episodes in QUAD_OBS_DEPLOYED mode
   QuadActorArch arch{};
+  EstEntry* est = nullptr;     // the deployed rollout's estimator table, by member
   lrna::Args* ga = nullptr;    // the general learner's gradient table
   std::vector<const float*> packed;  // the members' packed images (quad_pop_attach_eval)
   PopEpisodeEntry* eval = nullptr;   // the evaluation table, once attached
@@ -84,6 +92,7 @@ void release(QuadPop* p) {
   (void)hipFree(p->lt.r);
   (void)hipFree(p->lt.a);
   (void)hipFree(p->ga);
+  (void)hipFree(p->est);
   (void)hipFree(p->eval);
   for (auto& s : p->subsets) (void)hipFree(s.dev);
   delete p;
@@ -136,17 +145,32 @@ bool adam_fits(const QuadAdam& ad, const QuadActorArch& a) {
 // the gradient-norm partials follow the general learner's workspace
 int64_t arch_adam_offset(const QuadActorArch& a, int32_t batch) { return lrna::up16(lrna::layout_of(a.h1, a.h2, batch).bytes); }
 
-// quad_pop_create (arch == NULL: the 128-128 ReLU kernels) and quad_pop_create_arch (the general family's)
-int create(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
-           int32_t normalize_advantage, QuadPop** out) {
-  const std::string fn = arch ? "quad_pop_create_arch" : "quad_pop_create";
+bool is_128_relu(const QuadActorArch& a) { return a.h1 == 128 && a.h2 == 128 && a.activation == QUAD_ACTFN_RELU; }
+
+// quad_actor_rollout_deployed's estimator checks on member i's QuadPopDeploy
+int check_deploy(const std::string& who, const QuadPopDeploy& d) {
+  if (int rc = check_est(&d.est, who.c_str())) return rc;
+  if (!d.est.state) return pfail(who + ": the estimator state block is required");
+  if ((reinterpret_cast<uintptr_t>(d.est.state) | reinterpret_cast<uintptr_t>(d.est.alpha)) & 7u)
+    return pfail(who + ": est.state and est.alpha must be 8-byte aligned");
+  if (!(d.est_dt > 0.0) || !std::isfinite(d.est_dt)) return pfail(who + ": est_dt must be > 0 and finite");
+  return QUAD_OK;
+}
+
+// quad_pop_create (arch == NULL: the 128-128 ReLU kernels), quad_pop_create_arch (the general family's) and
+// quad_pop_create_deployed (fn names it; deploy: its estimators, one per member)
+int create(const char* fn_, const QuadActorArch* arch, const QuadPopMember* members, const QuadPopDeploy* deploy,
+           int32_t P, int32_t batch, int32_t normalize_advantage, QuadPop** out) {
+  const std::string fn = fn_;
+  const bool fam_learner = arch && !(deploy && is_128_relu(*arch));
   if (!members || !out) return pfail(fn + ": members / out is NULL");
   if (P < 1) return pfail(fn + ": P must be >= 1");
   if (P > POP_MAX_MEMBERS) return pfail(fn + ": P must be <= 65535 (the member is a grid y / z coordinate)");
   if (batch < 1 || batch > POP_MAX_BATCH)
     return pfail(fn + ": need 1 <= batch <= 8192 (the separate-block gradient form's limit)");
-  if (!arch && quad_ppo_grad_form() != 1) return pfail(fn + ": only the bf16x3 gradient has a population form");
-  std::vector<lrna::Args> ga(arch ? static_cast<size_t>(P) : 0);
+  if (!fam_learner && quad_ppo_grad_form() != 1) return pfail(fn + ": only the bf16x3 gradient has a population form");
+  std::vector<lrna::Args> ga(fam_learner ? static_cast<size_t>(P) : 0);
+  std::vector<EstEntry> est(deploy ? static_cast<size_t>(P) : 0);
   std::vector<RollEntry> roll(static_cast<size_t>(P));
   std::vector<GaeEntry> gae(static_cast<size_t>(P));
   std::vector<PackEntry> pack(static_cast<size_t>(P));
@@ -188,15 +212,20 @@ int create(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, i
                               m.advantages, m.returns, r.gamma, m.gae_lambda};
     pack[size_t(i)] = PackEntry{m.params, m.packed};
     value[size_t(i)] = ValueEntry{m.packed, r.last_obs, m.scratch_actions, m.last_values};
-    if (arch) {
+    if (deploy) {
+      const QuadPopDeploy& d = deploy[i];
+      if (int rc = check_deploy(fn + ": member " + std::to_string(i), d)) return rc;
+      est[size_t(i)] = EstEntry{EstArgs{d.est.alpha, d.est.alpha_all, d.est.max_dt, d.est.state}, d.est_dt};
+    }
+    if (fam_learner) {
       if (int rc = fill_member(fn.c_str(), m, i, batch, normalize_advantage, arch_adam_offset(*arch, batch), gt.data(),
                                at.data()))
         return rc;
-      if (!adam_fits(m.adam, *arch)) return pfail(who + "the Adam tensor sizes are not the arch's");
       ga[size_t(i)] = lrna::pop_entry(*arch, gt[size_t(i)], m, batch);
     } else if (int rc = fill_learner(m, i, batch, normalize_advantage, gt.data(), rt.data(), at.data())) {
       return rc;
     }
+    if (arch && !adam_fits(m.adam, *arch)) return pfail(who + "the Adam tensor sizes are not the arch's");
     if (m.adam.count != members[0].adam.count ||
         std::memcmp(m.adam.numel, members[0].adam.numel, sizeof(int32_t) * size_t(m.adam.count)) != 0)
       return pfail(who + "Adam tensor sizes differ from member 0's");
@@ -210,7 +239,9 @@ int create(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, i
   p->spec = v0->spec; p->kc = v0->kdev;
   p->nb = lrn::layout_both(batch).nb;
   p->adam_nblocks = at[0].nblocks;
-  p->general = arch != nullptr;
+  p->fam_actor = arch != nullptr;
+  p->fam_learner = fam_learner;
+  p->deployed = deploy != nullptr;
   if (arch) p->arch = *arch;
   for (int32_t i = 0; i < P; i++) p->packed.push_back(members[i].packed);
   DeviceGuard g(p->device);
@@ -219,8 +250,9 @@ int create(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, i
   if (!e) e = upload(&p->pack, pack.data(), pack.size() * sizeof(PackEntry));
   if (!e) e = upload(&p->value, value.data(), value.size() * sizeof(ValueEntry));
   if (!e) e = upload(&p->lt.g, gt.data(), gt.size() * sizeof(lrn::GArgs));
-  if (!e && !arch) e = upload(&p->lt.r, rt.data(), rt.size() * sizeof(lrn::RArgs));
-  if (!e && arch) e = upload(&p->ga, ga.data(), ga.size() * sizeof(lrna::Args));
+  if (!e && !fam_learner) e = upload(&p->lt.r, rt.data(), rt.size() * sizeof(lrn::RArgs));
+  if (!e && fam_learner) e = upload(&p->ga, ga.data(), ga.size() * sizeof(lrna::Args));
+  if (!e && deploy) e = upload(&p->est, est.data(), est.size() * sizeof(EstEntry));
   if (!e) e = upload(&p->lt.a, at.data(), at.size() * sizeof(lrn::AdamArgs));
   if (e) {
     release(p);
@@ -254,7 +286,7 @@ int64_t quad_pop_arch_workspace_bytes(const QuadActorArch* arch, const QuadAdam*
 int quad_pop_create(const QuadPopMember* members, int32_t P, int32_t batch, int32_t normalize_advantage,
                     QuadPop** out) {
   if (out) *out = nullptr;
-  return create(nullptr, members, P, batch, normalize_advantage, out);
+  return create("quad_pop_create", nullptr, members, nullptr, P, batch, normalize_advantage, out);
 }
 
 int quad_pop_create_arch(const QuadActorArch* arch, const QuadPopMember* members, int32_t P, int32_t batch,
@@ -263,7 +295,22 @@ int quad_pop_create_arch(const QuadActorArch* arch, const QuadPopMember* members
   if (!lrna::in_family(arch))
     return pfail("quad_pop_create_arch: the family is h1 a multiple of 32 in [32, 512], h2 in {64, 128, 256}, "
                  "QUAD_ACTFN_RELU or QUAD_ACTFN_TANH");
-  return create(arch, members, P, batch, normalize_advantage, out);
+  return create("quad_pop_create_arch", arch, members, nullptr, P, batch, normalize_advantage, out);
+}
+
+int64_t quad_pop_deployed_workspace_bytes(const QuadActorArch* arch, const QuadAdam* adam, int32_t batch) {
+  if (!lrna::in_family(arch)) return 0;
+  return is_128_relu(*arch) ? quad_pop_workspace_bytes(adam, batch) : quad_pop_arch_workspace_bytes(arch, adam, batch);
+}
+
+int quad_pop_create_deployed(const QuadActorArch* arch, const QuadPopMember* members, const QuadPopDeploy* deploy,
+                             int32_t P, int32_t batch, int32_t normalize_advantage, QuadPop** out) {
+  if (out) *out = nullptr;
+  if (!lrna::in_family(arch))
+    return pfail("quad_pop_create_deployed: the family is h1 a multiple of 32 in [32, 512], h2 in {64, 128, 256}, "
+                 "QUAD_ACTFN_RELU or QUAD_ACTFN_TANH");
+  if (!deploy) return pfail("quad_pop_create_deployed: deploy is NULL");
+  return create("quad_pop_create_deployed", arch, members, deploy, P, batch, normalize_advantage, out);
 }
 
 void quad_pop_destroy(QuadPop* pop) { release(pop); }
@@ -278,7 +325,7 @@ int quad_pop_pack(QuadPop* pop, int32_t subset, void* stream) {
   if (!s) return QUAD_EINVAL;
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return pop->general ? launch_pop_ac_pack(pop->arch, pop->pack, s->dev, s->count, st)
+  return pop->fam_actor ? launch_pop_ac_pack(pop->arch, pop->pack, s->dev, s->count, st)
                       : launch_pop_pack(pop->pack, s->dev, s->count, st);
 }
 
@@ -288,7 +335,10 @@ int quad_pop_rollout(QuadPop* pop, int32_t subset, int32_t t0, int32_t steps, vo
   if (steps < 1 || t0 < 0) return pfail("quad_pop_rollout: steps >= 1, t0 >= 0");
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipError_t e = pop->general
+  if (hipError_t e = pop->deployed
+                         ? launch_pop_ac_rollout_deployed(pop->arch, pop->kc, pop->roll, pop->est, s->dev, s->count,
+                                                          pop->n, pop->env_kind, pop->ctbr, uint32_t(t0), steps, st)
+                     : pop->fam_actor
                          ? launch_pop_ac_rollout(pop->arch, pop->kc, pop->roll, s->dev, s->count, pop->n, pop->env_kind,
                                                  pop->ctbr, uint32_t(t0), steps, st)
                          : launch_pop_rollout(pop->kc, pop->roll, s->dev, s->count, pop->n, pop->env_kind, pop->ctbr,
@@ -302,7 +352,7 @@ int quad_pop_value(QuadPop* pop, int32_t subset, void* stream) {
   if (!s) return QUAD_EINVAL;
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return pop->general ? launch_pop_ac_value(pop->arch, pop->value, s->dev, s->count, pop->n, st)
+  return pop->fam_actor ? launch_pop_ac_value(pop->arch, pop->value, s->dev, s->count, pop->n, st)
                       : launch_pop_value(pop->value, s->dev, s->count, pop->n, st);
 }
 
@@ -338,7 +388,7 @@ int quad_pop_ppo_grad(QuadPop* pop, int32_t subset, int32_t slot, void* stream) 
   if (slot < 0 || slot >= pop->nmb) return pfail("quad_pop_ppo_grad: slot out of range");
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (pop->general) return lrna::launch_pop_grad(pop->arch, pop->batch, pop->ga, s->dev, s->count, slot, st);
+  if (pop->fam_learner) return lrna::launch_pop_grad(pop->arch, pop->batch, pop->ga, s->dev, s->count, slot, st);
   if (int rc = lrn::launch_pop_grad_x3(pop->lt.g, s->dev, s->count, slot, pop->nb, st)) return rc;
   return launch_pop_reduce(pop->lt.r, s->dev, s->count, slot, st);
 }
@@ -361,7 +411,12 @@ int quad_pop_attach_eval(QuadPop* pop, const QuadPopEval* evals) {
     const std::string who = "quad_pop_attach_eval: member " + std::to_string(i) + ": ";
     EpisodeArgs a{};
     if (int rc = episode_args(evals[i].env, pop->packed[size_t(i)], &evals[i].run, &a)) return rc;
-    if (evals[i].run.obs_mode != QUAD_OBS_ENV) return pfail(who + "obs_mode must be QUAD_OBS_ENV");
+    if (pop->deployed) {
+      if (evals[i].run.obs_mode != QUAD_OBS_DEPLOYED)
+        return pfail(who + "obs_mode must be QUAD_OBS_DEPLOYED on a quad_pop_create_deployed population");
+    } else if (evals[i].run.obs_mode != QUAD_OBS_ENV) {
+      return pfail(who + "obs_mode must be QUAD_OBS_ENV");
+    }
     const QuadHandle* v = evals[i].env;
     if (first < 0) { first = i; v0 = v; }
     if (!same_envs(v, v0))
@@ -404,9 +459,10 @@ int quad_pop_episode(QuadPop* pop, int32_t subset, void* stream) {
     if (!pop->eval_ok[size_t(m)]) return pfail("quad_pop_episode: a member of the subset has no evaluation handle attached");
   DeviceGuard g(pop->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipError_t e = pop->general
+  if (hipError_t e = pop->fam_actor
                          ? launch_pop_actor_episode(pop->arch, pop->eval_kc, pop->eval, s->dev, s->count, pop->eval_n,
-                                                    pop->eval_kind, pop->eval_ctbr, st)
+                                                    pop->eval_kind, pop->eval_ctbr,
+                                                    pop->deployed ? QUAD_OBS_DEPLOYED : QUAD_OBS_ENV, st)
                          : launch_pop_policy_episode(pop->eval_kc, pop->eval, s->dev, s->count, pop->eval_n,
                                                      pop->eval_kind, pop->eval_ctbr, pop->eval_spec, st))
     return hfail("quad_pop_episode", e);

@@ -24,6 +24,12 @@ By default net_arch is fixed to "small" ([128, 128]) and activation_fn to "relu"
 activation_fn in {tanh, relu}. A population shares its arch, so the groups are then keyed on it too, and
 ppo.population_for trains (small, relu) groups on PopulationPPO and the other five on ArchPopulationPPO (DESIGN
 section 25). The sampler is random search, not TPE; Optuna is not a dependency, so --storage is accepted and ignored.
+
+--deployed trains and evaluates every trial on the observation the reference's ROS2 node hands the policy (DESIGN
+section 28): the trials get obs_mode="deployed" and --velocity-alpha, the groups train as ppo.deployed_population_for's
+populations, and the in-study evaluations fly deployed at the trial's alpha. --search-alpha also draws the estimator's
+coefficient per trial from {0.0, 0.5, 0.8, 0.95}, after every draw the sampler makes without it (so trial k's other
+parameters are what they are without the flag), and appends a params_velocity_alpha column to the CSV.
 """
 from __future__ import annotations
 
@@ -57,6 +63,8 @@ CSV_COLUMNS = ("number", "value", "datetime_start", "datetime_complete", "durati
                "params_learning_rate", "params_n_epochs", "params_n_steps", "params_net_arch", "user_attrs_gamma",
                "user_attrs_net_arch_name", "state")
 COMPLETE, PRUNED, WAITING = "COMPLETE", "PRUNED", "WAITING"
+VELOCITY_ALPHA_CHOICES = (0.0, 0.5, 0.8, 0.95)   # --search-alpha
+ALPHA_COLUMN = "params_velocity_alpha"            # appended to CSV_COLUMNS under --search-alpha
 
 
 def _log_uniform(rng: random.Random, lo: float, hi: float) -> float:
@@ -109,6 +117,8 @@ class Trial:
     values: Dict[int, float] = field(default_factory=dict)   # evaluation index (1..10) -> mean reward
     start: Optional[_dt.datetime] = None
     end: Optional[_dt.datetime] = None
+    obs_mode: str = "env"           # "deployed" under --deployed
+    velocity_alpha: float = 0.8     # the estimator's coefficient of a deployed trial
 
     @property
     def gamma(self) -> float:
@@ -116,12 +126,24 @@ class Trial:
 
 
 def make_trials(n_trials: int, seed: int, n_envs: int, n_steps_choices: Sequence[int] = N_STEPS_CHOICES,
-                search_arch: bool = False) -> List[Trial]:
+                search_arch: bool = False, deployed: bool = False, velocity_alpha: float = 0.8,
+                search_alpha: bool = False) -> List[Trial]:
+    """deployed: the trials collect and are evaluated on the deployed observation at velocity_alpha. search_alpha: the
+    coefficient is drawn per trial from VELOCITY_ALPHA_CHOICES once every trial's other parameters are drawn -- the rng
+    has then made every draw it makes without the flag, so those parameters do not depend on it -- and is recorded as
+    params["velocity_alpha"]."""
+    if search_alpha and not deployed:
+        raise ValueError("search_alpha draws the deployed observation's coefficient: it needs deployed")
     rng = random.Random(seed)
     out = []
     for k in range(n_trials):
         p = sample_ppo_params(rng, n_steps_choices, search_arch)
         out.append(Trial(k, p, seed=int(seed) * 100_003 + k, batch=clamp_batch_size(p["n_steps"], n_envs, p["batch_size"])))
+    for t in out:
+        if deployed:
+            t.obs_mode, t.velocity_alpha = "deployed", float(velocity_alpha)
+        if search_alpha:
+            t.velocity_alpha = t.params["velocity_alpha"] = rng.choice(VELOCITY_ALPHA_CHOICES)
     return out
 
 
@@ -172,6 +194,11 @@ class MedianPruner:
 def trial_row(t: Trial) -> dict:
     p = t.params
     dur = (t.end - t.start) if t.start and t.end else None
+    extra = {ALPHA_COLUMN: repr(p["velocity_alpha"])} if "velocity_alpha" in p else {}
+    return {**_trial_row(t, p, dur), **extra}
+
+
+def _trial_row(t: Trial, p: dict, dur) -> dict:
     return {"number": t.number, "value": "" if math.isnan(t.value) else repr(float(t.value)),
             "datetime_start": t.start.strftime("%Y-%m-%d %H:%M:%S.%f") if t.start else "",
             "datetime_complete": t.end.strftime("%Y-%m-%d %H:%M:%S.%f") if t.end else "",
@@ -189,9 +216,14 @@ def _hms(d: _dt.timedelta) -> str:
     return f"{s // 3600:02d}:{s % 3600 // 60:02d}:{s % 60:02d}.{d.microseconds:06d}"
 
 
+def csv_columns(trials: Sequence[Trial]) -> tuple:
+    """CSV_COLUMNS, with ALPHA_COLUMN appended when the trials carry a sampled velocity_alpha (--search-alpha)."""
+    return CSV_COLUMNS + ((ALPHA_COLUMN,) if any("velocity_alpha" in t.params for t in trials) else ())
+
+
 def write_csv(path: str, trials: Sequence[Trial]) -> None:
     with open(path, "w", newline="") as f:
-        w = csv.DictWriter(f, fieldnames=CSV_COLUMNS)
+        w = csv.DictWriter(f, fieldnames=csv_columns(trials))
         w.writeheader()
         for t in sorted(trials, key=lambda t: t.number):
             w.writerow(trial_row(t))
@@ -207,6 +239,8 @@ def read_csv(path: str) -> List[dict]:
             for k in ("params_clip_range", "params_ent_coef", "params_gae_lambda", "params_gamma_inv",
                       "params_learning_rate", "user_attrs_gamma"):
                 r[k] = float(r[k])
+            if ALPHA_COLUMN in r:
+                r[ALPHA_COLUMN] = float(r[ALPHA_COLUMN])
             r["value"] = float(r["value"]) if r["value"] != "" else float("nan")
             out.append(r)
     return out
@@ -224,6 +258,8 @@ def format_best(t: Trial) -> str:
              "  Params:"]
     lines += [f"    {k}: {p[k]}" for k in ("learning_rate", "n_steps", "batch_size", "n_epochs", "gamma_inv", "gae_lambda",
                                           "clip_range", "ent_coef", "net_arch", "activation_fn")]
+    if t.obs_mode == "deployed":  # the exported policy expects the node's estimator at this coefficient
+        lines += [f"    velocity_alpha: {t.velocity_alpha}"]
     lines += ["", "  User attrs:", f"    gamma: {t.gamma}", f"    net_arch_name: {p['net_arch']}", "",
               "  Ready-to-use config for train.py:", "  " + "-" * 40, "",
               "    model = PPO(", '        policy="MlpPolicy",', "        env=vec_env,",
@@ -243,7 +279,8 @@ def ppo_config(t: Trial):
     p = t.params
     return PPOConfig(learning_rate=p["learning_rate"], n_steps=p["n_steps"], batch_size=t.batch, n_epochs=p["n_epochs"],
                      gamma=t.gamma, gae_lambda=p["gae_lambda"], clip_range=p["clip_range"], ent_coef=p["ent_coef"],
-                     net_arch=tuple(NET_ARCH[p["net_arch"]]), activation=p["activation_fn"])
+                     net_arch=tuple(NET_ARCH[p["net_arch"]]), activation=p["activation_fn"],
+                     **(dict(obs_mode="deployed", velocity_alpha=t.velocity_alpha) if t.obs_mode == "deployed" else {}))
 
 
 def _non_finite_members(pop, members: Sequence[int]) -> List[int]:
@@ -268,7 +305,9 @@ def save_best(pop, m: int, t: Trial, out_dir: str, n_envs: int, n_timesteps: int
                    "gae_lambda": t.params["gae_lambda"], "clip_range": t.params["clip_range"],
                    "ent_coef": t.params["ent_coef"], "net_arch": NET_ARCH[t.params["net_arch"]],
                    "activation_fn": ACTIVATION_CLASS[t.params["activation_fn"]]},
-           "backend": f"uav_reinforcement_learning_control_amd (MI355X kernels, {type(pop).__name__})"}
+           "backend": f"uav_reinforcement_learning_control_amd (MI355X kernels, {type(pop).__name__})",
+           # as train --deployed records them: what the exported policy expects of the node's estimator
+           **({"obs_mode": t.obs_mode, "velocity_alpha": t.velocity_alpha} if t.obs_mode == "deployed" else {})}
     with open(os.path.join(out_dir, "config.json"), "w") as f:
         json.dump(cfg, f, indent=2)
     return path
@@ -278,9 +317,10 @@ def run_population(group: Sequence[Trial], finished: List[Trial], pruner: Median
                    device="cuda:0", save_dir: Optional[str] = None, best_so_far: float = -math.inf, log=print) -> float:
     """Train one group as a population of its arch (ppo.population_for) over the evaluation protocol; fills the trials' values / state / value and
     appends them to `finished` as they end. Returns the best completed value seen (for --save-best)."""
-    from .ppo.population import population_for
+    from .ppo.population import deployed_population_for, population_for
     points = [(k + 1) * (n_timesteps // N_EVALUATIONS) for k in range(N_EVALUATIONS)]
-    pop = population_for([(ppo_config(t), t.seed) for t in group], n_envs=n_envs, env="hover", wrapper=WRAPPER,
+    make = deployed_population_for if group[0].obs_mode == "deployed" else population_for
+    pop = make([(ppo_config(t), t.seed) for t in group], n_envs=n_envs, env="hover", wrapper=WRAPPER,
                          device=device)
     now = _dt.datetime.now
     for t in group:
@@ -332,7 +372,9 @@ def run_population(group: Sequence[Trial], finished: List[Trial], pruner: Median
 
 
 def run_study(a, n_steps_choices: Sequence[int] = N_STEPS_CHOICES, log=print) -> List[Trial]:
-    trials = make_trials(a.n_trials, a.seed, a.n_envs, n_steps_choices, getattr(a, "search_arch", False))
+    trials = make_trials(a.n_trials, a.seed, a.n_envs, n_steps_choices, getattr(a, "search_arch", False),
+                         deployed=getattr(a, "deployed", False), velocity_alpha=getattr(a, "velocity_alpha", 0.8),
+                         search_alpha=getattr(a, "search_alpha", False))
     groups = group_trials(trials, a.n_jobs)
     if getattr(a, "search_arch", False):  # six arch combinations make the populations about six times thinner
         log(population_sizes(groups))
@@ -367,17 +409,34 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--search-arch", action="store_true",
                     help="Also sample net_arch in {small, medium, large} and activation_fn in {tanh, relu}, the "
                          "reference's whole space; a population then shares its arch too, so populations get thinner")
+    ap.add_argument("--deployed", action="store_true",
+                    help="Train and evaluate every trial on the observation the ROS2 node hands the policy (the "
+                         "estimator's velocity, the clipped row): deployed populations, one launch per step for all")
+    ap.add_argument("--velocity-alpha", type=float, default=0.8,
+                    help="The estimator's low-pass coefficient under --deployed (policy_node.py's default 0.8)")
+    ap.add_argument("--search-alpha", action="store_true",
+                    help="Under --deployed: also draw velocity_alpha per trial from {0.0, 0.5, 0.8, 0.95}")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.search_alpha and not a.deployed:
+        ap.error("--search-alpha needs --deployed")
+    return a
+
+
 def main(argv=None, n_steps_choices: Sequence[int] = N_STEPS_CHOICES) -> int:
-    a = build_parser().parse_args(argv)
+    a = parse_args(argv)
     if a.storage:
         print(f"note: --storage {a.storage} is ignored (no Optuna here; results go to the CSV)")
     print(f"Starting study '{a.study_name}'")
     print(f"  Wrapper  : {WRAPPER}\n  Trials    : {a.n_trials}\n  Population: up to {a.n_jobs}")
     print(f"  Timeout   : {f'{a.timeout}s' if a.timeout else 'none'}\n  Steps/trial: {a.n_timesteps}\n"
           f"  Envs/trial : {a.n_envs}\n")
+    if a.deployed:
+        print(f"  Observation: deployed (velocity_alpha {'sampled per trial' if a.search_alpha else a.velocity_alpha})\n")
     t0 = time.perf_counter()
     finished = run_study(a, n_steps_choices)
     print(f"\nFinished trials: {len(finished)} in {time.perf_counter() - t0:.1f} s")

@@ -61,7 +61,7 @@ class PopulationPPO:
         c0 = members[0][0]
         total = c0.n_steps * int(n_envs)
         for k, (cfg, _) in enumerate(members):
-            refuse_deployed(type(self).__name__, k, cfg)
+            self._check_obs_mode(k, cfg)
             self._check_config(cfg, c0)
             if not (cfg.fused_policy and cfg.fused_rollout and cfg.fused_update):
                 raise ValueError("PopulationPPO needs fused_policy, fused_rollout and fused_update")
@@ -123,6 +123,24 @@ class PopulationPPO:
     # ---- what a kernel family's population differs in (ArchPopulationPPO overrides these) ----------------
     _policy_class, _learner_class = FusedPolicy, FusedLearner
     _block_envs = 256  # envs per rollout block: block b adds its episode statistics into slot b
+
+    def _check_obs_mode(self, k: int, cfg: PPOConfig) -> None:
+        refuse_deployed(type(self).__name__, k, cfg)
+
+    def _start_member(self, m: PPO) -> None:
+        """What PPO.collect_rollouts does before a member's first rollout."""
+        m.last_obs.copy_(m.env.reset())
+        m.last_start.fill_(1.0)
+        m._started = True
+
+    def _eval_run(self, i: int, e: QuadVecEnv, res: dict, verr: torch.Tensor) -> N.QuadPolicyRun:
+        """Member i's QuadPolicyRun for evaluate(): its rows of the metric tensors, the env's own observation."""
+        return N.QuadPolicyRun(obs_mode=N.OBS_ENV, max_steps=int(e.max_episode_steps), trace_envs=0,
+                               est=N.QuadVelEst(alpha=None, alpha_all=0.8, max_dt=0.1, state=None),
+                               est_dt=float(e.dt), trace_actions=None, trace_state12=None, trace_obs=None,
+                               trace_vel_est=None,
+                               metrics=N.QuadPidMetrics(**{k: res[k][i].data_ptr() for k, _ in N.PID_METRIC_FIELDS}),
+                               vel_err_sq=verr[i].data_ptr())
 
     def _check_config(self, cfg: PPOConfig, c0: PPOConfig) -> None:
         if tuple(cfg.net_arch) != (128, 128) or cfg.activation != "relu":
@@ -208,9 +226,7 @@ class PopulationPPO:
         N.check(L.quad_pop_pack(h, sid, st), "quad_pop_pack")
         if not self._started:
             for m in self.members:
-                m.last_obs.copy_(m.env.reset())
-                m.last_start.fill_(1.0)
-                m._started = True
+                self._start_member(m)
             self._started = True
         torch._foreach_zero_([self.members[i]._slots for i in act])
         T = self.n_steps
@@ -299,13 +315,7 @@ class PopulationPPO:
         for i, e in envs.items():
             e.reset()
             arr[i].env = e._h.value
-            arr[i].run = N.QuadPolicyRun(obs_mode=N.OBS_ENV, max_steps=int(e.max_episode_steps), trace_envs=0,
-                                         est=N.QuadVelEst(alpha=None, alpha_all=0.8, max_dt=0.1, state=None),
-                                         est_dt=float(e.dt), trace_actions=None, trace_state12=None, trace_obs=None,
-                                         trace_vel_est=None,
-                                         metrics=N.QuadPidMetrics(**{k: res[k][i].data_ptr()
-                                                                     for k, _ in N.PID_METRIC_FIELDS}),
-                                         vel_err_sq=verr[i].data_ptr())
+            arr[i].run = self._eval_run(i, e, res, verr)
         try:
             sid = self._subset(act)
             N.check(L.quad_pop_pack(h, sid, st), "quad_pop_pack")
@@ -404,3 +414,130 @@ def population_for(members: Sequence[Tuple[PPOConfig, int]], n_envs: int = 8, en
                          f"{batch} (it did not beat the path it would replace)")
     return ArchPopulationPPO([(replace(cfg, fused_rollout_arch=True, fused_update_arch=True), seed)
                               for cfg, seed in members], **kw)
+
+
+def refuse_env_mode(who: str, k: int, cfg: PPOConfig) -> None:
+    """refuse_deployed's mirror image: the deployed population's rollout launch builds the deployed observation for
+    every member, so a member asking for the env's own is refused by index, before anything is built."""
+    if getattr(cfg, "obs_mode", "env") != "deployed":
+        raise ValueError(f"{who}: member {k} has obs_mode={getattr(cfg, 'obs_mode', 'env')!r}; every member of a "
+                         'deployed population collects the deployed observation (obs_mode="deployed"; an env-mode '
+                         "member trains on population_for's classes)")
+
+
+def _in_family(hidden: tuple, act: str) -> bool:
+    return (len(hidden) == 2 and hidden[0] % 32 == 0 and 32 <= hidden[0] <= N.ACTOR_MAX_H1 and hidden[1] in N.ACTOR_H2
+            and act in N.ACTFNS)
+
+
+class DeployedPopulationPPO(ArchPopulationPPO):
+    """`ArchPopulationPPO` for members with obs_mode="deployed" (DESIGN section 28): P stand-alone `PPO` learners that
+    collect on the observation the ROS2 node hands the policy, driven by quad_pop_create_deployed's launches -- the
+    rollout is quad_actor_rollout_deployed behind the member dimension, the evaluations fly quad_actor_episode in
+    deployed mode. Members share the arch and the shapes as in the other populations and may differ in
+    velocity_alpha and est_max_dt; each member's est_state is referenced by the library's table, not copied, and
+    started as the stand-alone `PPO` starts it. Every arch of the family trains here, the (128, 128) relu net
+    included: as in a stand-alone deployed `PPO` it collects on the family's kernels and updates on `FusedLearner`.
+    Member m is bit-identical to `PPO(env, cfg, seed)` (tests/test_gpu_deployed_population.py)."""
+
+    def __init__(self, members: Sequence[Tuple[PPOConfig, int]], *args, **kw):
+        members = list(members)
+        if members and _arch_key(members[0][0]) == ((128, 128), "relu"):
+            self._learner_class = FusedLearner  # the pairing of PPO(obs_mode="deployed") for that net
+        self._eval_alpha: Optional[float] = None
+        super().__init__(members, *args, **kw)
+
+    def _check_obs_mode(self, k: int, cfg: PPOConfig) -> None:
+        refuse_env_mode(type(self).__name__, k, cfg)
+
+    def _check_config(self, cfg: PPOConfig, c0: PPOConfig) -> None:
+        if _arch_key(cfg) != _arch_key(c0):
+            raise ValueError(f"members must share net_arch and activation ({_arch_key(cfg)} != {_arch_key(c0)})")
+        hidden, act = _arch_key(cfg)
+        if not _in_family(hidden, act):
+            raise ValueError(f"DeployedPopulationPPO trains {LEARNER_FAMILY}, got net_arch {cfg.net_arch} "
+                             f"{cfg.activation}")
+        if (hidden, act) != ((128, 128), "relu") and not cfg.fused_update_arch:
+            raise ValueError("DeployedPopulationPPO needs fused_update_arch for a net other than (128, 128) relu")
+
+    def _workspace_bytes(self, m0: PPO, batch: int) -> int:
+        L = N.need_deployed_population()
+        return int(L.quad_pop_deployed_workspace_bytes(C.byref(m0._fp.arch), C.byref(m0._adam._build()), batch))
+
+    def _create(self, arr, P: int, batch: int) -> C.c_void_p:
+        L = N.need_deployed_population()
+        dep = (N.QuadPopDeploy * P)()
+        for d, m in zip(dep, self.members):
+            d.est = N.QuadVelEst(alpha=None, alpha_all=float(m.cfg.velocity_alpha), max_dt=float(m.cfg.est_max_dt),
+                                 state=_p(m.est_state))
+            d.est_dt = float(m.env.dt)
+        h = C.c_void_p()
+        N.check(L.quad_pop_create_deployed(C.byref(self.members[0]._fp.arch), arr, dep, P, batch,
+                                           int(self.normalize_advantage), C.byref(h)), "quad_pop_create_deployed")
+        return h
+
+    def _start_member(self, m: PPO) -> None:
+        m.last_obs.copy_(m.env.reset())
+        m._start_estimators()
+        m.last_start.fill_(1.0)
+        m._started = True
+
+    def _eval_run(self, i: int, e: QuadVecEnv, res: dict, verr: torch.Tensor) -> N.QuadPolicyRun:
+        run = super()._eval_run(i, e, res, verr)
+        cfg = self.members[i].cfg
+        alpha = cfg.velocity_alpha if self._eval_alpha is None else self._eval_alpha
+        run.obs_mode = N.OBS_DEPLOYED
+        run.est = N.QuadVelEst(alpha=None, alpha_all=float(alpha), max_dt=float(cfg.est_max_dt), state=None)
+        return run
+
+    def evaluate(self, num_episodes: int = 10, seeds: Optional[Sequence[int]] = None,
+                 max_episode_steps: Optional[int] = None,
+                 velocity_alpha: Optional[float] = None) -> List[Optional[dict]]:
+        """PopulationPPO.evaluate with every member's episodes flown on the deployed observation, each at the member's
+        own velocity_alpha and est_max_dt, in one launch: what evaluate.evaluate_episodes(member.policy, ...,
+        obs_mode="deployed", velocity_alpha=alpha) returns for member m. velocity_alpha: one coefficient for all
+        members instead of their own (a policy trained at one alpha flown at another)."""
+        self._eval_alpha = None if velocity_alpha is None else float(velocity_alpha)
+        try:
+            return super().evaluate(num_episodes, seeds, max_episode_steps)
+        finally:
+            self._eval_alpha = None
+
+
+# ((H1, H2), activation) whose 64-member deployed iteration did not take less than half of 64 stand-alone deployed
+# iterations in profiles/deployed_population/bench.json (DESIGN 28, by 18's bar): deployed_population_for keeps them
+# off the population path
+DEPLOYED_POPULATION_KEEP_SERIAL = frozenset()
+
+
+def deployed_population_for(members: Sequence[Tuple[PPOConfig, int]], n_envs: int = 8, env: str = "hover",
+                            wrapper: Optional[str] = None, device=None,
+                            env_kwargs: Optional[dict] = None) -> DeployedPopulationPPO:
+    """population_for for members with obs_mode="deployed": a DeployedPopulationPPO of the members' arch (the arch
+    flags switched on in the configs it gets, for a net other than (128, 128) relu). ValueError for an env-mode member
+    (by index), outside the family, for mixed arches, and for a row the drivers keep off the fused path
+    (ARCH_ROLLOUT_KEEP_TORCH -- every deployed net collects on the family's rollout --, ARCH_UPDATE_KEEP_TORCH,
+    DEPLOYED_POPULATION_KEEP_SERIAL)."""
+    members = list(members)
+    if len(members) < 1:
+        raise ValueError("deployed_population_for needs at least one (PPOConfig, seed)")
+    for k, (cfg, _) in enumerate(members):
+        refuse_env_mode("deployed_population_for", k, cfg)
+    keys = {_arch_key(cfg) for cfg, _ in members}
+    if len(keys) != 1:
+        raise ValueError(f"members must share net_arch and activation, got {sorted(keys)}")
+    (hidden, act), = keys
+    if not _in_family(hidden, act):
+        raise ValueError(f"deployed_population_for trains {LEARNER_FAMILY}, got net_arch {hidden} {act}")
+    small = (hidden, act) == ((128, 128), "relu")
+    c0 = members[0][0]
+    total = c0.n_steps * int(n_envs)
+    batch = int(c0.batch_size) if c0.batch_size is not None else max(1, total // c0.n_minibatches)
+    if (arch_rollout_keeps_torch(hidden, act, n_envs) or (not small and (hidden, act, batch) in ARCH_UPDATE_KEEP_TORCH)
+            or (hidden, act) in DEPLOYED_POPULATION_KEEP_SERIAL):
+        raise ValueError(f"net_arch {hidden} {act} stays off the deployed population path at {n_envs} envs, minibatch "
+                         f"{batch} (it did not beat the path it would replace)")
+    if not small:
+        members = [(replace(cfg, fused_rollout_arch=True, fused_update_arch=True), seed) for cfg, seed in members]
+    return DeployedPopulationPPO(members, n_envs=n_envs, env=env, wrapper=wrapper, device=device,
+                                 env_kwargs=env_kwargs)
